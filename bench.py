@@ -2,6 +2,7 @@
 """Benchmark of the AbX reverse-diffusion sampling hot path on MI355X (BASELINE.json metric: diffusion-steps/sec).
 
   python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--workload L352|6ct7like|6qd7like] [--samples S]
+                  [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run --nproc-per-node N
 ... bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* are read from the environment), or — when WORLD_SIZE is
@@ -14,7 +15,7 @@ resident in HBM when the timed region starts.  value = (samples on all ranks) * 
 Scaling.  The metric is "100 samples of one ~350-residue complex at 1/2/4/8 GPUs": the S = 100 samples are sharded over the
 ranks in contiguous blocks (sampler.shard_sample_ids; 12-13 samples per GPU at N = 8) -> "scaling": "strong" (default).  There
 is no collective inside a step; ONE all-gather of the final results (sampler.gather_results, RCCL over xGMI) runs after the
-timed loop and is reported as `gather_ms`.  `--scaling weak` gives every rank its own S samples instead; at N > 1 the default
+timed loop and is reported as `gather_ms`.  `--scaling weak` gives every rank its own S samples instead; at N > 1 a `--full`
 run also times that variant for a few steps and reports it under "weak" on the same JSON line.
 
 Workloads (abx_amd.synthetic.WORKLOADS): 'L352' (Lab 228 + antigen 124, BASELINE's nominal "~350-res complex", the headline),
@@ -22,9 +23,14 @@ Workloads (abx_amd.synthetic.WORKLOADS): 'L352' (Lab 228 + antigen 124, BASELINE
 Seeded random weights (no trained checkpoint exists offline), ESM disabled, device Philox noise, fp32 compute with float64
 diffuser state as the reference.
 
-Extra objects on the JSON line: "roofline" for the dominant kernel (measured live with HIP events on the launch stream) and
-"cpu_baseline": the oracle (CPU port of the same step) on sample 0 of the same complex, 1 warm-up + 3 timed steps on the
-physical cores of this box, with the HIP-vs-oracle parity of that very call ("parity").
+A plain run sets up, warms up, times the K steps and prints the JSON line.  `--full` adds what the headline does not need, each
+after the timed region: "roofline" for the dominant kernel and the per-kernel view of one more step (measured live with HIP
+events on the launch stream; `--no-op-profile` leaves it out), "cpu_baseline": the oracle (CPU port of the same step) on sample 0
+of the same complex, 1 warm-up + 3 timed steps on the physical cores of this box, with the HIP-vs-oracle parity of that very call
+("parity"; `--no-cpu-baseline` leaves it out), and at N > 1 the weak-scaling run (`--no-weak` leaves it out).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0's samples) as DIR/<name>.npy right after the timed
+region; the inputs are seeded, so two builds run with the same arguments can be compared array by array (dump_outputs).
 """
 import argparse
 import json
@@ -75,6 +81,39 @@ def model_parameter_shapes(cfg):
     from abx_amd.model.abx import ScoreNetwork
     m = ScoreNetwork(cfg.model, None)
     return OrderedDict((k, tuple(v.shape)) for k, v in m.state_dict().items())
+
+
+DUMP_MAX_BYTES = 4 * 10 ** 6        # per array: the 14 arrays of step_outputs stay under 64 MB in all
+DUMP_SAMPLE_SEED = 0
+
+
+def step_outputs(batch, out):
+    """What one step hands its caller: the reverse step's new state, the score network's heads, and the representations and
+    distogram bins that the next call reads as its self-conditioning input."""
+    f, s = out['heads']['folding'], out['heads']['sequence_module']
+    return OrderedDict([
+        ('rigids_t', batch['rigids_t']), ('seq_t', batch['seq_t']),
+        ('rot_score', f['rot_score']), ('trans_score', f['trans_score']), ('rigids', f['rigids']),
+        ('final_atom14_positions', f['final_atom14_positions']), ('final_atom_positions', f['final_atom_positions']),
+        ('angles_sin_cos', f['sidechains'][0]['angles_sin_cos']),
+        ('logits', s['logits']), ('seq_0', s['seq_0']), ('pLDDT', out['heads']['predicted_lddt']['pLDDT']),
+        ('representations_seq', out['representations']['seq']), ('representations_pair', out['representations']['pair']),
+        ('prev_pos', out['_prev_pos']),
+    ])
+
+
+def dump_outputs(arrays, d, max_bytes=DUMP_MAX_BYTES):
+    """Writes every tensor as d/<name>.npy: float64 stays float64, other floats become float32, integers float64 (exact).  A tensor
+    larger than `max_bytes` is written as a fixed sample: the same seeded, sorted row-major element indices for a given shape in
+    every run, taken on the device without a copy of the whole tensor."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        dt = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        k = max_bytes // (8 if dt == torch.float64 else 4)
+        if t.numel() > k:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.numel(), k, replace=False))
+            t = t[tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(idx, tuple(t.shape)))]
+        np.save(os.path.join(d, name + '.npy'), t.detach().to(dt).cpu().numpy())
 
 
 class OpTimer:
@@ -224,9 +263,12 @@ def cpu_baseline(model, D, batch, cfg, L, t_value, timed_steps=3):
     import tempfile
     physical, logical, cpu_model = host_cpu_info()
     # SURVEY §8d asks for the physical cores; on a 2-socket 128-core host the torch CPU path is faster on fewer threads, so the
-    # warm-up step is run at each candidate count and the timed steps use the fastest one (all of it is reported)
-    candidates = sorted({physical, min(physical, 64), min(physical, 32)}, reverse=True)
-    threads = physical
+    # warm-up step is run at each candidate count and the timed steps use the fastest one (all of it is reported).  A thread budget
+    # set in the environment (OMP_NUM_THREADS) caps the candidates: threads beyond the CPUs a job is granted only slow it down
+    budget = os.environ.get('OMP_NUM_THREADS', '').split(',')[0]
+    cap = min(physical, int(budget)) if budget.isdigit() and int(budget) > 0 else physical
+    candidates = sorted({cap, min(cap, 64), min(cap, 32)}, reverse=True)
+    threads = cap
     unit = 'sample-steps/s'
     one = {}
     for k, v in batch.items():
@@ -389,9 +431,13 @@ def main():
     ap.add_argument('--exact-class', default='', help='comma-separated op classes (abx_amd.ops.RANGE_TAGS: tri_attn, pair_transition, '
                     'plane_projection, ...) pinned to the exact fp32-MFMA kernels: the price of a checkpoint whose activations leave the '
                     'split-f16 operand range in that class (the sticky state of ScoreNetwork)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-op-profile', action='store_true')
-    ap.add_argument('--no-weak', action='store_true', help='N > 1: skip the additional weak-scaling measurement')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB')
+    ap.add_argument('--full', action='store_true', help='after the timed region also run the per-kernel op profile + roofline, the CPU '
+                    'oracle baseline with its parity, and at N > 1 the weak-scaling measurement')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU oracle baseline')
+    ap.add_argument('--no-op-profile', action='store_true', help='--full: skip the op profile and roofline')
+    ap.add_argument('--no-weak', action='store_true', help='--full, N > 1: skip the additional weak-scaling measurement')
     ap.add_argument('--launcher-selftest', action='store_true', help='CPU/gloo check of the multi-rank launch path, no GPU work')
     ap.add_argument('--force-collective', action='store_true', help='--gpus 1: still initialise the RCCL process group and run the barrier, the '
                     'MAX all_reduce and the final gather through 1-rank collectives on device tensors (exercises the multi-GPU code '
@@ -399,6 +445,8 @@ def main():
     ap.add_argument('--debug-one-gpu', action='store_true', help='debugging on a 1-GPU box: every rank uses cuda:0 and the gloo backend '
                                                                  '(exercises the whole multi-rank code path; the numbers mean nothing)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(args.gpus, sys.argv[1:])
@@ -511,6 +559,9 @@ def main():
         return elapsed, st
 
     elapsed, st = measure(args.scaling, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0 and st['B'] > 0:
+        # before anything else runs the network: the representations it returned live in buffers that the next call overwrites
+        dump_outputs(step_outputs(st['batch'], st['out']), args.dump_outputs)
     total = st['total']
     value = total * args.steps / elapsed
     per_rank = [len(sampler.shard_sample_ids(total, r, world)) for r in range(world)]
@@ -567,7 +618,7 @@ def main():
         'step_mfma_f32_frac': value / world * algorithmic_flops_per_sample_step(L) / 1e12 / MFMA_F32_PEAK_TF,
     }
 
-    if rank == 0 and not args.no_op_profile and B0 > 0:
+    if args.full and rank == 0 and not args.no_op_profile and B0 > 0:
         # per-KERNEL view of one more step: the three pair-stack op groups run through one C call each in the timed region
         # (abx_tri_mul_fwd / abx_tri_attn_block_fwd / abx_transition_fwd, csrc/blocks.hip); for this instrumented step the engine
         # issues the same kernels in the same order one descriptor at a time, so that every launch gets its own pair of HIP events
@@ -679,10 +730,10 @@ def main():
         result['op_profile_ms'] = [{'op': s[0], 'ms': round(s[1], 3), 'calls': s[2], 'avg_ms': round(s[1] / s[2], 4),
                                     'tflops': (s[3] / (s[1] / 1e3) / 1e12 if s[3] else None)} for s in summ[:40]]
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline(model, D, st['batch'], cfg, L, float(grid[(st['next_k'] + 1) % 99]))
 
-    if world > 1 and args.scaling == 'strong' and not args.no_weak:
+    if args.full and world > 1 and args.scaling == 'strong' and not args.no_weak:
         st = None
         torch.cuda.empty_cache()
         wsteps = max(1, min(args.steps, 3))

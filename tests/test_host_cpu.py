@@ -317,6 +317,28 @@ def test_bench_launches_its_own_ranks():
     assert r['gathered_ids'] == list(range(7)) and r['samples_per_rank'] == [4, 3]
 
 
+def test_bench_dump_outputs_types_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float64 stays float64, float32 and integers are written as float32 / float64, a tensor above the
+    size cap as the same seeded sample of its elements in every run, and a strided tensor is sampled without being copied whole."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(6, 50, 40, generator=g)
+    arrays = {'f64': torch.randn(3, 7, generator=g, dtype=torch.float64), 'i64': torch.arange(12).reshape(3, 4),
+              'big': big, 'big_t': big.transpose(0, 2)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(arrays, str(tmp_path / d), max_bytes=4000)
+    a = {n: np.load(tmp_path / 'a' / (n + '.npy')) for n in arrays}
+    assert a['f64'].dtype == np.float64 and np.array_equal(a['f64'], arrays['f64'].numpy())
+    assert a['i64'].dtype == np.float64 and np.array_equal(a['i64'], np.arange(12.0).reshape(3, 4))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(big.numel(), 1000, replace=False))
+    for n in ('big', 'big_t'):
+        assert a[n].dtype == np.float32 and a[n].shape == (1000,)
+        assert np.array_equal(a[n], np.load(tmp_path / 'b' / (n + '.npy')))
+        assert np.array_equal(a[n], arrays[n].contiguous().reshape(-1).numpy()[idx])      # row-major element indices
+
+
 _WORKER_EMPTY = r'''
 import os, sys, torch, torch.distributed as dist
 sys.path.insert(0, sys.argv[1])

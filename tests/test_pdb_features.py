@@ -119,7 +119,7 @@ def test_ab_metrics_rmsd_and_aar():
 
 
 @pytest.mark.parametrize('code', ['6ct7', '6qd7'])
-def test_npz_entry_of_a_name_idx_list_matches_reference(code):
+def test_npz_entry_of_a_name_idx_list_matches_reference(code, tmp_path):
     """The --name_idx / --data_dir path of the reference's inference.py (abx/data/dataset.py:90-214): <data_dir>/<name>.npz in the
     make_pdb_npz schema -> the collated batch.  Against the reference's own get_structure_label_npz / Patch_Around_Anchor / collate_fn
     outputs on the same arrays (pdb_<code>.npz 'batch.*') and against the raw-PDB route."""
@@ -141,15 +141,15 @@ def test_npz_entry_of_a_name_idx_list_matches_reference(code):
         if torch.is_tensor(v):
             assert torch.equal(v, p[k]), k
     with pytest.raises(ValueError, match='make_pdb_npz'):
-        np.savez(os.path.join('/tmp', 'abx_bad_entry.npz'), foo=np.zeros(3))
-        A.load_complex_npz('/tmp', 'abx_bad_entry')
+        np.savez(str(tmp_path / 'abx_bad_entry.npz'), foo=np.zeros(3))
+        A.load_complex_npz(str(tmp_path), 'abx_bad_entry')
 
 
-def test_model_features_json():
+def test_model_features_json(tmp_path):
     """read_model_features: generate_area / optimize_steps of the reference's feature-pipeline JSON (config_data_feature.json layout)."""
     import json
     from abx_amd import design
-    path = '/tmp/abx_feats.json'
+    path = str(tmp_path / 'abx_feats.json')
     json.dump([["make_to_device", {"fields": ["seq"], "device": "%(device)s"}], ["make_gt_frames", {}],
                ["make_diffuser_features", {"generate_area": "H3", "optimize_steps": [4, 8]}]], open(path, 'w'))
     assert design.read_model_features(path) == ('H3', [4, 8])

@@ -4,10 +4,10 @@
 TAG=${1:-r04}
 export TMPDIR=/tmp
 O=gpurun_out/$TAG; mkdir -p $O
-python bench.py --steps 4 --warmup 2 > $O/bench_L352.json 2> $O/bench_L352.err
-for b in 50 25 13 12 1; do python bench.py --samples $b --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_b$b.json 2>> $O/bench.err; done
-python bench.py --workload 6ct7like --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_6ct7like.json 2>> $O/bench.err
-python bench.py --workload 6qd7like --samples 32 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_6qd7like.json 2>> $O/bench.err
+python bench.py --steps 4 --warmup 2 --full > $O/bench_L352.json 2> $O/bench_L352.err
+for b in 50 25 13 12 1; do python bench.py --samples $b --steps 6 --warmup 2 --full --no-cpu-baseline > $O/bench_b$b.json 2>> $O/bench.err; done
+python bench.py --workload 6ct7like --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench_6ct7like.json 2>> $O/bench.err
+python bench.py --workload 6qd7like --samples 32 --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench_6qd7like.json 2>> $O/bench.err
 rocprofv3 --kernel-trace --stats -d $O/prof -o x -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-op-profile > $O/prof.log 2>&1
 python tools/rocprof_summary.py $(find $O/prof -name "*results.db" | head -1) $O/kernel_stats.csv
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-op-profile > $O/pmc_fetch.log 2>&1
