@@ -134,8 +134,12 @@ class AbxTriMulPack(C.Structure):
     _fields_ = [('glu', AbxLinearPack), ('out', AbxLinearPack), ('gate', AbxLinearPack)]
 
 
+class AbxTriRowPack(C.Structure):
+    _fields_ = [('planes', C.c_void_p), ('csum', c_f), ('bias', c_f), ('b_exp', I), ('H', I)]
+
+
 class AbxTriAttnPack(C.Structure):
-    _fields_ = [('qkv', AbxLinearPack), ('gate', AbxLinearPack), ('pair', AbxLinearPack), ('out', AbxLinearPack)]
+    _fields_ = [('qkv', AbxLinearPack), ('gate', AbxLinearPack), ('pair', AbxLinearPack), ('out', AbxLinearPack), ('row', AbxTriRowPack)]
 
 
 class AbxScoreArgs(C.Structure):
@@ -198,6 +202,10 @@ _PROTOS = {
     'abx_row_stats': (I, [c_f, LL, LL, LL, I, I, I, F, c_f, _S]),
     'abx_layernorm': (I, [c_f, LL, LL, I, c_f, c_f, F, c_f, LL, c_f, LL, _S]),
     'abx_tri_attn_fwd': (I, [C.POINTER(AbxTriAttn), _S]),
+    'abx_tri_rowpack_bytes': (LL, []),
+    'abx_tri_rowpack': (I, [C.POINTER(AbxLinearPack), c_f, C.POINTER(AbxTriRowPack), _S]),
+    'abx_tri_attn_rowfused_ok': (I, [I]),
+    'abx_tri_attn_rowfused_fwd': (I, [C.POINTER(AbxTriAttn), c_f, LL, LL, LL, C.POINTER(AbxTriRowPack), I, _S]),
     'abx_seq_attn_fwd': (I, [c_f, c_f, c_f, c_f, c_f, I, I, I, I, F, _S]),
     'abx_ipa_pack': (I, [c_f, c_f, c_f, c_f, c_f, c_f, I, I, F, _S]),
     'abx_ipa_attn': (I, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, I, I, _S]),

@@ -11,6 +11,11 @@
 //     O^T[d][q]   += sum_key V[key][d] * P[key][q]    (P fragments feed the B operand straight from registers)
 // The orientation (starting / ending node) is expressed only through strides; no transposed copy of the pair stack.
 //
+// abx_tri_attn_rowfused_fwd — the same attention for rows of L <= 352 with the q | k | v projection of the row inside the kernel
+// (tri_attn8_rowfused_kernel below: phase P projects [k | v | q] of the row's head from LayerNorm(z[b, s]) with the arithmetic of the
+// split-f16 GEMM straight into the K / V planes in LDS and the Q fragments in registers, phase A is the computing-wave body of tri_attn8):
+// q | k | v never travel through HBM; bit-identical to the projection GEMM followed by abx_tri_attn_fwd.
+//
 // abx_seq_attn_fwd — sequence attention with 32-head pair bias (seqformer.py:314-356, split_first=False :278-281):
 // lanes are keys so that the bias rows are read coalesced, K/V of the (b, h) pair in LDS.
 #include <stdlib.h>
@@ -672,6 +677,244 @@ __global__ __launch_bounds__(NTH) void tri_attn4_kernel(const AbxTriAttn a) {
     probe.finish();
 }
 
+// One row of tri_attn8: the computing-wave body from the running softmax state to the stored output rows, shared by tri_attn8_kernel (key chunks
+// double-buffered by its producer wave, one block barrier per chunk) and tri_attn8_rowfused_kernel (the whole row is one resident chunk: no
+// barrier inside), so that the two cannot drift apart.  qf / boff: the query fragments and bias offsets of the wave's two query tiles
+// (tri_attn8_kernel loads and splits q, the row-fused kernel takes them from its projection accumulators); cc: chunks consumed so far
+// (chunk cc sits in buffer cc & 1).
+struct Tri8Row { long long base; const float* km; const float* biasb; int b, h, s, part; };
+template <int KC4, bool BVEC, bool CHUNK_BARRIER, class Stamp>
+__device__ __forceinline__ void tri8_row_compute(const AbxTriAttn& a, const Tri8Row& cur, const char* lds, const float* Msb, int& cc, const int nchunk,
+                                                 const f16x8 (&qf)[2][4], const unsigned (&boff)[2], const bool any_masked, const bool has_tile,
+                                                 const int qtA, const int nqt, const int lane, const int koff0, const int koffc, const int voff, Stamp&& stamp) {
+    constexpr int PLN = KC4 * RST, BUF4 = 4 * PLN;
+    constexpr float SCL = 128.0f, ISCL = 1.0f / 128.0f, PEXP = 8.0f;
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+    using I3 = std::integral_constant<int, 3>; using I4 = std::integral_constant<int, 4>;
+    const int L = a.L;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lq = lane & 15, g = lane >> 4;
+    // running maximum (in accumulator units) and the running sum of the softmax weights: the sums come off the MATRIX pipe as a
+    // 49th output channel (A operand = ones: every row of ls is the column sum of the weight pieces the PV product uses) - 8 MFMA
+    // issue slots per tile pair instead of the 48 VALU ones of the add tree + the four-lane reduction; the kernel is issue bound
+    float mr[2] = {-INFINITY, -INFINITY};
+    f32x4 ls[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+    f32x4 oo[2][3];
+#pragma unroll
+    for (int X = 0; X < 2; ++X)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) oo[X][d] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // logits of the key tile in flight: bias -> 2^7 (bias log2 e + S^T) -> softmax weights P 2^8 -> (the next tile's bias)
+    f32x4 sc[2][4];
+    __amdgpu_buffer_rsrc_t brsrc;
+    {
+        const unsigned long long bu = reinterpret_cast<unsigned long long>(cur.biasb);
+        // (readfirstlane returns int: through unsigned, or a low half with bit 31 set sign-extends into the high half)
+        const unsigned long long bu_u = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(bu >> 32)) << 32) |
+                                        (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)bu);
+        brsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(bu_u), 0,
+                                                  __builtin_amdgcn_readfirstlane((int)(L * a.bias_sq * 4)), 0x00020000);
+    }
+    // bias of sub-blocks [S0, S1) of the key tile that starts at key k_abs of the row, into sc
+    auto bias_issue = [&](int k_abs, auto s0_, auto s1_) __attribute__((always_inline)) {
+        constexpr int S0 = decltype(s0_)::value, S1 = decltype(s1_)::value;
+        if (BVEC) {
+            // buffer loads: the pair's (L, Lp) bias as the resource (wave-uniform descriptor), (query row, key) in the per-lane 32-bit
+            // offset, the sub-block as immediate: no 64-bit vector address arithmetic.  Keys beyond the padded row read the next row's
+            // floats (beyond the matrix: the range check returns 0): replaced by the -inf clamp
+            // (the tile's first key goes into the per-lane offset, not the scalar one: only the former is range-checked)
+#pragma unroll
+            for (int X = 0; X < 2; ++X) {
+                const unsigned vo = boff[X] + (unsigned)k_abs * 4u;
+#pragma unroll
+                for (int sub = S0; sub < S1; ++sub)
+                    sc[X][sub] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brsrc, vo + sub * 64, 0, 0));
+            }
+        } else {
+#pragma unroll
+            for (int X = 0; X < 2; ++X)
+#pragma unroll
+                for (int sub = S0; sub < S1; ++sub) {
+                    const int kq = k_abs + sub * 16 + g * 4;
+                    const float* brow = cur.biasb ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(cur.biasb) + boff[X]) - g * 4 : nullptr;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        sc[X][sub][r] = brow ? brow[(long long)min(kq + r, L - 1) * a.bias_sk] : 0.f;
+                }
+        }
+    };
+    if (has_tile) bias_issue(0, I0{}, I4{});
+    if (wave == 0) stamp();
+
+    for (int ch = 0; ch < nchunk; ++ch, ++cc) {
+        const int c0 = ch * KC4, buf = cc & 1;
+        const int nkeys = min(KC4, L - c0);
+        const int nkt = (nkeys + 63) / 64;
+        const bool more = ch + 1 < nchunk;
+        const char* Kp = lds + buf * BUF4;
+        const char* Vp = Kp + 2 * PLN;
+        const float* Ms = Msb + buf * KC4;
+        if (has_tile)
+        for (int kt = 0; kt < nkt; ++kt) {
+            const int k0 = kt * 64;
+            const bool full = nkeys - k0 > 32;              // otherwise: sub-blocks 0, 1 and the first PV step only
+            // next key tile of this row (its bias is requested under the PV work below): first key, or -1
+            const int k_next = kt + 1 < nkt ? c0 + k0 + 64 : (more ? c0 + KC4 : -1);
+            if ((BVEC || cur.biasb) && !a.bias_log2) {      // (bias_log2: the projection applied the factor, AbxGemm.alpha)
+#pragma unroll
+                for (int X = 0; X < 2; ++X)
+#pragma unroll
+                    for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) sc[X][sub][r] *= LOG2E * SCL;
+            }
+            // ---- S^T tiles (accumulators start from the bias): terms a1 p0, a0 p1, a0 p0, smallest first
+            auto qk = [&](auto sub_) __attribute__((always_inline)) {
+                constexpr int sub = decltype(sub_)::value;
+                const char* kr = Kp + (k0 + sub * 16) * RST;
+                const f16x8 r0 = *reinterpret_cast<const f16x8*>(kr + koff0);
+                const f16x8 r1 = *reinterpret_cast<const f16x8*>(kr + koff0 + PLN);
+                const f16x8 rc = *reinterpret_cast<const f16x8*>(kr + koffc);
+#pragma unroll
+                for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r0, qf[X][1], sc[X][sub], 0, 0, 0);
+#pragma unroll
+                for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(rc, qf[X][3], sc[X][sub], 0, 0, 0);
+#pragma unroll
+                for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r1, qf[X][0], sc[X][sub], 0, 0, 0);
+#pragma unroll
+                for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(rc, qf[X][2], sc[X][sub], 0, 0, 0);
+#pragma unroll
+                for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r0, qf[X][0], sc[X][sub], 0, 0, 0);
+            };
+            qk(I0{});
+            qk(I1{});
+            if (full) {
+                qk(I2{});
+                qk(I3{});
+            } else {
+#pragma unroll
+                for (int X = 0; X < 2; ++X) {
+                    sc[X][2] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                    sc[X][3] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                }
+            }
+            // ---- key clamps (masked / padded keys), online softmax (base 2) of this lane's query columns
+            if (any_masked || k0 + 64 > nkeys) {
+#pragma unroll
+                for (int sub = 0; sub < 4; ++sub) {
+                    const f32x4 mk = *reinterpret_cast<const f32x4*>(Ms + k0 + sub * 16 + g * 4);
+#pragma unroll
+                    for (int X = 0; X < 2; ++X)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) sc[X][sub][r] = vmin(sc[X][sub][r], mk[r]);
+                }
+            }
+#pragma unroll
+            for (int X = 0; X < 2; ++X) {
+                const float m0 = vmax3(sc[X][0][0], sc[X][0][1], sc[X][0][2]), m1 = vmax3(sc[X][0][3], sc[X][1][0], sc[X][1][1]);
+                const float m2 = vmax3(sc[X][1][2], sc[X][1][3], sc[X][2][0]), m3 = vmax3(sc[X][2][1], sc[X][2][2], sc[X][2][3]);
+                const float m4 = vmax3(sc[X][3][0], sc[X][3][1], sc[X][3][2]);
+                const float mx = quad_max(vmax(vmax3(m0, m1, m2), vmax3(m3, m4, sc[X][3][3])));
+                const float m_new = vmax(mr[X], mx);
+                const float alpha = __builtin_amdgcn_exp2f((mr[X] - m_new) * ISCL);
+                const float m_sh = PEXP - m_new * ISCL;
+#pragma unroll
+                for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sc[X][sub][r] = __builtin_amdgcn_exp2f(fmaf(sc[X][sub][r], ISCL, m_sh));     // P 2^8
+                mr[X] = m_new;
+                if (!__all(alpha == 1.0f)) {                    // O^T columns are the queries: lane-local rescale
+#pragma unroll
+                    for (int d = 0; d < 3; ++d)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) oo[X][d][r] *= alpha;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ls[X][r] *= alpha;
+                }
+            }
+            // ---- O^T += V^T P: one step contracts the 32 keys of two sub-blocks; the bias of the next tile goes into the
+            // registers the weights leave
+            auto pv = [&](auto m_) __attribute__((always_inline)) {
+                constexpr int m = decltype(m_)::value;
+                f16x8 pa[2][2];
+#pragma unroll
+                for (int X = 0; X < 2; ++X) {
+                    unsigned p0[4], p1[4];
+                    split2h_ns(sc[X][2 * m][0], sc[X][2 * m][1], p0[0], p1[0]);
+                    split2h_ns(sc[X][2 * m][2], sc[X][2 * m][3], p0[1], p1[1]);
+                    split2h_ns(sc[X][2 * m + 1][0], sc[X][2 * m + 1][1], p0[2], p1[2]);
+                    split2h_ns(sc[X][2 * m + 1][2], sc[X][2 * m + 1][3], p0[3], p1[3]);
+                    pa[X][0] = __builtin_bit_cast(f16x8, u32x4{p0[0], p0[1], p0[2], p0[3]});
+                    pa[X][1] = __builtin_bit_cast(f16x8, u32x4{p1[0], p1[1], p1[2], p1[3]});
+                }
+                if (k_next >= 0) bias_issue(k_next, std::integral_constant<int, 2 * m>{}, std::integral_constant<int, 2 * m + 2>{});
+                {
+                    const _Float16 one = (_Float16)1.0f;
+                    const f16x8 ones = {one, one, one, one, one, one, one, one};
+#pragma unroll
+                    for (int X = 0; X < 2; ++X) ls[X] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, pa[X][1], ls[X], 0, 0, 0);
+#pragma unroll
+                    for (int X = 0; X < 2; ++X) ls[X] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, pa[X][0], ls[X], 0, 0, 0);
+                }
+                const char* vr = Vp + (k0 + m * 32) * RST + voff;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    f16x8 vb[2];
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) {
+                        const s16x4 lo = lds_tr16(vr + p * PLN + d * 32);
+                        const s16x4 hi = lds_tr16(vr + p * PLN + d * 32 + 16 * RST);
+                        vb[p] = __builtin_bit_cast(f16x8, s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+                    }
+#pragma unroll
+                    for (int X = 0; X < 2; ++X) oo[X][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vb[0], pa[X][1], oo[X][d], 0, 0, 0);
+#pragma unroll
+                    for (int X = 0; X < 2; ++X) oo[X][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vb[1], pa[X][0], oo[X][d], 0, 0, 0);
+#pragma unroll
+                    for (int X = 0; X < 2; ++X) oo[X][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vb[0], pa[X][0], oo[X][d], 0, 0, 0);
+                }
+            };
+            pv(I0{});
+            if (full) {
+                pv(I1{});
+            } else if (k_next >= 0) {
+                bias_issue(k_next, I2{}, I4{});             // (a half tile is the last of its row: not reached)
+            }
+        }
+        if (wave == 0) stamp();
+        if (CHUNK_BARRIER) __syncthreads();
+        if (wave == 0) stamp();
+    }
+    bool bad = false;           // range safety (AbxTriAttn.range_flag): a key / value / query / gate beyond the split ranges, or not finite
+    // ---- normalise, gate, store.  O^T layout: column = query lq, rows d = dblk*16 + g*4 + r
+#pragma unroll
+    for (int X = 0; X < 2; ++X) {
+        const int qrow = (qtA + X) * 16 + lq;
+        if (qtA + X >= nqt || qrow >= L) continue;
+        const float inv = 0.0625f / ls[X][0];               // O^T accumulated (16 v) (P 2^8), ls = sum P 2^8 (every row)
+        const long long go = cur.base + (long long)qrow * a.sl;
+        float* op = a.out + (long long)cur.b * a.ob + (long long)cur.s * a.os + (long long)qrow * a.ol + cur.h * TD;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const int dd = d * 16 + g * 4;
+            f32x4 v = oo[X][d];
+            if (a.gate) {
+                const f32x4 gv = *reinterpret_cast<const f32x4*>(a.gate + go + dd);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = v[r] * inv * sigmoidf_(gv[r]);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] *= inv;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bad |= __builtin_amdgcn_classf(v[r], 0x207);
+            *reinterpret_cast<f32x4*>(op + dd) = v;
+        }
+    }
+    if (a.range_flag && __any(bad) && lane == 0) atomicOr(a.range_flag, a.range_tag);
+}
+
+
 // ---- triangle attention, paired query tiles (split-f16) ----------------------------------------------------------------------
 // Same (b, row, head) decomposition and LDS image as tri_attn4_kernel (K / V of a row staged in key chunks as two f16 planes each,
 // swapped S^T = K Q^T, transposing V reads, online base-2 softmax per query column).  What is different:
@@ -724,7 +967,7 @@ __global__ __launch_bounds__(NTH) void tri_attn8_kernel(const AbxTriAttn a) {
     const int per_vp = rows_g * a.q_parts;
     const int nvp = a.B * a.H * G;
     const long long nslots = (long long)((nvp - xcd + 7) / 8) * per_vp;          // slots of this XCD
-    struct Row { long long base; const float* km; const float* biasb; int b, h, s, part; };
+    using Row = Tri8Row;
     auto decode = [&](long long slot, Row& r) __attribute__((always_inline)) -> bool {
         const int sp = (int)(slot % per_vp), vp = (int)(slot / per_vp) * 8 + xcd;
         const int bh = vp / G;
@@ -751,8 +994,7 @@ __global__ __launch_bounds__(NTH) void tri_attn8_kernel(const AbxTriAttn a) {
     const int nchunk = (L + KC4 - 1) / KC4;
     const int nqt_row = (L + 15) / 16, tpp = (nqt_row + a.q_parts - 1) / a.q_parts;
 
-    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>; using I4 = std::integral_constant<int, 4>;
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
 
     if (wave == NCW) {
         // ================= producer wave: K / V of the chunk after the one being computed, across row boundaries ==============
@@ -931,7 +1173,6 @@ __global__ __launch_bounds__(NTH) void tri_attn8_kernel(const AbxTriAttn a) {
     // 2^-25 absolute error is far below the rounding of the neighbouring products), so the three product terms a1 p0 + a0 p1 + a0 p0
     // use the stored planes as they are
     const float qscale = a.scale * LOG2E * 8.0f;
-    constexpr float SCL = 128.0f, ISCL = 1.0f / 128.0f, PEXP = 8.0f;
     const int koff0 = lq * RST + g * 16;                                  // K fragment, channels 8g .. (plane p: + p PLN)
     const int koffc = lq * RST + (g >> 1) * PLN + 64 + (g & 1) * 16;      // channels 32 + 8(g&1) .. of plane g >> 1
     const int voff = (4 * g + (lq >> 2)) * RST + (lq & 3) * 8;            // transposing V reads (see tri_attn4_kernel)
@@ -983,224 +1224,8 @@ __global__ __launch_bounds__(NTH) void tri_attn8_kernel(const AbxTriAttn a) {
             qf[X][2] = __builtin_bit_cast(f16x8, u32x4{p0[0], p0[1], p0[2], p0[3]});
             qf[X][3] = g < 2 ? __builtin_bit_cast(f16x8, u32x4{p1[0], p1[1], p1[2], p1[3]}) : __builtin_bit_cast(f16x8, u32x4{0u, 0u, 0u, 0u});
         }
-        // running maximum (in accumulator units) and the running sum of the softmax weights: the sums come off the MATRIX pipe as a
-        // 49th output channel (A operand = ones: every row of ls is the column sum of the weight pieces the PV product uses) - 8 MFMA
-        // issue slots per tile pair instead of the 48 VALU ones of the add tree + the four-lane reduction; the kernel is issue bound
-        float mr[2] = {-INFINITY, -INFINITY};
-        f32x4 ls[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-        f32x4 oo[2][3];
-#pragma unroll
-        for (int X = 0; X < 2; ++X)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) oo[X][d] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // logits of the key tile in flight: bias -> 2^7 (bias log2 e + S^T) -> softmax weights P 2^8 -> (the next tile's bias)
-        f32x4 sc[2][4];
-        __amdgpu_buffer_rsrc_t brsrc;
-        {
-            const unsigned long long bu = reinterpret_cast<unsigned long long>(cur.biasb);
-            // (readfirstlane returns int: through unsigned, or a low half with bit 31 set sign-extends into the high half)
-            const unsigned long long bu_u = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(bu >> 32)) << 32) |
-                                            (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)bu);
-            brsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(bu_u), 0,
-                                                      __builtin_amdgcn_readfirstlane((int)(L * a.bias_sq * 4)), 0x00020000);
-        }
-        // bias of sub-blocks [S0, S1) of the key tile that starts at key k_abs of the row, into sc
-        auto bias_issue = [&](int k_abs, auto s0_, auto s1_) __attribute__((always_inline)) {
-            constexpr int S0 = decltype(s0_)::value, S1 = decltype(s1_)::value;
-            if (BVEC) {
-                // buffer loads: the pair's (L, Lp) bias as the resource (wave-uniform descriptor), (query row, key) in the per-lane 32-bit
-                // offset, the sub-block as immediate: no 64-bit vector address arithmetic.  Keys beyond the padded row read the next row's
-                // floats (beyond the matrix: the range check returns 0): replaced by the -inf clamp
-                // (the tile's first key goes into the per-lane offset, not the scalar one: only the former is range-checked)
-#pragma unroll
-                for (int X = 0; X < 2; ++X) {
-                    const unsigned vo = boff[X] + (unsigned)k_abs * 4u;
-#pragma unroll
-                    for (int sub = S0; sub < S1; ++sub)
-                        sc[X][sub] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brsrc, vo + sub * 64, 0, 0));
-                }
-            } else {
-#pragma unroll
-                for (int X = 0; X < 2; ++X)
-#pragma unroll
-                    for (int sub = S0; sub < S1; ++sub) {
-                        const int kq = k_abs + sub * 16 + g * 4;
-                        const float* brow = cur.biasb ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(cur.biasb) + boff[X]) - g * 4 : nullptr;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            sc[X][sub][r] = brow ? brow[(long long)min(kq + r, L - 1) * a.bias_sk] : 0.f;
-                    }
-            }
-        };
-        if (has_tile) bias_issue(0, I0{}, I4{});
-        if (wave == 0) STAMP()
-
-        for (int ch = 0; ch < nchunk; ++ch, ++cc) {
-            const int c0 = ch * KC4, buf = cc & 1;
-            const int nkeys = min(KC4, L - c0);
-            const int nkt = (nkeys + 63) / 64;
-            const bool more = ch + 1 < nchunk;
-            const char* Kp = lds + buf * BUF4;
-            const char* Vp = Kp + 2 * PLN;
-            const float* Ms = Msb + buf * KC4;
-            if (has_tile)
-            for (int kt = 0; kt < nkt; ++kt) {
-                const int k0 = kt * 64;
-                const bool full = nkeys - k0 > 32;              // otherwise: sub-blocks 0, 1 and the first PV step only
-                // next key tile of this row (its bias is requested under the PV work below): first key, or -1
-                const int k_next = kt + 1 < nkt ? c0 + k0 + 64 : (more ? c0 + KC4 : -1);
-                if ((BVEC || cur.biasb) && !a.bias_log2) {      // (bias_log2: the projection applied the factor, AbxGemm.alpha)
-#pragma unroll
-                    for (int X = 0; X < 2; ++X)
-#pragma unroll
-                        for (int sub = 0; sub < 4; ++sub)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) sc[X][sub][r] *= LOG2E * SCL;
-                }
-                // ---- S^T tiles (accumulators start from the bias): terms a1 p0, a0 p1, a0 p0, smallest first
-                auto qk = [&](auto sub_) __attribute__((always_inline)) {
-                    constexpr int sub = decltype(sub_)::value;
-                    const char* kr = Kp + (k0 + sub * 16) * RST;
-                    const f16x8 r0 = *reinterpret_cast<const f16x8*>(kr + koff0);
-                    const f16x8 r1 = *reinterpret_cast<const f16x8*>(kr + koff0 + PLN);
-                    const f16x8 rc = *reinterpret_cast<const f16x8*>(kr + koffc);
-#pragma unroll
-                    for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r0, qf[X][1], sc[X][sub], 0, 0, 0);
-#pragma unroll
-                    for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(rc, qf[X][3], sc[X][sub], 0, 0, 0);
-#pragma unroll
-                    for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r1, qf[X][0], sc[X][sub], 0, 0, 0);
-#pragma unroll
-                    for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(rc, qf[X][2], sc[X][sub], 0, 0, 0);
-#pragma unroll
-                    for (int X = 0; X < 2; ++X) sc[X][sub] = __builtin_amdgcn_mfma_f32_16x16x32_f16(r0, qf[X][0], sc[X][sub], 0, 0, 0);
-                };
-                qk(I0{});
-                qk(I1{});
-                if (full) {
-                    qk(I2{});
-                    qk(I3{});
-                } else {
-#pragma unroll
-                    for (int X = 0; X < 2; ++X) {
-                        sc[X][2] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                        sc[X][3] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                    }
-                }
-                // ---- key clamps (masked / padded keys), online softmax (base 2) of this lane's query columns
-                if (any_masked || k0 + 64 > nkeys) {
-#pragma unroll
-                    for (int sub = 0; sub < 4; ++sub) {
-                        const f32x4 mk = *reinterpret_cast<const f32x4*>(Ms + k0 + sub * 16 + g * 4);
-#pragma unroll
-                        for (int X = 0; X < 2; ++X)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) sc[X][sub][r] = vmin(sc[X][sub][r], mk[r]);
-                    }
-                }
-#pragma unroll
-                for (int X = 0; X < 2; ++X) {
-                    const float m0 = vmax3(sc[X][0][0], sc[X][0][1], sc[X][0][2]), m1 = vmax3(sc[X][0][3], sc[X][1][0], sc[X][1][1]);
-                    const float m2 = vmax3(sc[X][1][2], sc[X][1][3], sc[X][2][0]), m3 = vmax3(sc[X][2][1], sc[X][2][2], sc[X][2][3]);
-                    const float m4 = vmax3(sc[X][3][0], sc[X][3][1], sc[X][3][2]);
-                    const float mx = quad_max(vmax(vmax3(m0, m1, m2), vmax3(m3, m4, sc[X][3][3])));
-                    const float m_new = vmax(mr[X], mx);
-                    const float alpha = __builtin_amdgcn_exp2f((mr[X] - m_new) * ISCL);
-                    const float m_sh = PEXP - m_new * ISCL;
-#pragma unroll
-                    for (int sub = 0; sub < 4; ++sub)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) sc[X][sub][r] = __builtin_amdgcn_exp2f(fmaf(sc[X][sub][r], ISCL, m_sh));     // P 2^8
-                    mr[X] = m_new;
-                    if (!__all(alpha == 1.0f)) {                    // O^T columns are the queries: lane-local rescale
-#pragma unroll
-                        for (int d = 0; d < 3; ++d)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) oo[X][d][r] *= alpha;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) ls[X][r] *= alpha;
-                    }
-                }
-                // ---- O^T += V^T P: one step contracts the 32 keys of two sub-blocks; the bias of the next tile goes into the
-                // registers the weights leave
-                auto pv = [&](auto m_) __attribute__((always_inline)) {
-                    constexpr int m = decltype(m_)::value;
-                    f16x8 pa[2][2];
-#pragma unroll
-                    for (int X = 0; X < 2; ++X) {
-                        unsigned p0[4], p1[4];
-                        split2h_ns(sc[X][2 * m][0], sc[X][2 * m][1], p0[0], p1[0]);
-                        split2h_ns(sc[X][2 * m][2], sc[X][2 * m][3], p0[1], p1[1]);
-                        split2h_ns(sc[X][2 * m + 1][0], sc[X][2 * m + 1][1], p0[2], p1[2]);
-                        split2h_ns(sc[X][2 * m + 1][2], sc[X][2 * m + 1][3], p0[3], p1[3]);
-                        pa[X][0] = __builtin_bit_cast(f16x8, u32x4{p0[0], p0[1], p0[2], p0[3]});
-                        pa[X][1] = __builtin_bit_cast(f16x8, u32x4{p1[0], p1[1], p1[2], p1[3]});
-                    }
-                    if (k_next >= 0) bias_issue(k_next, std::integral_constant<int, 2 * m>{}, std::integral_constant<int, 2 * m + 2>{});
-                    {
-                        const _Float16 one = (_Float16)1.0f;
-                        const f16x8 ones = {one, one, one, one, one, one, one, one};
-#pragma unroll
-                        for (int X = 0; X < 2; ++X) ls[X] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, pa[X][1], ls[X], 0, 0, 0);
-#pragma unroll
-                        for (int X = 0; X < 2; ++X) ls[X] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ones, pa[X][0], ls[X], 0, 0, 0);
-                    }
-                    const char* vr = Vp + (k0 + m * 32) * RST + voff;
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) {
-                        f16x8 vb[2];
-#pragma unroll
-                        for (int p = 0; p < 2; ++p) {
-                            const s16x4 lo = lds_tr16(vr + p * PLN + d * 32);
-                            const s16x4 hi = lds_tr16(vr + p * PLN + d * 32 + 16 * RST);
-                            vb[p] = __builtin_bit_cast(f16x8, s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-                        }
-#pragma unroll
-                        for (int X = 0; X < 2; ++X) oo[X][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vb[0], pa[X][1], oo[X][d], 0, 0, 0);
-#pragma unroll
-                        for (int X = 0; X < 2; ++X) oo[X][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vb[1], pa[X][0], oo[X][d], 0, 0, 0);
-#pragma unroll
-                        for (int X = 0; X < 2; ++X) oo[X][d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vb[0], pa[X][0], oo[X][d], 0, 0, 0);
-                    }
-                };
-                pv(I0{});
-                if (full) {
-                    pv(I1{});
-                } else if (k_next >= 0) {
-                    bias_issue(k_next, I2{}, I4{});             // (a half tile is the last of its row: not reached)
-                }
-            }
-            if (wave == 0) STAMP()
-            __syncthreads();
-            if (wave == 0) STAMP()
-        }
-        bool bad = false;           // range safety (AbxTriAttn.range_flag): a key / value / query / gate beyond the split ranges, or not finite
-        // ---- normalise, gate, store.  O^T layout: column = query lq, rows d = dblk*16 + g*4 + r
-#pragma unroll
-        for (int X = 0; X < 2; ++X) {
-            const int qrow = (qtA + X) * 16 + lq;
-            if (qtA + X >= nqt || qrow >= L) continue;
-            const float inv = 0.0625f / ls[X][0];               // O^T accumulated (16 v) (P 2^8), ls = sum P 2^8 (every row)
-            const long long go = cur.base + (long long)qrow * a.sl;
-            float* op = a.out + (long long)cur.b * a.ob + (long long)cur.s * a.os + (long long)qrow * a.ol + cur.h * TD;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const int dd = d * 16 + g * 4;
-                f32x4 v = oo[X][d];
-                if (a.gate) {
-                    const f32x4 gv = *reinterpret_cast<const f32x4*>(a.gate + go + dd);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = v[r] * inv * sigmoidf_(gv[r]);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] *= inv;
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) bad |= __builtin_amdgcn_classf(v[r], 0x207);
-                *reinterpret_cast<f32x4*>(op + dd) = v;
-            }
-        }
-        if (a.range_flag && __any(bad) && lane == 0) atomicOr(a.range_flag, a.range_tag);
+        tri8_row_compute<KC4, BVEC, true>(a, cur, lds, Msb, cc, nchunk, qf, boff, any_masked, has_tile, qtA, nqt, lane, koff0, koffc, voff,
+                                          [&]() __attribute__((always_inline)) { STAMP() });
         if (wave == 0) STAMP()
 #ifdef TRI8_STAMP
         ++st_row;
@@ -1209,6 +1234,396 @@ __global__ __launch_bounds__(NTH) void tri_attn8_kernel(const AbxTriAttn a) {
     }
 #undef STAMP
     probe.finish();
+}
+
+template <int I0_, int I1_, class F> __device__ __forceinline__ void tri_static_for(F&& f) {
+    if constexpr (I0_ < I1_) {
+        f(std::integral_constant<int, I0_>{});
+        tri_static_for<I0_ + 1, I1_>(f);
+    }
+}
+
+// ---- triangle attention with the q | k | v projection of the row inside (split-f16) ------------------------------------------------
+// tri_attn8_kernel reads q | k | v of a pair row (b, s) from memory, where the LayerNorm -> Linear projection (gemm_as.hip) has just put
+// them: 576 fp32 per pair position written and read back, 57 GB per launch at 100 samples of L = 352, for values only this row's
+// attention consumes (seqformer.py:527-548).  Here a slot (b, row s, head h) has two phases:
+//   P  wave w projects the 32 positions 32 w .. 32 w + 31 of the row (its two query tiles of phase A): [k_h | v_h | q_h] =
+//      LN(z[b, s, l, :]) W_h with the arithmetic of gemm_as / gemm3_mainloop - the pieces of split2h_mix on the shifted row, the shifted
+//      statistics summed in k-tile order, the terms a1 p2, a0 p1, a0 p0 per k-step, v_mfma_f32_32x32x16_f16, the folded-LayerNorm epilogue
+//      rs (acc - dmean csum / cs) + bias - with the operands SWAPPED as in gemm3_mlp_block: a lane holds ONE position and 16 channels of
+//      a 32-column tile, so the row statistics are lane-local.  The walk is k-group outer: the wave holds the pieces of four k-tiles (32
+//      registers; all twelve - 96 - next to one accumulator set spilled) and the accumulators of all five column tiles (80; phase A's are
+//      not live yet), and re-reads its rows from the L2 per k-group.  k and v leave through split2b_mix straight into the K / V planes of tri_attn8 in LDS
+//      (16-byte stores: the head's columns are packed so that a lane holds 8 consecutive channels); q stays in registers: the pack gives
+//      lane half hh the channels 16 hh .. 16 hh + 15 and BOTH halves the channels 32 .. 47, so the fragments (query lq, group g) of the
+//      wave's two query tiles are one v_permlane16_swap per value away.
+//      The head's weight planes (AbxTriRowPack: per head 15 stages of 8 KB = (4 k-tiles, column tile) in LDS fragment order) arrive by
+//      global_load_lds, issued by the twelfth wave (at L <= 352 it has no rows): the first three stages into a 24 KB ring while the
+//      computing waves are still in phase A of the previous slot, the other twelve into the plane region, which is empty until the tile
+//      epilogues write K / V.  Five block barriers per slot (see the issuing wave); a barrier per stage cost 0.8 ms per launch more.
+//      The issuing wave also touches the z row of the next slot, so that its projection starts from the L2.
+//   A  tri8_row_compute on the resident row (one "chunk"), no barrier inside.
+// Every product, sum and rounding is the one the two launches perform: the output is bit-identical to gemm_as + tri_attn8.
+// Slot order (TriRowArgs.order): 0 = (b, row, h) with the four heads of a row on neighbouring workgroups of one XCD (the 270 KB of
+// z[b, s] come from HBM once and from that L2 three times; the XCD keeps four bias maps hot), 1 = (b, h, row) as tri_attn8.
+constexpr int RF_LK = 352;                                   // keys the planes hold: the largest eligible row
+constexpr int RF_PLN = RF_LK * RST;                          // 33 792
+constexpr int RF_OFF_MSB = 4 * RF_PLN;                       // key clamps [384]
+constexpr int RF_OFF_RING = RF_OFF_MSB + 384 * 4;            // 136 704
+constexpr int RF_STAGE = 8192;                               // [4 k-tiles][2 planes][32 columns][16] f16
+constexpr int RF_NRING = 3;                                 // stages the ring holds
+constexpr int RF_G0 = RF_NRING;                             // stages of a slot requested ahead into the ring; the others go through the plane region
+constexpr int RF_OFF_CONST = RF_OFF_RING + RF_NRING * RF_STAGE;      // [csum 160 | bias 160] of the slot's head, packed column order
+constexpr int RF_LDS = RF_OFF_CONST + 2 * 160 * 4;           // 162 560 <= 163 840
+constexpr int RF_TILES = 5, RF_SPS = 3 * RF_TILES;           // column tiles (160 packed columns), stages per slot
+constexpr int RF_HEAD_BYTES = RF_SPS * RF_STAGE;             // 122 880 per head
+constexpr int RF_DEFAULT_ORDER = 0;                          // slot order of slot_order = -1 (AbxTriRowPack / abx_tri_attn_rowfused_fwd)
+constexpr int RF_NK = 12;                                    // k-tiles: 192 input channels
+
+struct TriRowArgs {
+    const float* z; long long zb, zs, zl;                    // element (b, s, l, c) at z + b zb + s zs + l zl + c
+    const char* wp; const float* csum; const float* bias;    // AbxTriRowPack
+    float cs, inv_cs, eps;                                   // 2^-(a_exp + b_exp), its inverse, LayerNorm eps
+    int order;
+};
+
+__global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const AbxTriAttn a, const TriRowArgs p) {
+    constexpr int PLN = RF_PLN;
+    constexpr int NCW = TRI_THREADS / 64 - 1;               // computing waves; the last wave issues the weight DMA
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    char* lds = reinterpret_cast<char*>(smem);
+    float* Msb = reinterpret_cast<float*>(lds + RF_OFF_MSB);
+    char* ring = lds + RF_OFF_RING;
+    float* cst = reinterpret_cast<float*>(lds + RF_OFF_CONST);
+    const int L = a.L;
+    const ClockProbe probe(a.clock_probe);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // ---- the slots of this workgroup: XCD x = blockIdx & 7 owns the rows (order 0) / the (b, h) pairs (order 1) x, x + 8, ...
+    const int xcd = blockIdx.x & 7, wg = blockIdx.x >> 3, NW = gridDim.x >> 3;
+    // (32-bit: the dispatch keeps B S H below 2^31; 64-bit divisions are ~80 vector instructions each)
+    const unsigned nunit = p.order == 0 ? (unsigned)a.B * (unsigned)a.S : (unsigned)a.B * (unsigned)a.H;
+    const unsigned per_unit = p.order == 0 ? (unsigned)a.H : (unsigned)a.S;
+    const unsigned nslots = (nunit + 7 - xcd) / 8 * per_unit;                   // slots of this XCD (every one is valid)
+    const int nmine = (unsigned)wg < nslots ? (int)((nslots - wg + NW - 1) / NW) : 0;       // slots wg, wg + NW, ... of them
+    auto decode = [&](int i, Tri8Row& r) __attribute__((always_inline)) {
+        const unsigned slot = (unsigned)wg + (unsigned)i * (unsigned)NW;
+        const unsigned unit = slot / per_unit * 8 + xcd;
+        const int sub = (int)(slot % per_unit);
+        if (p.order == 0) { r.b = (int)(unit / (unsigned)a.S); r.s = (int)(unit % (unsigned)a.S); r.h = sub; }
+        else { r.b = (int)(unit / (unsigned)a.H); r.h = (int)(unit % (unsigned)a.H); r.s = sub; }
+        r.b = __builtin_amdgcn_readfirstlane(r.b);
+        r.h = __builtin_amdgcn_readfirstlane(r.h);
+        r.s = __builtin_amdgcn_readfirstlane(r.s);
+        r.part = 0;
+        r.base = 0;                                              // (no q | k | v rows in memory, no gate)
+        r.km = a.keymask ? a.keymask + (long long)r.b * a.km_sb : nullptr;
+        r.biasb = a.bias + (long long)r.b * a.bias_sb + (long long)r.h * a.bias_sh;
+    };
+
+    if (wave == NCW) {
+        // ================= issuing wave ===================================================================================================
+        // The 15 stages of a slot's head in three groups: G0 = stages 0 - 2 -> the ring (requested while the computing waves are in phase A
+        // of the previous slot), G1 = 3 - 8 and G2 = 9 - 14 -> the plane region, which is empty between barrier (a) of a slot - every wave
+        // has left phase A of the previous one - and its tile epilogues.  Barriers of a slot: (a) G0 landed, (b) G1, the key clamps and
+        // the column constants landed (G2 in flight), (c) G2 landed, (d) every wave has read its last weight fragment (the epilogues may write K / V over
+        // them), (e) K / V complete.  Inside a group the waves run free.
+        __builtin_amdgcn_s_setprio(3);
+        Tri8Row r;
+        auto dma = [&](int hd, int s0, auto ns_, char* dst) __attribute__((always_inline)) {
+            constexpr int NI = decltype(ns_)::value * (RF_STAGE / 1024);
+            const char* src = p.wp + (long long)hd * RF_HEAD_BYTES + s0 * RF_STAGE + lane * 16;
+#pragma unroll 8
+            for (int i = 0; i < NI; ++i)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024),
+                                                 (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
+        };
+        if (nmine > 0) {
+            decode(0, r);
+            dma(r.h, 0, std::integral_constant<int, RF_G0>{}, ring);
+        }
+        for (int it = 0; it < nmine; ++it) {
+            decode(it, r);
+            // key clamps of the slot, applied as logit = min(logit, clamp): +inf valid, finfo.min masked, -inf beyond L (tri_attn8_kernel), and
+            // the column constants of its head (read by the tile epilogues).  Their loads are issued HERE, in front of barrier (a) - this wave
+            // idles there through phase A of the previous slot - and are UNCONDITIONAL (no key mask: the same number of loads from the
+            // column sums, results dropped): behind barrier (a) this wave's vector-memory queue holds the 96 DMA instructions and nothing
+            // else, so the counted waits below are exact whatever the descriptor holds.
+            float kmv[6], csv[3], biv[3];
+            {
+                const float* kmp = r.km ? r.km : p.csum;
+                const int kmax = r.km ? L - 1 : RF_TILES * 32 - 1;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) kmv[j] = kmp[min(lane + 64 * j, kmax)];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const int t = min(lane + 64 * j, RF_TILES * 32 - 1);
+                    csv[j] = p.csum[r.h * (RF_TILES * 32) + t];
+                    biv[j] = p.bias[r.h * (RF_TILES * 32) + t];
+                }
+            }
+            // (a): G0 (requested a phase ago), the touches and the loads above have landed; the values pass through the statement, so the
+            // compiler has no wait of its own to place between the DMA instructions below
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier"
+                         : "+v"(kmv[0]), "+v"(kmv[1]), "+v"(kmv[2]), "+v"(kmv[3]), "+v"(kmv[4]), "+v"(kmv[5]), "+v"(csv[0]), "+v"(csv[1]), "+v"(csv[2]),
+                           "+v"(biv[0]), "+v"(biv[1]), "+v"(biv[2])
+                         :
+                         : "memory");
+            dma(r.h, RF_G0, std::integral_constant<int, RF_SPS - RF_G0>{}, lds);
+            const bool has_km = r.km != nullptr;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const int t = lane + 64 * j;
+                Msb[t] = (t < L) ? ((!has_km || kmv[j] != 0.f) ? INFINITY : ABX_NEG_MAX) : -INFINITY;
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int t = lane + 64 * j;
+                if (t < RF_TILES * 32) {
+                    cst[t] = csv[j];
+                    cst[RF_TILES * 32 + t] = biv[j];
+                }
+            }
+            // (b): G1 = the first 48 of the 96 DMA instructions has landed (results return in issue order; the 48 of G2 stay in flight)
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((RF_SPS - RF_G0) / 2 * (RF_STAGE / 1024)) : "memory");
+            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");                     // (c): G2 has landed
+            asm volatile("s_barrier" ::: "memory");                                            // (d)
+            asm volatile("s_barrier" ::: "memory");                                            // (e)
+            // while the computing waves are in phase A: G0 of the NEXT slot, and a touch of its z row (one load per 128-byte line), so that its
+            // projection starts from the L2 instead of waiting out an HBM round trip in front of every wave's first k-tile
+            if (it + 1 < nmine) {
+                decode(it + 1, r);
+                dma(r.h, 0, std::integral_constant<int, RF_G0>{}, ring);
+                const float* zr = p.z + (long long)r.b * p.zb + (long long)r.s * p.zs;
+                unsigned x = 0;
+                for (int l = lane; l < L; l += 64) {
+                    const float* zq = zr + (long long)l * p.zl;
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) x ^= __builtin_bit_cast(unsigned, zq[j * 32]);
+                }
+                asm volatile("" ::"v"(x));
+            }
+        }
+        probe.finish();
+        return;
+    }
+
+    // ================= computing waves ======================================================================================
+    const float qscale = a.scale * LOG2E * 8.0f;                          // (the scales of tri_attn8_kernel)
+    const int nqt = (L + 15) / 16;
+    const int qtA = 2 * wave;
+    const bool has_tile = qtA < nqt;                                      // == the wave has rows to project (32 w < L)
+    const float invK = 1.0f / (float)(RF_NK * 16);
+    bool any_masked = false;
+    int b_masked = -1;
+    Tri8Row cur;
+    for (int it = 0; it < nmine; ++it) {
+        decode(it, cur);
+        if (cur.b != b_masked) {                                // wave-uniform: does this sample mask any key?
+            any_masked = false;
+            if (cur.km) {
+                for (int j = lane; j < L; j += 64) any_masked |= cur.km[j] == 0.f;
+                any_masked = __any(any_masked);
+            }
+            b_masked = cur.b;
+        }
+        f16x8 qf[2][4];
+        bool badp = false;
+        // (the per-lane constants of a phase are recomputed per slot behind an opaque lane id: as invariants of the whole kernel they are held
+        // across BOTH phases and spill - the producer of tri_attn8_kernel does the same)
+        int ln = threadIdx.x & 63;
+        asm volatile("" : "+v"(ln));
+        const int hh = ln >> 5, pr = ln & 31;                               // projection lane = (position of the wave's 32, k half / channel half)
+        const int foff = pr * 32 + ((hh ^ ((pr >> 3) & 1)) << 4);           // weight fragment inside a (k-tile, plane) image of the ring
+        float m2048 = -2048.0f, c16 = 16.0f;
+        asm volatile("" : "+v"(m2048), "+v"(c16));
+        // ---- phase P.  Stage (kg, t) = k-tiles 4 kg .. 4 kg + 3 of column tile t: the wave holds the pieces of four k-tiles (32 registers) and
+        // the accumulators of all five column tiles (80); every output element still sums its k-tiles in ascending order.
+        // Pieces and statistics: as_conv_ktile / as_conv_finish of gemm_as.hip, k-tiles in order.
+        f32x16 acc[RF_TILES];
+#pragma unroll
+        for (int t = 0; t < RF_TILES; ++t)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+        const int pos = min(32 * wave + pr, L - 1);              // positions beyond the row: the last one again (keys clamped to -inf, queries never stored)
+        const float* zp = p.z + (long long)cur.b * p.zb + (long long)cur.s * p.zs + (long long)pos * p.zl + 8 * hh;
+        float lshift = 0.f;
+        f32x2 ls2 = {0.f, 0.f}, lq2 = {0.f, 0.f};
+        tri_static_for<0, 3>([&](auto kg_) __attribute__((always_inline)) {
+            constexpr int kg = decltype(kg_)::value;
+            u32x4 a0[4], a1[4];
+            if (has_tile) {
+                f32x4 lo[4], hi[4];
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) {
+                    lo[kk] = *reinterpret_cast<const f32x4*>(zp + (4 * kg + kk) * 16);
+                    hi[kk] = *reinterpret_cast<const f32x4*>(zp + (4 * kg + kk) * 16 + 4);
+                }
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) {
+                    float xv[8];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { xv[e] = lo[kk][e]; xv[4 + e] = hi[kk][e]; }
+                    if (kg == 0 && kk == 0) lshift = __shfl(xv[0], pr, 64);      // the row's first element
+                    const f32x2 sh2 = {lshift, lshift};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        f32x2 xp = {xv[2 * e], xv[2 * e + 1]};
+                        xp -= sh2;
+                        ls2 += xp;
+                        lq2 = __builtin_elementwise_fma(xp, xp, lq2);
+                        xv[2 * e] = xp[0];
+                        xv[2 * e + 1] = xp[1];
+                    }
+                    unsigned q0[4], q1[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) split2h_mix(xv[2 * e], xv[2 * e + 1], m2048, q0[e], q1[e]);
+                    a0[kk] = u32x4{q0[0], q0[1], q0[2], q0[3]};
+                    a1[kk] = u32x4{q1[0], q1[1], q1[2], q1[3]};
+                }
+            }
+            tri_static_for<0, RF_TILES>([&](auto t_) __attribute__((always_inline)) {
+                constexpr int t = decltype(t_)::value;
+                constexpr int n = kg * RF_TILES + t;                                  // stage of the slot
+                // (the issuing wave's barriers (a), (b), (c): the stage's group has landed)
+                if constexpr (n == 0 || n == RF_G0 || n == RF_G0 + (RF_SPS - RF_G0) / 2) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if (has_tile) {
+                    const char* ws = (n < RF_G0 ? ring + n * RF_STAGE : lds + (n - RF_G0) * RF_STAGE) + foff;
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk) {
+                        const u32x4 w0 = *reinterpret_cast<const u32x4*>(ws + kk * 2048);
+                        const u32x4 w1 = *reinterpret_cast<const u32x4*>(ws + kk * 2048 + 1024);
+                        const u32x4 w2 = f16x8_lo(w0);
+                        // a1 p2, a0 p1, a0 p0 (smallest first), from a zero accumulator
+                        acc[t] = mfma_split(w2, a1[kk], acc[t]);
+                        acc[t] = mfma_split(w1, a0[kk], acc[t]);
+                        acc[t] = mfma_split(w0, a0[kk], acc[t]);
+                    }
+                }
+            });
+        });
+        float dm = 0.f, rs = 0.f;
+        {
+            const float ls = ls2[0] + ls2[1], lqs = lq2[0] + lq2[1];
+            const float sm = ls + __shfl_xor(ls, 32, 64), sq = lqs + __shfl_xor(lqs, 32, 64);
+            dm = sm * invK;
+            rs = (1.0f / sqrtf(fmaxf(sq * invK - dm * dm, 0.f) + p.eps)) * p.cs;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (d) every wave has read its last weight fragment out of the plane region
+        // ---- the five column tiles: k 0..31 | k 32..47, v 0..15 | v 16..47 | q (16 hh ..) | q 32..47 (both halves)
+        const float* cst_l = cst + 4 * hh;
+        char* kdst = lds + (32 * wave + pr) * RST + hh * 16;            // (plane p1: + PLN; V planes: + 2 PLN)
+        tri_static_for<0, RF_TILES>([&](auto t_) __attribute__((always_inline)) {
+            constexpr int t = decltype(t_)::value;
+            if (has_tile) {
+                // folded-LayerNorm epilogue (gemm_as plain_slice): register 4 i + c = packed column 8 i + 4 hh + c of the tile
+                float x[16];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x4 cs4 = *reinterpret_cast<const f32x4*>(cst_l + t * 32 + 8 * i);
+                    const f32x4 bi4 = *reinterpret_cast<const f32x4*>(cst_l + RF_TILES * 32 + t * 32 + 8 * i);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const float csump = cs4[c] * p.inv_cs;
+                        const float v = rs * (acc[t][4 * i + c] - dm * csump);
+                        x[4 * i + c] = v + bi4[c];
+                    }
+                    badp |= __builtin_amdgcn_classf((x[4 * i] + x[4 * i + 1]) + (x[4 * i + 2] + x[4 * i + 3]), 0x207);
+                }
+                if constexpr (t < 3) {
+                    // registers 0..7 / 8..15: 8 consecutive channels each -> planes p0, p1 of 16 x value (the producer's split2b_mix)
+#pragma unroll
+                    for (int half = 0; half < 2; ++half) {
+                        // tile 0: K 8 hh, K 16 + 8 hh; tile 1: K 32 + 8 hh, V 8 hh; tile 2: V 16 + 8 hh, V 32 + 8 hh
+                        constexpr int TAB[3][2] = {{0, 32}, {64, 2 * PLN}, {2 * PLN + 32, 2 * PLN + 64}};
+                        unsigned w0[4], w1[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) split2b_mix(x[8 * half + 2 * e], x[8 * half + 2 * e + 1], c16, w0[e], w1[e]);
+                        char* d = kdst + TAB[t][half];
+                        *reinterpret_cast<u32x4*>(d) = u32x4{w0[0], w0[1], w0[2], w0[3]};
+                        *reinterpret_cast<u32x4*>(d + PLN) = u32x4{w1[0], w1[1], w1[2], w1[3]};
+                    }
+                } else {
+                    // q: lanes l and l ^ 16 hold the positions lq and 16 + lq of the same channels; query tile X = 0 takes registers 0..7 of the
+                    // even 16-lane row, X = 1 registers 8..15 of the odd one (v_permlane16_swap: odd rows of the first <-> even rows of the second)
+                    float qv[2][8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(x[e]), __float_as_uint(x[8 + e]), false, false);
+                        qv[0][e] = __uint_as_float(sw[0]);
+                        qv[1][e] = __uint_as_float(sw[1]);
+                    }
+#pragma unroll
+                    for (int X = 0; X < 2; ++X) {
+                        unsigned p0[4], p1[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) split2h_ns(qv[X][2 * e] * qscale, qv[X][2 * e + 1] * qscale, p0[e], p1[e]);
+                        if constexpr (t == 3) {
+                            qf[X][0] = __builtin_bit_cast(f16x8, u32x4{p0[0], p0[1], p0[2], p0[3]});
+                            qf[X][1] = __builtin_bit_cast(f16x8, u32x4{p1[0], p1[1], p1[2], p1[3]});
+                        } else {
+                            qf[X][2] = __builtin_bit_cast(f16x8, u32x4{p0[0], p0[1], p0[2], p0[3]});
+                            qf[X][3] = hh == 0 ? __builtin_bit_cast(f16x8, u32x4{p1[0], p1[1], p1[2], p1[3]}) : __builtin_bit_cast(f16x8, u32x4{0u, 0u, 0u, 0u});
+                        }
+                    }
+                }
+            }
+        });
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (e) the K / V planes and the clamps of the row are complete
+        // ---- phase A
+        int cc = 0;
+        int la = threadIdx.x & 63;
+        asm volatile("" : "+v"(la));
+        const int lqa = la & 15, ga = la >> 4;
+        const int koff0 = lqa * RST + ga * 16;
+        const int koffc = lqa * RST + (ga >> 1) * PLN + 64 + (ga & 1) * 16;
+        const int voff = (4 * ga + (lqa >> 2)) * RST + (lqa & 3) * 8;
+        unsigned boff[2];
+#pragma unroll
+        for (int X = 0; X < 2; ++X) {
+            const int qrow = min((qtA + X) * 16 + lqa, L - 1);     // beyond the row: the last query row again (never stored)
+            boff[X] = (unsigned)(((long long)qrow * a.bias_sq + ga * 4) * 4);
+        }
+        if (a.range_flag && __any(badp) && la == 0) atomicOr(a.range_flag, a.range_tag);
+        tri8_row_compute<RF_LK, true, false>(a, cur, lds, Msb, cc, 1, qf, boff, any_masked, has_tile, qtA, nqt, la, koff0, koffc, voff,
+                                             []() __attribute__((always_inline)) {});
+    }
+    probe.finish();
+}
+
+// head-major image of the q | k | v planes for tri_attn8_rowfused_kernel: per head 3 groups of 4 k-tiles x 5 column tiles, each (group, tile) the
+// 8 KB ring stage [k-tile][plane][column 32][16] in the bank-swizzled fragment order; packed column m of a tile -> source column:
+//   tiles 0 - 2 (k 0..31 | k 32..47, v 0..15 | v 16..47): channel 16 (i >> 1) + 8 hh + 4 (i & 1) + c of the tile's 32 (m = 8 i + 4 hh + c)
+//   tile 3: q channel 16 hh + 4 i + c; tile 4: q channel 32 + 4 i + c for both hh
+__device__ __forceinline__ int rf_source_col(int h, int t, int m) {
+    const int i = m >> 3, hh = (m >> 2) & 1, c = m & 3;
+    const int kv = 16 * (i >> 1) + 8 * hh + 4 * (i & 1) + c;
+    if (t == 0) return 192 + 48 * h + kv;
+    if (t == 1) return kv < 16 ? 192 + 48 * h + 32 + kv : 384 + 48 * h + (kv - 16);
+    if (t == 2) return 384 + 48 * h + 16 + kv;
+    if (t == 3) return 48 * h + 16 * hh + 4 * i + c;
+    return 48 * h + 32 + 4 * i + c;
+}
+__global__ void tri_rowpack_kernel(const unsigned short* __restrict__ planes, const float* __restrict__ csum, const float* __restrict__ bias,
+                                   int N, int H, unsigned short* __restrict__ out, float* __restrict__ csum_h, float* __restrict__ bias_h) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;      // one thread per (head, tile, packed column, k-tile, plane, k half)
+    const int total = H * RF_TILES * 32 * RF_NK * 2 * 2;
+    if (idx >= total) return;
+    int r = idx;
+    const int half = r & 1; r >>= 1;
+    const int plane = r & 1; r >>= 1;
+    const int kt = r % RF_NK; r /= RF_NK;
+    const int m = r & 31; r >>= 5;
+    const int t = r % RF_TILES, h = r / RF_TILES;
+    const int n = rf_source_col(h, t, m);
+    const unsigned short* src = planes + (((long long)kt * 2 + plane) * N + n) * 16 + half * 8;
+    unsigned short* dst = out + ((long long)h * RF_HEAD_BYTES + ((kt / 4) * RF_TILES + t) * RF_STAGE + (kt % 4) * 2048 + plane * 1024 + m * 32 +
+                                 ((half ^ ((m >> 3) & 1)) << 4)) / 2;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dst[e] = src[e];
+    if (kt == 0 && plane == 0 && half == 0) {
+        csum_h[(h * RF_TILES + t) * 32 + m] = csum[n];
+        bias_h[(h * RF_TILES + t) * 32 + m] = bias[n];
+    }
 }
 
 // ---- sequence attention with pair bias (seqformer.py:314-356): 32 heads x 17 channels, bias (b, h, q, k) ---------------------------
@@ -1458,4 +1873,84 @@ extern "C" int abx_seq_attn_fwd(const float* qkv, const float* bias, const float
         case 8: return launch(&seq_attn2_kernel<8, 512>, 3);
         default: return launch(&seq_attn2_kernel<12, 256>, 4);
     }
+}
+
+// ---- row-fused triangle attention: pack, switch, entry ------------------------------------------------------------------------------
+namespace {
+inline long long rf_up(long long x) { return (x + 255) / 256 * 256; }
+}  // namespace
+
+extern "C" long long abx_tri_rowpack_bytes(void) { return rf_up(4LL * RF_HEAD_BYTES) + 2 * rf_up(4LL * RF_TILES * 32 * 4); }
+
+extern "C" int abx_tri_rowpack(const AbxLinearPack* qkv, void* buf, AbxTriRowPack* out, hipStream_t st) {
+    ABX_REQUIRE(qkv && buf && out, "abx_tri_rowpack: bad args");
+    ABX_REQUIRE(qkv->K == RF_NK * 16 && qkv->N == 3 * 4 * TD && qkv->planes && qkv->csum && qkv->bias,
+                "abx_tri_rowpack: qkv = LayerNorm-folded 192 -> 576 pack with planes");
+    ABX_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "abx_tri_rowpack: buf must be 256-byte aligned");
+    char* p = static_cast<char*>(buf);
+    unsigned short* planes = reinterpret_cast<unsigned short*>(p); p += rf_up(4LL * RF_HEAD_BYTES);
+    float* csum = reinterpret_cast<float*>(p); p += rf_up(4LL * RF_TILES * 32 * 4);
+    float* bias = reinterpret_cast<float*>(p);
+    const int total = 4 * RF_TILES * 32 * RF_NK * 2 * 2;
+    hipLaunchKernelGGL(tri_rowpack_kernel, dim3((total + 255) / 256), dim3(256), 0, st, qkv->planes, qkv->csum, qkv->bias, qkv->N, 4, planes, csum, bias);
+    if (int rc = abx_check_launch("abx_tri_rowpack")) return rc;
+    out->planes = planes;
+    out->csum = csum;
+    out->bias = bias;
+    out->b_exp = qkv->b_exp;
+    out->H = 4;
+    return ABX_OK;
+}
+
+extern "C" int abx_tri_attn_rowfused_ok(int L) {
+    // ("set and not 0", the reading of ABX_NO_OPM_FUSED; the Python side asks this function instead of reading the variable itself)
+    static const bool off = [] { const char* e = getenv("ABX_NO_TRI_ROWFUSED"); return e && *e && !(e[0] == '0' && e[1] == 0); }();
+    return (!off && L > 0 && L <= ABX_TRI_ROWFUSED_LMAX) ? 1 : 0;
+}
+
+extern "C" int abx_tri_attn_rowfused_fwd(const AbxTriAttn* ap, const float* z, long long zb, long long zs, long long zl, const AbxTriRowPack* pk,
+                                         int slot_order, hipStream_t st) {
+    ABX_REQUIRE(ap != nullptr && z && pk, "abx_tri_attn_rowfused_fwd: null argument");
+    AbxTriAttn a = *ap;
+    ABX_REQUIRE(a.out && a.bias && pk->planes && pk->csum && pk->bias, "abx_tri_attn_rowfused_fwd: null operand");
+    ABX_REQUIRE(a.D == TD && a.H == 4 && pk->H == 4, "abx_tri_attn_rowfused_fwd: 4 heads of 48 channels");
+    ABX_REQUIRE(a.B > 0 && a.S > 0 && a.L > 0, "abx_tri_attn_rowfused_fwd: empty problem");
+    ABX_REQUIRE(a.L <= ABX_TRI_ROWFUSED_LMAX, "abx_tri_attn_rowfused_fwd: L beyond ABX_TRI_ROWFUSED_LMAX (the two launches serve longer rows)");
+    ABX_REQUIRE(!a.exact && !a.kv_planes && !a.gate, "abx_tri_attn_rowfused_fwd: split-f16 arithmetic, no gate, no operand images");
+    ABX_REQUIRE(slot_order >= -1 && slot_order <= 1, "abx_tri_attn_rowfused_fwd: slot_order is -1, 0 or 1");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    ABX_REQUIRE((zb % 4 == 0) && (zs % 4 == 0) && (zl % 4 == 0) && (a.ob % 4 == 0) && (a.os % 4 == 0) && (a.ol % 4 == 0) && al16(z) && al16(a.out) &&
+                    al16(pk->planes) && al16(pk->csum) && al16(pk->bias),
+                "abx_tri_attn_rowfused_fwd: strides must be multiples of 4 floats, pointers 16-byte aligned");
+    ABX_REQUIRE(a.bias_sk == 1 && a.bias_sq % 4 == 0 && a.bias_sq >= a.L && a.bias_sb % 4 == 0 && a.bias_sh % 4 == 0 && al16(a.bias) &&
+                    (long long)a.L * a.bias_sq * 4 < (1LL << 31),
+                "abx_tri_attn_rowfused_fwd: the bias must be key-contiguous rows padded to a multiple of 4 floats, 16-byte aligned");
+    ABX_REQUIRE(pk->b_exp >= -100 && pk->b_exp <= 100, "abx_tri_attn_rowfused_fwd: plane exponent out of range");
+    ABX_REQUIRE((long long)a.B * a.S * a.H < (1LL << 31), "abx_tri_attn_rowfused_fwd: grid too large");
+    a.q = a.k = a.v = nullptr;
+    a.q_parts = 1;
+    a.row_groups = 1;
+    TriRowArgs p;
+    p.z = z; p.zb = zb; p.zs = zs; p.zl = zl;
+    p.wp = reinterpret_cast<const char*>(pk->planes); p.csum = pk->csum; p.bias = pk->bias;
+    p.cs = ldexpf(1.0f, -ABX_F16_A_EXP - pk->b_exp);
+    p.inv_cs = ldexpf(1.0f, ABX_F16_A_EXP + pk->b_exp);
+    p.eps = 1e-5f;
+    p.order = slot_order < 0 ? RF_DEFAULT_ORDER : slot_order;
+    static int n_cu = 0;
+    if (n_cu == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
+            abx_set_error("abx_tri_attn_rowfused_fwd: hipGetDeviceProperties failed");
+            return ABX_ERR_ARG;
+        }
+        n_cu = prop.multiProcessorCount > 8 ? prop.multiProcessorCount / 8 * 8 : 8;
+    }
+    const long long nunit = p.order == 0 ? (long long)a.B * a.S : (long long)a.B * a.H;
+    const long long slots_xcd = (nunit + 7) / 8 * (p.order == 0 ? a.H : a.S);
+    const unsigned wg_xcd = (unsigned)std::min<long long>(n_cu / 8, slots_xcd);
+    if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&tri_attn8_rowfused_kernel), RF_LDS, "abx_tri_attn_rowfused_fwd")) return rc;
+    hipLaunchKernelGGL(tri_attn8_rowfused_kernel, dim3(8 * wg_xcd), dim3(TRI_THREADS), RF_LDS, st, a, p);
+    return abx_check_launch("abx_tri_attn_rowfused_fwd");
 }

@@ -328,7 +328,21 @@ extern "C" int abx_tri_attn_block_fwd(const AbxTriAttnPack* wp, float* z, const 
     // never on the critical path), the projection pays for the split and the 8-byte stores (13.7 -> 15.6 ms): profiles/r06h_kb_kvplanes.txt.
     static const bool kv_planes_on = getenv("ABX_KV_PLANES") != nullptr;
     const int planes = (kv_planes_on && !exact && !attn_exact && abx_gemm_planes_ok(M2)) ? 1 : 0;
-    {   // q | k | v, and the pair bias stored (b, h, i, j) in the same grid (abx_gemm_side: one launch on the split-f16 path - the side
+    // Row-fused route (attention.hip tri_attn8_rowfused_kernel): q | k | v of a pair row are projected inside the attention workgroup of that row
+    // and never written - the launches are the pair-bias projection alone, the transpose, the fused kernel, the tail.  Chosen by L alone
+    // (abx_tri_attn_rowfused_ok: never by B - a sample's bits do not depend on the batch), on the split-f16 route with a row pack.
+    const bool rowfused = !exact && !attn_exact && !planes && wp->row.planes && abx_tri_attn_rowfused_ok(L);
+    if (rowfused) {
+        AbxGemm s2 = {};
+        s2.A = z; s2.sAb = LL * C; s2.sAm = C; s2.sAk = 1;
+        s2.C = w.bT; s2.sCb = 4 * LL; s2.sCm = LL; s2.c_transposed = 1;
+        s2.M = (int)LL; s2.batch = B;
+        set_weights(s2, pair, true, 0);
+        set_range(s2, range_flag, range_tag, 0);
+        s2.alpha = ABX_TRI_BIAS_LOG2;
+        if (int rc = abx_gemm(&s2, st)) return rc;
+    } else {
+        // q | k | v, and the pair bias stored (b, h, i, j) in the same grid (abx_gemm_side: one launch on the split-f16 path - the side
         // rides in the free half of the projection's last column tile -, the two launches otherwise)
         AbxGemm g = {};
         g.A = z; g.sAm = C; g.sAk = 1;
@@ -370,7 +384,9 @@ extern "C" int abx_tri_attn_block_fwd(const AbxTriAttnPack* wp, float* z, const 
         a.bias_log2 = attn_exact ? 0 : 1;
         a.kv_planes = planes;
         if (!attn_exact) { a.range_flag = range_flag; a.range_tag = range_tag; }
-        if (int rc = abx_tri_attn_fwd(&a, st)) return rc;
+        if (rowfused) {
+            if (int rc = abx_tri_attn_rowfused_fwd(&a, z, LL * C, per_row ? (long long)L * C : C, per_row ? C : (long long)L * C, &wp->row, -1, st)) return rc;
+        } else if (int rc = abx_tri_attn_fwd(&a, st)) return rc;
     }
     if (!exact) {
         // gated tail: z += (sigmoid(LN(z) Wg + bg) * o) Wo + bo in ONE kernel (AbxGemm.mlp = 2)

@@ -7,7 +7,7 @@ import torch
 
 from abx_amd import _lib
 from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxLinearPack, AbxLinearSrc,
-                           AbxTriMulPack, AbxTriAttnPack, check)
+                           AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
 def _stream():
@@ -549,10 +549,28 @@ def tri_mul_fwd(pack, z_in, z_out, mask_f, B, L, outgoing, workspace):
     return z_out
 
 
+class TriRowPack:
+    """Head-major image of a q | k | v LinearPack (abx_tri_rowpack) for the row-fused triangle attention: .c is the AbxTriRowPack, the device
+    buffer it points into is kept alive here together with the source pack."""
+
+    def __init__(self, qkv):
+        lib = _lib.load()
+        nbytes = int(lib.abx_tri_rowpack_bytes())
+        self.buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=qkv.buf.device)
+        off = (-self.buf.data_ptr()) % 256
+        self.c = AbxTriRowPack()
+        check(lib.abx_tri_rowpack(C.byref(qkv.c), self.buf[off:].data_ptr(), C.byref(self.c), _stream()), 'abx_tri_rowpack')
+        self.qkv = qkv
+
+
 def tri_attn_pack(qkv, gate, pair, out):
     p = AbxTriAttnPack()
     p.qkv, p.gate, p.pair, p.out = qkv.c, gate.c, pair.c, out.c
     p._keep = (qkv, gate, pair, out)
+    p._row = None
+    if qkv.buf.is_cuda and qkv.K == 192 and qkv.N == 576 and qkv.c.csum:
+        p._row = TriRowPack(qkv)                    # (the row-fused route of abx_tri_attn_block_fwd / tri_attn(z rows, rowpack=))
+        p.row = p._row.c
     return p
 
 
@@ -572,10 +590,32 @@ def tri_attn_block_fwd(pack, z, mask_f, B, L, per_row, workspace, exact=False, a
     return z
 
 
-def tri_attn_kernel_name(L, exact=None, bias_vec=True):
-    """Name of the kernel abx_tri_attn_fwd launches (mirror of the selection in csrc/attention.hip), for per-kernel aggregation."""
-    if GEMM_EXACT if exact is None else exact:
+def _tri_rowfused_ok(L):
+    """True when the library takes the row-fused triangle attention for rows of length L (abx_tri_attn_rowfused_ok: L <= 352 and the
+    ABX_NO_TRI_ROWFUSED switch, which only the C side reads - abx_tri_attn_block_fwd and the descriptor-level path ask the same function)."""
+    return bool(_lib.load().abx_tri_attn_rowfused_ok(int(L)))
+
+
+_TRI_ATTN_LAST = None       # (L, exact, row-fused) of the most recent tri_attn launch: what a caller that times launches asks the name of
+
+
+def tri_attn_kernel_name(L, exact=None, bias_vec=True, rowfused=None):
+    """Name of the kernel the triangle attention of a row of length L runs on (mirror of the selection in csrc/attention.hip), for
+    per-kernel aggregation.  rowfused: True = tri_attn on the z rows with a row pack (abx_tri_attn_rowfused_fwd), False = tri_attn on projected
+    q | k | v rows (abx_tri_attn_fwd); None = whatever the most recent tri_attn call of this (L, exact) launched - the caller that times a
+    launch asks right behind it - and, with no such call, what the model path does for a complex of this length: the fused kernel when the
+    library admits L (abx_tri_attn_rowfused_ok: a function of L and of the ABX_NO_TRI_ROWFUSED switch, read on the C side only), the GEMMs
+    of the pass are the split-f16 ones (gemm_mode) and the k | v operand images are off."""
+    ex = bool(GEMM_EXACT if exact is None else exact)
+    if ex:
         return 'tri_attn_kernel'
+    if rowfused is None:
+        if _TRI_ATTN_LAST is not None and _TRI_ATTN_LAST[:2] == (int(L), ex):
+            rowfused = _TRI_ATTN_LAST[2]
+        else:
+            rowfused = _tri_rowfused_ok(L) and gemm_mode(L) == 2 and not KV_PLANES
+    if rowfused:
+        return 'tri_attn8_rowfused_kernel'
     kc = 128 if (L + 127) // 128 == (L + 191) // 192 else 192
     return 'tri_attn8_kernel<%d, 768, %s>' % (kc, 'true' if bias_vec else 'false')
 
@@ -594,18 +634,25 @@ def kv_planes_ok(M):
     return bool(_lib.load().abx_gemm_planes_ok(int(M))) and not GEMM_EXACT and not (GEMM_TUNE & 2048)
 
 
-def tri_attn(qkvg, biasT, keymask, out, B, L, per_row, H=4, D=48, bias_is_qk=False, exact=None, clock_probe=None, tune=0, bias_log2=False, kv_planes=False):
+def tri_attn(qkvg, biasT, keymask, out, B, L, per_row, H=4, D=48, bias_is_qk=False, exact=None, clock_probe=None, tune=0, bias_log2=False, kv_planes=False,
+             rowpack=None, slot_order=-1):
     """qkvg (B*L*L, 4*H*D) = [q|k|v|gate], or (B*L*L, 3*H*D) = [q|k|v]: no gate (the gated tail applies it: gemm(..., mlp=, gate=));
+    or the pair rows z (B*L*L, H*D = 192) themselves with rowpack = the TriRowPack of the LayerNorm-folded q | k | v projection: the
+    row-fused kernel projects q | k | v of a row inside the attention (abx_tri_attn_rowfused_fwd: L <= 352, split-f16, bias_is_qk rows;
+    bit-identical to gemm + tri_attn on the projected rows); slot_order: -1 library default, 0 = (b, row, h), 1 = (b, h, row);
     biasT (B,H,L,L) projected from the UNtransposed pair tensor (bias_is_qk=False) or
     already laid out [b,h,q,k] for this orientation (bias_is_qk=True; then (B,H,L,Lp) with rows padded to Lp % 4 == 0 floats gives
     the kernel 16-byte bias loads for any L); out (B*L*L, H*D)."""
     lib = _lib.load()
     W = qkvg.shape[1]
-    assert W in (3 * H * D, 4 * H * D) and qkvg.is_contiguous() and out.is_contiguous() and biasT.is_contiguous()
+    fused = rowpack is not None
+    assert (W == H * D) if fused else (W in (3 * H * D, 4 * H * D)), 'z rows (H*D wide) go with rowpack=, projected rows are 3 or 4 x H*D wide'
+    assert qkvg.is_contiguous() and out.is_contiguous() and biasT.is_contiguous()
     a = AbxTriAttn()
     es = qkvg.element_size()
     base = qkvg.data_ptr()
-    a.q, a.k, a.v = base, base + H * D * es, base + 2 * H * D * es
+    if not fused:
+        a.q, a.k, a.v = base, base + H * D * es, base + 2 * H * D * es
     if W == 4 * H * D:
         a.gate = base + 3 * H * D * es
     a.sb = L * L * W
@@ -631,6 +678,12 @@ def tri_attn(qkvg, biasT, keymask, out, B, L, per_row, H=4, D=48, bias_is_qk=Fal
     if clock_probe is not None:
         assert clock_probe.dtype == torch.int64 and clock_probe.numel() >= 2
         a.clock_probe = _p(clock_probe)
+    global _TRI_ATTN_LAST
+    _TRI_ATTN_LAST = (int(L), bool(a.exact), fused)
+    if fused:
+        assert not kv_planes and not a.exact and not tune, 'the row-fused kernel: split-f16, no operand images, no tune bits'
+        check(lib.abx_tri_attn_rowfused_fwd(C.byref(a), base, a.sb, a.ss, a.sl, C.byref(rowpack.c), int(slot_order), _stream()), 'abx_tri_attn_rowfused_fwd')
+        return out
     check(lib.abx_tri_attn_fwd(C.byref(a), _stream()), 'abx_tri_attn_fwd')
     return out
 

@@ -312,6 +312,36 @@ typedef struct AbxTriAttn {
 #define ABX_TRI_BIAS_LOG2 (1.4426950408889634f * 128.0f)
 int abx_tri_attn_fwd(const AbxTriAttn* desc, hipStream_t stream);
 
+/* Triangle attention with the q | k | v projection of the row inside (csrc/attention.hip tri_attn8_rowfused_kernel): replaces the
+ * LayerNorm -> proj_q | proj_k | proj_v GEMM (seqformer.py:520-529, :527-548) AND abx_tri_attn_fwd (Attention.forward :272-312) for rows of
+ * L <= ABX_TRI_ROWFUSED_LMAX.  q, k, v of pair row (b, s) are computed from z[b, s, :, :] in the workgroup that attends over that row (the
+ * arithmetic of the split-f16 GEMM: same pieces, same products in the same order, same folded-LayerNorm epilogue) and never reach memory;
+ * the output is bit-identical to abx_gemm (exact = 2, LayerNorm folded) followed by abx_tri_attn_fwd (exact = 0, bias_log2 as given).
+ * AbxTriRowPack: the q | k | v pack re-ordered per head ([k 48 | v 48 | q 48 + 16], columns permuted to the kernel's fragment order) by
+ * abx_tri_rowpack into caller memory of abx_tri_rowpack_bytes() (256-byte aligned; set-up work, asynchronous on the stream). */
+typedef struct AbxTriRowPack {
+    const unsigned short* planes;       /* [H][15 stages][4 k-tiles][2 planes][32 columns][16] float16 */
+    const float* csum;                  /* [H][160] column sums (folded LayerNorm) in packed column order */
+    const float* bias;                  /* [H][160] */
+    int b_exp;                          /* exponent of the planes (that of the source pack) */
+    int H;                              /* heads: 4 */
+} AbxTriRowPack;
+#define ABX_TRI_ROWFUSED_LMAX 352
+long long abx_tri_rowpack_bytes(void);
+/* (abx_tri_rowpack: declared with AbxLinearPack below) */
+/* 1 when abx_tri_attn_block_fwd takes the row-fused route for rows of length L: L <= ABX_TRI_ROWFUSED_LMAX (a function of L alone, never of
+ * the batch: a sample's bits do not depend on how many samples share a launch) and the environment variable ABX_NO_TRI_ROWFUSED is not
+ * set to something other than "0" (A/B measurements: forces the two launches). */
+int abx_tri_attn_rowfused_ok(int L);
+/* desc: as for abx_tri_attn_fwd with exact = 0, gate = NULL, kv_planes = 0, q_parts unused; q / k / v / sb / ss / sl are ignored; keymask
+ * may be NULL (no key masked).  The bias must be
+ * key-contiguous rows padded to a multiple of 4 floats, 16-byte aligned (bias_sk == 1: what abx_tri_attn_block_fwd passes).
+ * z: the pair rows, element (b, s, l, c) at z + b*zb + s*zs + l*zl + c (192 channels; the orientation is in zs / zl like ss / sl).
+ * slot_order: 0 = (b, row, h): the four heads of a row run on neighbouring workgroups of one XCD (z[b, s] is fetched from HBM once);
+ * 1 = (b, h, row): the order of tri_attn8_kernel (one bias map per XCD, z fetched four times); -1 = library default. */
+int abx_tri_attn_rowfused_fwd(const AbxTriAttn* desc, const float* z, long long zb, long long zs, long long zl, const AbxTriRowPack* pack,
+                              int slot_order, hipStream_t stream);
+
 /* Sequence attention with pair bias (seqformer.py:314-356 + Attention.forward split_first=False :278-312).
  * qkv: [B*L][H*3*D] with per-head layout [q D | k D | v D]; bias [b][h][q][k]; gate pre-activation [B*L][H*D];
  * out [B*L][H*D] = softmax(...) v * sigmoid(gate).  D <= 32. */
@@ -552,7 +582,12 @@ int abx_tri_mul_fwd(const AbxTriMulPack* w, const float* z_in, float* z_out, con
  * launches (gate projection * attention output into the workspace, output projection + residual).  exact here is two bits: bit 0 the
  * GEMMs, bit 1 the attention kernel (a small complex runs exact GEMMs - too few rows for the split tiles - with the split-f16
  * attention, which has no size limit: exact = 1; everything exact: exact = 3). */
-typedef struct AbxTriAttnPack { AbxLinearPack qkv, gate, pair, out; } AbxTriAttnPack;
+/* the head-major image of a q | k | v pack for abx_tri_attn_rowfused_fwd (AbxTriRowPack above).  qkv: LayerNorm-folded 192 -> 576 pack ([proj_q | proj_k | proj_v], 4 heads x 48 channels each) */
+int abx_tri_rowpack(const AbxLinearPack* qkv, void* buf, AbxTriRowPack* out, hipStream_t stream);
+/* row: optional (planes == NULL: never the row-fused route) - abx_tri_rowpack of qkv.  With it, exact = 0 and abx_tri_attn_rowfused_ok(L) the
+ * launches are: the pair-bias projection alone (abx_gemm), the bias transpose / pad, abx_tri_attn_rowfused_fwd, the gated tail; the
+ * q | k | v region of the workspace is not written.  Same bits as the route above. */
+typedef struct AbxTriAttnPack { AbxLinearPack qkv, gate, pair, out; AbxTriRowPack row; } AbxTriAttnPack;
 long long abx_tri_attn_block_workspace_bytes(int B, int L);
 int abx_tri_attn_block_fwd(const AbxTriAttnPack* w, float* z, const float* mask, int B, int L, int per_row, int exact, void* workspace,
                            int* range_flag, int range_tag, hipStream_t stream);

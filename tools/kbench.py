@@ -188,6 +188,19 @@ def main():
         for per_row in (True, False):
             ms = timeit(lambda: ops.tri_attn(x, bT, mask, o, Bc, L, per_row, bias_is_qk=True))
             rec(f'tri_attn per_row={per_row}', ms, 4.0 * Bc * L * 4 * LL * 48, 4.0 * M2 * (768 + 192))
+        if L <= 352 and L % 4 == 0:
+            # the row-fused route: q | k | v projected inside the attention from the z rows (tools/probes/kb_tri_rowfused.py compares the routes)
+            Wl = lambda n: r(n, 192) / 14
+            rowp = ops.TriRowPack(ops.LinearPack([(Wl(192), r(192), 0), (Wl(192), r(192), 0), (Wl(192), r(192), 0)], 192,
+                                                 ln=(1.0 + 0.2 * r(192), 0.1 * r(192))))
+            zr, b4 = r(M2, 192), bT.view(Bc, 4, L, L)
+            for per_row in (True, False):
+                ms = timeit(lambda: ops.tri_attn(zr, b4, mask, o, Bc, L, per_row, bias_is_qk=True, bias_log2=True, rowpack=rowp))
+                rec(f'tri_attn rowfused per_row={per_row}', ms, 4.0 * Bc * L * 4 * LL * 48 + 2.0 * M2 * 576 * 192, 4.0 * M2 * (192 + 192 + 4))
+            Wp = r(192, 4) / 14
+            bp, csp, Wp3 = r(4), Wp.sum(0).contiguous(), ops.split_weights(Wp)
+            ms = timeit(lambda: ops.gemm(zr.view(Bc, LL, 192), Wp, bT.transpose(1, 2), bias=bp, ln=(None, csp), B3=Wp3, exact=2, alpha=ops.TRI_BIAS_LOG2))
+            rec('pair bias alone N=4 + LN (T-store)', ms, 2.0 * M2 * 4 * 192, 4.0 * M2 * (192 + 4))
         bT2 = torch.empty_like(bT)
         ms = timeit(lambda: ops.transpose_last2(bT.view(Bc * 4, L, L), bT2.view(Bc * 4, L, L)))
         rec('transpose_last2 (bias)', ms, 0, 8.0 * Bc * 4 * LL)

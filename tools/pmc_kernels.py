@@ -3,7 +3,8 @@
     python tools/pmc_kernels.py <which> [Bc] [L]
 which: qkvg (LN -> 768, gemm3 128x128 tiles: tune 2048)  qkv (round 5: LN -> q | k | v 576 + pair-bias side, A-stationary kernel)
        gtail (gated tail of the triangle attention, AbxGemm.mlp = 2)  mlp (fused transition)  trans2 (768 -> 192 + resid, gemm3 128x192)  glu (LN -> glu planes, transposed store)
-       contract (plane x plane)  projout (channel-major A, gate, resid)  tri (triangle attention)  ipa (IPA attention)"""
+       contract (plane x plane)  projout (channel-major A, gate, resid)  tri (triangle attention)  ipa (IPA attention)
+       trif / trif1 (row-fused triangle attention on the z rows, slot order (b, row, h) / (b, h, row))  pairbias (the 4-column pair-bias projection alone)"""
 import os
 import sys
 
@@ -72,6 +73,18 @@ elif which == 'tri':
     x, bT, mask, o = r(M2, 576), r(Bc, 4, LL), torch.ones(Bc, L, device=DEV), torch.empty(M2, 192, device=DEV)       # (q | k | v: no gate since round 5)
     for _ in range(REPS):
         ops.tri_attn(x, bT, mask, o, Bc, L, True, bias_is_qk=True)
+elif which in ('trif', 'trif1'):
+    W = lambda n: r(n, 192) / 14
+    ln = (1.0 + 0.2 * r(192), 0.1 * r(192))
+    rowp = ops.TriRowPack(ops.LinearPack([(W(192), r(192), 0), (W(192), r(192), 0), (W(192), r(192), 0)], 192, ln=ln))
+    z, bT, mask, o = r(M2, 192), r(Bc, 4, L, L), torch.ones(Bc, L, device=DEV), torch.empty(M2, 192, device=DEV)
+    for _ in range(REPS):
+        ops.tri_attn(z, bT, mask, o, Bc, L, True, bias_is_qk=True, bias_log2=True, rowpack=rowp, slot_order=1 if which == 'trif1' else 0)
+elif which == 'pairbias':
+    z, Wp = r(Bc, LL, 192), r(192, 4) / 14
+    bT, bp, csp, Wp3 = torch.empty(Bc, 4, LL, device=DEV), r(4), Wp.sum(0).contiguous(), ops.split_weights(Wp)
+    for _ in range(REPS):
+        ops.gemm(z, Wp, bT.transpose(1, 2), bias=bp, ln=(None, csp), B3=Wp3, exact=2, alpha=ops.TRI_BIAS_LOG2)
 elif which == 'ipa':
     M1 = Bc * L
     qp, kp, vp = r(ops.ipa_qpack_numel(Bc, L)), r(M1 * 12 * 28), r(M1 * 12 * 40)
