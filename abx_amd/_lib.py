@@ -185,6 +185,24 @@ class AbxGuidanceArgs(C.Structure):
     ]
 
 
+SCORE_COLS = 19           # ABX_SCORE_COLS
+
+
+class AbxDesignScoreArgs(C.Structure):
+    _fields_ = [
+        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
+        ('pred_seq', c_f), ('pred_seq_sb', LL),
+        ('pred_mask', c_f), ('res_mask', c_f),
+        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+        ('cdr_def', c_f), ('chain_id', c_f), ('residx', c_f),
+        ('complex_batched', I),
+        ('radius', c_f),
+        ('overlap_tolerance', F), ('bond_tolerance_factor', F),
+        ('out', c_f), ('out_stride', LL),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -236,6 +254,8 @@ _PROTOS = {
     'abx_reverse_step': (I, [C.POINTER(AbxReverseArgs), _S]),
     'abx_clash_grad_workspace_bytes': (LL, [I, I]),
     'abx_clash_grad': (I, [C.POINTER(AbxGuidanceArgs), c_f, _S]),
+    'abx_design_scores_workspace_bytes': (LL, [I, I]),
+    'abx_design_scores': (I, [C.POINTER(AbxDesignScoreArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

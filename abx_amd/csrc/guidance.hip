@@ -20,6 +20,7 @@
 // itself (56 KB per sample), so the kernel is ALU / LDS bound and far from any roofline that matters for the step (< 0.1 ms).
 #include "common.h"
 #include "abx_hip.h"
+#include "peptide_dev.h"
 
 namespace {
 
@@ -30,9 +31,7 @@ constexpr int AT = RT * 14;            // atoms per tile (224)
 // consecutive numbers (a cropped antigen patch or a chain with missing residues keeps one chain id across the gap)
 __device__ __forceinline__ bool linked_to_prev(const AbxGuidanceArgs& a, long long ab, int res) {
     if (res <= 0 || res >= a.L) return false;
-    const long long r = ab + res;
-    if (a.chain_id[r] != a.chain_id[r - 1]) return false;
-    return !a.residx || a.residx[r] == a.residx[r - 1] + 1;
+    return linked_rows(a.chain_id, a.residx, ab + res);
 }
 
 __global__ __launch_bounds__(256) void clash_kernel(const AbxGuidanceArgs a, float* __restrict__ epart) {
@@ -102,75 +101,20 @@ __global__ __launch_bounds__(256) void clash_kernel(const AbxGuidanceArgs a, flo
     if (tid == 0) epart[(long long)b * gridDim.x + it] = (ered[0] + ered[1]) + (ered[2] + ered[3]);
 }
 
-// Flat-bottom term relu(sqrt(1e-6 + (v - v0)^2) - tol * sd): returns the energy, `slope` = dE/dv (0 inside the flat bottom)
-__device__ __forceinline__ float flat_bottom(float v, float v0, float tol_sd, float& slope) {
-    const float err = sqrtf(1e-6f + (v - v0) * (v - v0));
-    const float e = err - tol_sd;
-    slope = e > 0.f ? (v - v0) / err : 0.f;
-    return e > 0.f ? e : 0.f;
-}
-
-// Peptide-geometry terms of the residue pair (l, l + 1) (eval/metric_scripts/cal_vio.py:29-110): the C-N bond length and the cosines
-// of the CA-C-N and C-N-CA angles against their literature values (abx/common/residue_constants.py:475-480), each a flat-bottom
-// violation.  g[0..3] receive dE/d(CA_l, C_l, N_u, CA_u) of THIS pair, eb / ea the bond / angle energies.
-struct PairGrad { float g[4][3]; float eb, ea; };
+// The peptide terms (peptide_dev.h::peptide_terms) of the residue pair (l, l + 1): zero when the pair is not linked or its C / N is
+// missing.  g[0..3] receive dE/d(CA_l, C_l, N_u, CA_u) of THIS pair, eb / ea the bond / angle energies.
 __device__ __forceinline__ void peptide_pair(const AbxGuidanceArgs& a, long long ab, int l, PairGrad& o) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) o.g[k][0] = o.g[k][1] = o.g[k][2] = 0.f;
     o.eb = o.ea = 0.f;
+    o.viol = 0;
     if (l < 0 || !linked_to_prev(a, ab, l + 1)) return;
     const long long r = ab + l;
     const bool m_ca = a.atom_mask[r * 14 + 1] != 0, m_c = a.atom_mask[r * 14 + 2] != 0;
     const bool m_n = a.atom_mask[(r + 1) * 14 + 0] != 0, m_ca2 = a.atom_mask[(r + 1) * 14 + 1] != 0;
     if (!m_c || !m_n) return;
-    const float* ca = a.atom14 + (r * 14 + 1) * 3;
-    const float* c = a.atom14 + (r * 14 + 2) * 3;
-    const float* n = a.atom14 + ((r + 1) * 14 + 0) * 3;
-    const float* ca2 = a.atom14 + ((r + 1) * 14 + 1) * 3;
-    const bool pro = a.aatype[r + 1] == 14;
-    const float l0 = pro ? 1.341f : 1.329f, sd = pro ? 0.016f : 0.014f;
-    // ---- bond: v = |C - N|
-    const float bx = n[0] - c[0], by = n[1] - c[1], bz = n[2] - c[2];           // C -> N
-    const float d = sqrtf(1e-6f + bx * bx + by * by + bz * bz);
-    float sl;
-    o.eb = a.w_bond * flat_bottom(d, l0, a.bond_tolerance_factor * sd, sl);
-    {
-        const float s = a.w_bond * sl / d;                                      // dE/dN = s * (N - C)
-        o.g[2][0] += s * bx; o.g[2][1] += s * by; o.g[2][2] += s * bz;
-        o.g[1][0] -= s * bx; o.g[1][1] -= s * by; o.g[1][2] -= s * bz;
-    }
-    if (a.w_angle == 0.f) return;
-    // unit vector C -> N (l2_normalize: x / sqrt(max(|x|^2, 1e-12)), abx/model/utils.py:12-14)
-    const float nb = sqrtf(fmaxf(bx * bx + by * by + bz * bz, 1e-12f));
-    const float vx = bx / nb, vy = by / nb, vz = bz / nb;
-    // cos(x, y) of unit vectors u = p / |p|, v = q / |q| about a vertex: d cos / dp = (v - cos u) / |p|, d cos / dq = (u - cos v) / |q|
-    if (m_ca) {     // ---- CA_l - C_l - N_u  (vertex C): p = CA - C, q = N - C
-        const float px = ca[0] - c[0], py = ca[1] - c[1], pz = ca[2] - c[2];
-        const float np_ = sqrtf(fmaxf(px * px + py * py + pz * pz, 1e-12f));
-        const float ux = px / np_, uy = py / np_, uz = pz / np_;
-        const float cs = ux * vx + uy * vy + uz * vz;
-        const float e = flat_bottom(cs, -0.4473f, a.bond_tolerance_factor * 0.0311f, sl);
-        o.ea += a.w_angle * e;
-        const float k = a.w_angle * sl;
-        const float gp[3] = {k * (vx - cs * ux) / np_, k * (vy - cs * uy) / np_, k * (vz - cs * uz) / np_};
-        const float gq[3] = {k * (ux - cs * vx) / nb, k * (uy - cs * vy) / nb, k * (uz - cs * vz) / nb};
-#pragma unroll
-        for (int x = 0; x < 3; ++x) { o.g[0][x] += gp[x]; o.g[2][x] += gq[x]; o.g[1][x] -= gp[x] + gq[x]; }
-    }
-    if (m_ca2) {    // ---- C_l - N_u - CA_u  (vertex N): p = C - N = -b, q = CA_u - N
-        const float qx = ca2[0] - n[0], qy = ca2[1] - n[1], qz = ca2[2] - n[2];
-        const float nq = sqrtf(fmaxf(qx * qx + qy * qy + qz * qz, 1e-12f));
-        const float wx = qx / nq, wy = qy / nq, wz = qz / nq;
-        const float ux = -vx, uy = -vy, uz = -vz;
-        const float cs = ux * wx + uy * wy + uz * wz;
-        const float e = flat_bottom(cs, -0.5203f, a.bond_tolerance_factor * 0.0353f, sl);
-        o.ea += a.w_angle * e;
-        const float k = a.w_angle * sl;
-        const float gp[3] = {k * (wx - cs * ux) / nb, k * (wy - cs * uy) / nb, k * (wz - cs * uz) / nb};
-        const float gq[3] = {k * (ux - cs * wx) / nq, k * (uy - cs * wy) / nq, k * (uz - cs * wz) / nq};
-#pragma unroll
-        for (int x = 0; x < 3; ++x) { o.g[1][x] += gp[x]; o.g[3][x] += gq[x]; o.g[2][x] -= gp[x] + gq[x]; }
-    }
+    peptide_terms(a.atom14 + (r * 14 + 1) * 3, a.atom14 + (r * 14 + 2) * 3, a.atom14 + ((r + 1) * 14 + 0) * 3,
+                  a.atom14 + ((r + 1) * 14 + 1) * 3, m_ca, m_ca2, a.aatype[r + 1] == 14, a.w_bond, a.w_angle, a.bond_tolerance_factor, o);
 }
 
 // Peptide bond / angle terms added to grad_atom, then the frame pull-back.  One thread per RESIDUE: it owns the backbone atoms

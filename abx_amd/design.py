@@ -5,6 +5,7 @@ and write the PDB files (per step in trajectory mode, asynchronously).
     python -m abx_amd.design --pdb_file 6ct7_H_L_S.pdb --num_samples 100 --mode design --output_dir out/      (raw PDB, 8f-1)
     python -m abx_amd.design --workload L256 --num_samples 4 --mode trajectory --num_t 10 --output_dir out/   (synthetic complex)
     python -m abx_amd.design --pdb_file 6ct7_H_L_S.pdb --mode optimize --optimize_steps 10 --guidance --num_samples 100     (config 4)
+    python -m abx_amd.design --pdb_file 6ct7_H_L_S.pdb --num_samples 100 --score --output_dir out/     (+ per-CDR RMSD / AAR, violation and clash counts)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m abx_amd.design \
         --pdb_list diffab_test.txt --pdb_dir pdbs/ --num_samples 100 --output_dir out/                        (a test set on 8 GPUs)
 
@@ -27,6 +28,8 @@ Multi-GPU (one process per GPU under torch.distributed.run): the SAMPLES of ever
 (sampler.shard_sample_ids: contiguous blocks; per-sample noise keys, so a sample's trajectory does not depend on where it runs),
 every rank writes the PDB files of its own samples, and the designed sequences / pLDDT are gathered with one RCCL all_gather per
 field (sampler.gather_results) for `<output_dir>/<complex>_designs.tsv`, written by rank 0.
+--score: every design is scored on the GPU as its record is made (abx_amd.metrics.DesignScorer, one launch pair per record, no host
+synchronisation); the scores travel as one more field of the same gathers and become the columns metrics.SCORE_COLUMNS of the TSV.
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -77,12 +80,33 @@ def read_model_features(path):
 
 
 def _write_designs(out_dir, cname, rows):
-    """<out_dir>/<complex>_designs.tsv: (sample id, mean pLDDT, designed antibody sequence) per sample."""
+    """<out_dir>/<complex>_designs.tsv: (sample id, mean pLDDT, designed antibody sequence) per sample; with --score a row carries
+    a fourth entry, its metrics.SCORE_COLUMNS values, written as further columns."""
     tsv = os.path.join(out_dir, f'{cname}_designs.tsv')
+    scored = bool(rows) and len(rows[0]) > 3
     with open(tsv, 'w') as f:
-        f.write('sample\tmean_pLDDT\tantibody_sequence\n')
-        for i, pl, toks in rows:
-            f.write(f'{i}\t{pl:.3f}\t{index_to_str_seq(toks)}\n')
+        if scored:
+            from .metrics import SCORE_COLUMNS, format_scores
+            f.write('sample\tmean_pLDDT\tantibody_sequence\t' + '\t'.join(SCORE_COLUMNS) + '\n')
+            for i, pl, toks, sc in rows:
+                f.write(f'{i}\t{pl:.3f}\t{index_to_str_seq(toks)}\t' + '\t'.join(format_scores(sc)) + '\n')
+        else:
+            f.write('sample\tmean_pLDDT\tantibody_sequence\n')
+            for i, pl, toks in rows:
+                f.write(f'{i}\t{pl:.3f}\t{index_to_str_seq(toks)}\n')
+    return tsv
+
+
+def _write_trajectory_scores(out_dir, cname, table):
+    """<out_dir>/<complex>_trajectory_scores.tsv: one line per (sample, record of the trajectory).  table (samples, records, 1 + columns):
+    t of the record, then its metrics.SCORE_COLUMNS values."""
+    from .metrics import SCORE_COLUMNS, format_scores
+    tsv = os.path.join(out_dir, f'{cname}_trajectory_scores.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\tstep\tt\t' + '\t'.join(SCORE_COLUMNS) + '\n')
+        for i, recs in enumerate(table.tolist()):
+            for k, r in enumerate(recs):
+                f.write(f'{i}\t{k}\t{r[0]:.4f}\t' + '\t'.join(format_scores(r[1:])) + '\n')
     return tsv
 
 
@@ -135,6 +159,9 @@ def main(argv=None):
                     '1-rank all_gather (exercises the collective path on a 1-GPU box; same results)')
     ap.add_argument('--exact_gemm', action='store_true', help='exact fp32-MFMA kernels instead of the split-f16 ones (slower; the remedy when '
                     'the sampler reports non-finite frames: an activation beyond the split kernels\' range)')
+    ap.add_argument('--score', action='store_true', help='score every design on the GPU (abx_design_scores): per-CDR RMSD / AAR against the '
+                    'input structure, peptide-violation and clash counts as further columns of <complex>_designs.tsv; in trajectory mode also '
+                    '<complex>_trajectory_scores.tsv with one line per sample and step')
     a = ap.parse_args(argv)
     if a.exact_gemm:
         from abx_amd import ops
@@ -253,6 +280,11 @@ def main(argv=None):
                   f'rank {rank} runs {[(jobs[ji][1], len(ids_)) for ji, ids_ in work]}')
     set_rows = []                                               # set-level mode: (job, sample id, mean pLDDT, Lab, tokens...) rows of this rank
     maxLab = max([load_job(ji)['Lab'] for ji in range(len(jobs))]) if plan is not None else 0
+    NS = 0                                                      # --score: score columns per sample (+ (t, scores) of every trajectory record)
+    if a.score:
+        from .metrics import SCORE_COLUMNS, DesignScorer
+        NS = len(SCORE_COLUMNS)
+    n_rec = a.num_t if (a.score and a.mode == 'trajectory') else 0
 
     ref_written = set()
     for ji, ids in work:
@@ -298,7 +330,8 @@ def main(argv=None):
             torch.cuda.synchronize()
             t_feat = time.perf_counter()
             traj = sampler.sample_fn(batch, cfg, diffuser, model, mode=a.mode, num_t=a.num_t,
-                                     sample_ids=torch.tensor(ids, device=dev, dtype=torch.int64), on_record=writer.submit, guidance=guide)
+                                     sample_ids=torch.tensor(ids, device=dev, dtype=torch.int64), on_record=writer.submit, guidance=guide,
+                                     **({'scorer': DesignScorer(batch)} if a.score else {}))
             torch.cuda.synchronize()
             t_samp = time.perf_counter()
             new_files = writer.close()
@@ -309,23 +342,40 @@ def main(argv=None):
                                 range_fallbacks=len(traj[-1].get('range_fallbacks', [])),
                                 range_sticky_ops=list(traj[-1].get('range_sticky_ops', []))))
             local = {'seq': traj[-1]['seq'], 'pLDDT': traj[-1]['pLDDT']}
+            if a.score:
+                local['scores'] = traj[-1]['scores']
+                if n_rec:                                       # (samples, records, 1 + NS): t, then the scores of the record
+                    local['traj_scores'] = torch.stack([torch.cat([torch.full((n, 1), r['time'], dtype=torch.float64, device=dev), r['scores']], 1)
+                                                        for r in traj], 1)
         else:                                                   # more ranks than samples: join the gather with zero-row blocks
             local = {'seq': torch.zeros(0, Lab, dtype=torch.int64, device=dev), 'pLDDT': torch.zeros(0, Lab, device=dev)}
+            if a.score:
+                local['scores'] = torch.zeros(0, NS, dtype=torch.float64, device=dev)
+                if n_rec:
+                    local['traj_scores'] = torch.zeros(0, n_rec, 1 + NS, dtype=torch.float64, device=dev)
         if plan is not None:
-            row = torch.zeros(n, 4 + maxLab, dtype=torch.float64)
+            row = torch.zeros(n, 4 + maxLab + NS + n_rec * (1 + NS), dtype=torch.float64)
             row[:, 0], row[:, 1], row[:, 3] = ji, torch.tensor(ids, dtype=torch.float64), Lab
             row[:, 2] = local['pLDDT'].float().mean(1).double().cpu()       # (the float32 mean of the sample-sharded path: same TSV digits)
             row[:, 4:4 + Lab] = local['seq'].double().cpu()
+            if a.score:
+                row[:, 4 + maxLab:4 + maxLab + NS] = local['scores'].cpu()
+                if n_rec:
+                    row[:, 4 + maxLab + NS:] = local['traj_scores'].reshape(n, -1).cpu()
             set_rows.append(row)
             continue
         if a.debug_one_gpu and world > 1:                       # gloo moves host tensors
             local = {k: v.cpu() for k, v in local.items()}
         res = sampler.gather_results(local, N, rank, world, group, force=a.force_collective)
         if rank == 0:
-            files.append(_write_designs(out_dir, cname, [(i, float(res['pLDDT'][i].float().mean()), res['seq'][i].tolist()) for i in range(N)]))
+            sc = res['scores'].tolist() if a.score else None
+            files.append(_write_designs(out_dir, cname, [(i, float(res['pLDDT'][i].float().mean()), res['seq'][i].tolist()) + ((sc[i],) if a.score else ())
+                                                         for i in range(N)]))
+            if n_rec:
+                files.append(_write_trajectory_scores(out_dir, cname, res['traj_scores'].cpu()))
     if plan is not None:
         # ---- the one collective of the set: every rank's rows of the designs table (counts known from the common plan)
-        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, 4 + maxLab, dtype=torch.float64)
+        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, 4 + maxLab + NS + n_rec * (1 + NS), dtype=torch.float64)
         if not (a.debug_one_gpu and world > 1):
             table = table.to(dev)
         counts = [sum(len(ids_) for _, ids_ in p) for p in plan]
@@ -336,7 +386,10 @@ def main(argv=None):
                 rows = rows[torch.argsort(rows[:, 1])]
                 assert rows.shape[0] == N, (jobs[ji][1], rows.shape)
                 files.append(_write_designs(jobs[ji][2], load_job(ji)['cname'],
-                                            [(int(r[1]), float(r[2]), r[4:4 + int(r[3])].long().tolist()) for r in rows]))
+                                            [(int(r[1]), float(r[2]), r[4:4 + int(r[3])].long().tolist()) +
+                                             ((r[4 + maxLab:4 + maxLab + NS].tolist(),) if a.score else ()) for r in rows]))
+                if n_rec:
+                    files.append(_write_trajectory_scores(jobs[ji][2], load_job(ji)['cname'], rows[:, 4 + maxLab + NS:].reshape(N, n_rec, 1 + NS)))
     if world > 1 or a.force_collective:
         import torch.distributed as dist
         dist.barrier()

@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1040,3 +1040,60 @@ def clash_grad(atom14, atom_mask, aatype, chain_id, frame_trans, overlap_toleran
     a.B, a.L = B, L
     check(lib.abx_clash_grad(C.byref(a), _p(ws), _stream()), 'abx_clash_grad')
     return energy, g_atom, g_t, g_r
+
+
+def design_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, cdr_def, chain_id, Lab=None, residx=None, mask=None, res_mask=None,
+                  overlap_tolerance=1.5, bond_tolerance_factor=12.0, out=None):
+    """Per-structure design scores (abx_design_scores; columns: abx_amd.metrics.SCORE_COLUMNS).
+    atom14 (B,Lp,14,3) f32 with Lab <= Lp <= L (rows beyond Lp take the ground-truth coordinates; the batch stride is free: a
+    [:, :Lab] view of a (B,L,14,3) tensor is read in place), seq (B,>=Lab) int64 predicted tokens.
+    The complex, shared by the B structures ((L,...) tensors) or one per structure ((B,L,...)): gt_atom14 (L,14,3) f32, gt_seq (L) int64,
+    gt_exists (L,14), chain_id (L) int32, residx (L) int32 or None (None: neighbours are linked by chain id alone); cdr_def (L) int32.
+    mask (B,L,14) or None (None: the atoms of the residue types); res_mask (L) or None.
+    out: (B, 19) float64 with unit column stride and any row stride (rows of a preallocated table), or None.  No synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = cdr_def.shape[-1]
+    B, Lp = atom14.shape[0], atom14.shape[1]
+    Lab = int(seq.shape[1] if Lab is None else Lab)
+    batched = gt_atom14.dim() == 4
+    lead = (B, L) if batched else (L,)
+    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
+    assert tuple(gt_atom14.shape) == lead + (14, 3) and tuple(gt_exists.shape) == lead + (14,) and tuple(gt_seq.shape) == lead and \
+        tuple(chain_id.shape) == lead and tuple(cdr_def.shape) == (L,), 'complex tensors: (L,...) shared or (B,L,...) per structure'
+    x = _f32(atom14)
+    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
+        x = x.contiguous()
+    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
+    keep = [x, sq]
+
+    def own(t, dtype):
+        t = t.to(dtype).contiguous()
+        keep.append(t)
+        return _p(t)
+
+    a = AbxDesignScoreArgs()
+    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
+    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
+    if mask is not None:
+        assert tuple(mask.shape) == (B, L, 14), mask.shape
+        a.pred_mask = own(mask, torch.uint8)
+    if res_mask is not None:
+        assert tuple(res_mask.shape) == (L,), res_mask.shape
+        a.res_mask = own(res_mask, torch.uint8)
+    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
+    a.cdr_def, a.chain_id = own(cdr_def, torch.int32), own(chain_id, torch.int32)
+    if residx is not None:
+        assert tuple(residx.shape) == lead, residx.shape
+        a.residx = own(residx, torch.int32)
+    a.complex_batched = 1 if batched else 0
+    a.radius = _p(vdw_radius_table(dev))
+    a.overlap_tolerance, a.bond_tolerance_factor = float(overlap_tolerance), float(bond_tolerance_factor)
+    if out is None:
+        out = torch.empty(B, _lib.SCORE_COLS, dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (B, _lib.SCORE_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (B, 19) float64 rows'
+    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else _lib.SCORE_COLS
+    a.B, a.L, a.Lab = B, L, Lab
+    ws = torch.empty(max(int(lib.abx_design_scores_workspace_bytes(B, L)), 8), dtype=torch.uint8, device=dev)
+    check(lib.abx_design_scores(C.byref(a), _p(ws), _stream()), 'abx_design_scores')
+    return out

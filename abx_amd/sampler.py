@@ -23,7 +23,8 @@ def set_t_feats(feats, diffuser, t, ones):
 
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
-              noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False):
+              noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
+              scorer=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -31,7 +32,9 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     guidance: None (the reference's un-guided sampler, bit-identical code path) or an abx_amd.guidance.ViolationGuidance whose
     clash / bond gradients on the predicted structure are subtracted from the scores before the reverse step.
     use_graph: record the step into two hipGraphs (abx_amd.graph.GraphedSteps) after one eager step and replay them; needs the
-    device noise generator (noise_fn None) and gives the same results as the eager loop."""
+    device noise generator (noise_fn None) and gives the same results as the eager loop.
+    scorer: None, or an abx_amd.metrics.DesignScorer of the complex: every record gets 'scores' (B, len(metrics.SCORE_COLUMNS)) float64,
+    rows of one table allocated before the loop; one launch pair per record, outside any captured step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -50,6 +53,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     batch.pop('_static', None)          # trajectory-invariant embeddings: rebuilt once per trajectory from THIS batch
     log_start = len(getattr(model, 'range_log', None) or [])     # (the model's range log is cumulative: report this trajectory's part)
     traj = []
+    score_table = scorer.new_table(len(steps) if mode == 'trajectory' else 1, B) if scorer is not None else None
     with torch.no_grad():
         if sc_conf.embed.embed_self_conditioning and self_condition and len(steps) > 0:
             batch = set_t_feats(batch, diffuser, float(steps[0]), ones)
@@ -93,6 +97,8 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                    'pLDDT': torch.tile(pl[:, None], (1, Lab)), 'time': float(t), 'rigids_t': rigids_t, 'seq_t': seq_t}
             if mode == 'trajectory' or k == len(steps) - 1:
                 traj.append({kk: (v.clone() if torch.is_tensor(v) else v) for kk, v in rec.items()})
+                if scorer is not None:
+                    traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)

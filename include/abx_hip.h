@@ -524,6 +524,49 @@ long long abx_clash_grad_workspace_bytes(int B, int L);
 int abx_clash_grad(const AbxGuidanceArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Design scores (SURVEY.md 8f-4 "eval metrics"): what the reference computes offline from the written PDB files, per structure of a
+ * batch of B designs of ONE complex, on the device.  One row of ABX_SCORE_COLS float64 values per structure:
+ *   0-13  {heavy,light}_cdr{1,2,3}_{AAR,RMSD} and heavy_cdr3_Loop_{AAR,RMSD} in the order of abx/common/ab_utils.py:124-167
+ *         (calc_ab_metrics; abx_amd.metrics.SCORE_COLUMNS): ONE Kabsch superposition (abx/utils.py:444-465, the optimal proper
+ *         rotation) of the antibody C-alpha (rows < Lab, slot 1) on the ground truth, then sqrt(mean |delta|^2) and the fraction of
+ *         equal tokens over the rows whose cdr_def is 1 / 3 / 5 / 8 / 10 / 12; Loop = rows [4:-2] of the CDR-H3 rows in sequence order.
+ *         A row whose ground-truth C-alpha does not exist is left out of the fit, the RMSD and the AAR (the Loop slice is taken
+ *         before that); a region without rows gives NaN in both of its columns.  Centroids, covariance, rotation (Horn's quaternion
+ *         form, Jacobi sweeps on the 4x4 matrix) and deviations are float64.
+ *   14-16 n_viol_c_n, n_viol_ca_c_n, n_viol_c_n_ca: the sums of the three violation masks of between_residue_bond_loss
+ *         (eval/metric_scripts/cal_vio.py:74-75, 93-94, 107-108) in its fp32 arithmetic; linked pairs as in AbxGuidanceArgs.
+ *   17-18 n_clash, n_clash_inter: the number of atom pairs (each once) with d < r_a + r_b - overlap_tolerance under the pair rules of
+ *         the clash energy of abx_clash_grad (the same fp32 expression: n_clash > 0 exactly when that energy is positive), and those
+ *         of them whose atoms carry different chain ids.
+ * The predicted structure: pred_atom14 (B, Lpred, 14, 3) with Lab <= Lpred <= L and the batch stride pred_sb (floats), pred_seq
+ * (B, >= Lab) tokens with the batch stride pred_seq_sb; rows >= Lpred take their coordinates, rows >= Lab their residue type from the
+ * ground truth (a sampler record holds the antibody only).  pred_mask (B, L, 14) is optional: NULL = an atom exists where the radius
+ * table of its residue type is positive (rows >= Lpred: where the ground-truth atom exists).  res_mask (L) optional: 0 removes a
+ * (padding) row from the violation and clash counts.
+ * The complex: gt_atom14 (L,14,3), gt_exists (L,14), gt_seq (L), chain_id (L), residx (L, optional) shared by the B structures
+ * (complex_batched = 0) or one per structure (complex_batched = 1: (B,L,...)); cdr_def (L) is always shared.
+ * out: row b starts at out + b * out_stride (doubles, out_stride >= ABX_SCORE_COLS): successive calls can fill successive rows of
+ * one table.  Two launches, no synchronisation, no allocation; the caller allocates the workspace
+ * (abx_design_scores_workspace_bytes).  L > 1 as for abx_clash_grad. */
+#define ABX_SCORE_COLS 19
+typedef struct AbxDesignScoreArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const int* cdr_def; const int* chain_id;
+    const int* residx;                              /* optional residue numbers */
+    int complex_batched;
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs */
+    float overlap_tolerance, bond_tolerance_factor;
+    double* out; long long out_stride;
+    int B, L, Lab;
+} AbxDesignScoreArgs;
+long long abx_design_scores_workspace_bytes(int B, int L);
+int abx_design_scores(const AbxDesignScoreArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
