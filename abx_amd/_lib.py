@@ -203,6 +203,27 @@ class AbxDesignScoreArgs(C.Structure):
     ]
 
 
+RELAX_COLS = 11           # ABX_RELAX_COLS
+
+
+class AbxRelaxArgs(C.Structure):
+    _fields_ = [
+        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
+        ('pred_seq', c_f), ('pred_seq_sb', LL),
+        ('pred_mask', c_f), ('res_mask', c_f),
+        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+        ('chain_id', c_f), ('residx', c_f), ('movable', c_f),
+        ('radius', c_f), ('chi_axis', c_f), ('rigid_group', c_f),
+        ('overlap_tolerance', F), ('between_chain_factor', F), ('bond_tolerance_factor', F), ('w_clash', F), ('w_bond', F), ('w_angle', F),
+        ('k_restraint', F), ('eta0', F), ('rho', F), ('grow', F), ('shrink', F),
+        ('max_iter', I),
+        ('out_atom14', c_f), ('out_sb', LL),
+        ('report', c_f), ('report_stride', LL),
+        ('gen_grad', c_f),
+        ('B', I), ('L', I), ('Lab', I), ('M', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -256,6 +277,9 @@ _PROTOS = {
     'abx_clash_grad': (I, [C.POINTER(AbxGuidanceArgs), c_f, _S]),
     'abx_design_scores_workspace_bytes': (LL, [I, I]),
     'abx_design_scores': (I, [C.POINTER(AbxDesignScoreArgs), c_f, _S]),
+    'abx_relax_workspace_bytes': (LL, [I, I, I]),
+    'abx_relax_lds_bytes': (LL, [I, I]),
+    'abx_relax': (I, [C.POINTER(AbxRelaxArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

@@ -30,6 +30,11 @@ every rank writes the PDB files of its own samples, and the designed sequences /
 field (sampler.gather_results) for `<output_dir>/<complex>_designs.tsv`, written by rank 0.
 --score: every design is scored on the GPU as its record is made (abx_amd.metrics.DesignScorer, one launch pair per record, no host
 synchronisation); the scores travel as one more field of the same gathers and become the columns metrics.SCORE_COLUMNS of the TSV.
+--relax: every design is relaxed on the GPU after the last step (abx_amd.relax.ViolationRelaxer, abx_relax: one launch per batch): the
+violation energy of the designed residues (+ --relax_flank linked neighbours on each side) is minimised over rigid-body motions and chi
+angles of those residues; <name>_relaxed.pdb is written beside every design (upstream's naming, which its eval_metric.py skips) and
+<output_dir>/<complex>_relax.tsv holds one line per sample: relax.RELAX_COLUMNS and, with --score, the scores of the relaxed structure.
+The design files and <complex>_designs.tsv are what they are without --relax.
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -110,6 +115,20 @@ def _write_trajectory_scores(out_dir, cname, table):
     return tsv
 
 
+def _write_relax(out_dir, cname, rows, scored):
+    """<out_dir>/<complex>_relax.tsv: (sample id, values) per sample; values = the relax.RELAX_COLUMNS report and, when scored, the
+    metrics.SCORE_COLUMNS of the relaxed structure."""
+    from .relax import RELAX_COLUMNS, format_report
+    from .metrics import SCORE_COLUMNS, format_scores
+    NR = len(RELAX_COLUMNS)
+    tsv = os.path.join(out_dir, f'{cname}_relax.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(RELAX_COLUMNS + (SCORE_COLUMNS if scored else ())) + '\n')
+        for i, v in rows:
+            f.write(f'{i}\t' + '\t'.join(format_report(v[:NR]) + (format_scores(v[NR:]) if scored else [])) + '\n')
+    return tsv
+
+
 def _relaunch_on_gpus(gpu_list, argv):
     """--gpu_list a b c ... outside torch.distributed.run: one rank per listed GPU on 127.0.0.1."""
     import socket
@@ -124,7 +143,7 @@ def _relaunch_on_gpus(gpu_list, argv):
     return subprocess.call(cmd, env=env)
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--pdb_file', nargs='*', default=None, help='antibody-antigen complex(es), <code>_<H>_<L>_<antigen chains>.pdb')
     ap.add_argument('--pdb_list', default=None, help='text file with one complex name per line (a test-set index)')
@@ -162,6 +181,17 @@ def main(argv=None):
     ap.add_argument('--score', action='store_true', help='score every design on the GPU (abx_design_scores): per-CDR RMSD / AAR against the '
                     'input structure, peptide-violation and clash counts as further columns of <complex>_designs.tsv; in trajectory mode also '
                     '<complex>_trajectory_scores.tsv with one line per sample and step')
+    ap.add_argument('--relax', action='store_true', help='relax every design on the GPU (abx_relax): rigid-body + chi minimisation of the '
+                    'violation energy of the designed residues; writes <name>_relaxed.pdb beside each design and <complex>_relax.tsv')
+    ap.add_argument('--relax_iters', type=int, default=200, help='--relax: energy evaluations per design at most')
+    ap.add_argument('--relax_flank', type=int, default=0, help='--relax: linked neighbours on each side of the designed residues that move too')
+    ap.add_argument('--relax_restraint', type=float, default=0.0, help='--relax: weight of the C-alpha restraint to the design (0: none; k > 0 '
+                    'bounds the motion by k * sum |dCA|^2 <= the violation energy of the design)')
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.exact_gemm:
         from abx_amd import ops
@@ -285,6 +315,10 @@ def main(argv=None):
         from .metrics import SCORE_COLUMNS, DesignScorer
         NS = len(SCORE_COLUMNS)
     n_rec = a.num_t if (a.score and a.mode == 'trajectory') else 0
+    NR = 0                                                      # --relax: report columns per sample (+ the scores of the relaxed structure)
+    if a.relax:
+        from .relax import RELAX_COLUMNS, ViolationRelaxer
+        NR = len(RELAX_COLUMNS) + NS
 
     ref_written = set()
     for ji, ids in work:
@@ -331,10 +365,17 @@ def main(argv=None):
             t_feat = time.perf_counter()
             traj = sampler.sample_fn(batch, cfg, diffuser, model, mode=a.mode, num_t=a.num_t,
                                      sample_ids=torch.tensor(ids, device=dev, dtype=torch.int64), on_record=writer.submit, guidance=guide,
-                                     **({'scorer': DesignScorer(batch)} if a.score else {}))
+                                     **({'scorer': DesignScorer(batch)} if a.score else {}),
+                                     **({'relaxer': ViolationRelaxer(batch, flank=a.relax_flank, max_iter=a.relax_iters,
+                                                                     k_restraint=a.relax_restraint)} if a.relax else {}))
             torch.cuda.synchronize()
             t_samp = time.perf_counter()
             new_files = writer.close()
+            if a.relax:                                         # <name>_relaxed.pdb beside every design, through the same writer
+                from .io import postprocess_trajectory
+                last = traj[-1]
+                new_files += postprocess_trajectory(dict(meta, suffix='_relaxed'), [{'seq': last['seq'], 'atom14_results': last['atom14_relaxed'],
+                                                                                     'pLDDT': last['pLDDT'], 'time': 0.0}], out_dir)
             files += new_files
             t_done = time.perf_counter()
             TIMINGS.append(dict(complex=cname, L=int(L), samples=n, mode=a.mode, opt_step=opt_step, read_and_featurise_s=t_feat - t_job,
@@ -347,21 +388,27 @@ def main(argv=None):
                 if n_rec:                                       # (samples, records, 1 + NS): t, then the scores of the record
                     local['traj_scores'] = torch.stack([torch.cat([torch.full((n, 1), r['time'], dtype=torch.float64, device=dev), r['scores']], 1)
                                                         for r in traj], 1)
+            if a.relax:
+                local['relax'] = torch.cat([traj[-1]['relax']] + ([traj[-1]['scores_relaxed']] if a.score else []), 1)
         else:                                                   # more ranks than samples: join the gather with zero-row blocks
             local = {'seq': torch.zeros(0, Lab, dtype=torch.int64, device=dev), 'pLDDT': torch.zeros(0, Lab, device=dev)}
             if a.score:
                 local['scores'] = torch.zeros(0, NS, dtype=torch.float64, device=dev)
                 if n_rec:
                     local['traj_scores'] = torch.zeros(0, n_rec, 1 + NS, dtype=torch.float64, device=dev)
+            if a.relax:
+                local['relax'] = torch.zeros(0, NR, dtype=torch.float64, device=dev)
         if plan is not None:
-            row = torch.zeros(n, 4 + maxLab + NS + n_rec * (1 + NS), dtype=torch.float64)
+            row = torch.zeros(n, 4 + maxLab + NS + n_rec * (1 + NS) + NR, dtype=torch.float64)
             row[:, 0], row[:, 1], row[:, 3] = ji, torch.tensor(ids, dtype=torch.float64), Lab
             row[:, 2] = local['pLDDT'].float().mean(1).double().cpu()       # (the float32 mean of the sample-sharded path: same TSV digits)
             row[:, 4:4 + Lab] = local['seq'].double().cpu()
             if a.score:
                 row[:, 4 + maxLab:4 + maxLab + NS] = local['scores'].cpu()
                 if n_rec:
-                    row[:, 4 + maxLab + NS:] = local['traj_scores'].reshape(n, -1).cpu()
+                    row[:, 4 + maxLab + NS:4 + maxLab + NS + n_rec * (1 + NS)] = local['traj_scores'].reshape(n, -1).cpu()
+            if a.relax:
+                row[:, row.shape[1] - NR:] = local['relax'].cpu()
             set_rows.append(row)
             continue
         if a.debug_one_gpu and world > 1:                       # gloo moves host tensors
@@ -373,9 +420,11 @@ def main(argv=None):
                                                          for i in range(N)]))
             if n_rec:
                 files.append(_write_trajectory_scores(out_dir, cname, res['traj_scores'].cpu()))
+            if a.relax:
+                files.append(_write_relax(out_dir, cname, list(enumerate(res['relax'].tolist())), a.score))
     if plan is not None:
         # ---- the one collective of the set: every rank's rows of the designs table (counts known from the common plan)
-        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, 4 + maxLab + NS + n_rec * (1 + NS), dtype=torch.float64)
+        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, 4 + maxLab + NS + n_rec * (1 + NS) + NR, dtype=torch.float64)
         if not (a.debug_one_gpu and world > 1):
             table = table.to(dev)
         counts = [sum(len(ids_) for _, ids_ in p) for p in plan]
@@ -389,7 +438,10 @@ def main(argv=None):
                                             [(int(r[1]), float(r[2]), r[4:4 + int(r[3])].long().tolist()) +
                                              ((r[4 + maxLab:4 + maxLab + NS].tolist(),) if a.score else ()) for r in rows]))
                 if n_rec:
-                    files.append(_write_trajectory_scores(jobs[ji][2], load_job(ji)['cname'], rows[:, 4 + maxLab + NS:].reshape(N, n_rec, 1 + NS)))
+                    files.append(_write_trajectory_scores(jobs[ji][2], load_job(ji)['cname'],
+                                                          rows[:, 4 + maxLab + NS:4 + maxLab + NS + n_rec * (1 + NS)].reshape(N, n_rec, 1 + NS)))
+                if a.relax:
+                    files.append(_write_relax(jobs[ji][2], load_job(ji)['cname'], [(int(r[1]), r[r.shape[0] - NR:].tolist()) for r in rows], a.score))
     if world > 1 or a.force_collective:
         import torch.distributed as dist
         dist.barrier()

@@ -107,7 +107,8 @@ def _one_record_files(meta, rec, output_dir, multi):
         if meta.get('subdir') is not None:              # inference.py's layout: one directory per sample (<k:04d>/<name>.pdb)
             out_i = os.path.join(output_dir, meta['subdir'][i])
             os.makedirs(out_i, exist_ok=True)
-        path = f'{out_i}/{name}@{time:.4f}.pdb' if time else f'{out_i}/{name}.pdb'
+        stem = name + meta.get('suffix', '')           # (suffix: e.g. '_relaxed', upstream's name for a relaxed design)
+        path = f'{out_i}/{stem}@{time:.4f}.pdb' if time else f'{out_i}/{stem}.pdb'
         save_pdb(index_to_str_seq(seq[:nh]), parts[1], index_to_str_seq(seq[nh:nh + nl]), parts[2],
                  rec['atom14_results'][i, :nh + nl], path, rec['pLDDT'][i], antigen)
         files.append(path)

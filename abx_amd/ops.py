@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1097,3 +1097,85 @@ def design_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, cdr_def, chain_id, 
     ws = torch.empty(max(int(lib.abx_design_scores_workspace_bytes(B, L)), 8), dtype=torch.uint8, device=dev)
     check(lib.abx_design_scores(C.byref(a), _p(ws), _stream()), 'abx_design_scores')
     return out
+
+
+_CHI_TABLES = {}
+
+
+def chi_tables(device):
+    """(chi_axis (21,4,2) int32, rigid_group (21,14) int32) for abx_relax: the atom14 slots of the second and third atom of every chi
+    definition (-1 where the residue type has no such chi) and the rigid group of every atom14 slot (cached per device)."""
+    key = str(device)
+    if key not in _CHI_TABLES:
+        from abx_amd import residue_constants as rc
+        idx37 = torch.as_tensor(rc.chi_angles_atom_indices).long()[:, :, 1:3]                         # (21, 4, 2) atom37 indices
+        a14 = torch.as_tensor(rc.restype_atom37_to_atom14).long()
+        axis = torch.gather(a14[:, None, :].expand(-1, 4, -1), 2, idx37)
+        axis = torch.where(torch.as_tensor(rc.chi_angles_mask)[:, :, None] > 0, axis, torch.full_like(axis, -1))
+        group = torch.as_tensor(rc.restype_atom14_to_rigid_group)
+        _CHI_TABLES[key] = (axis.to(device=device, dtype=torch.int32).contiguous(), group.to(device=device, dtype=torch.int32).contiguous())
+    return _CHI_TABLES[key]
+
+
+def relax(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, movable, Lab=None, residx=None, mask=None, res_mask=None, n_movable=None,
+          overlap_tolerance=1.5, between_chain_factor=0.2, bond_tolerance_factor=12.0, w_clash=1.0, w_bond=1.0, w_angle=1.0,
+          k_restraint=0.0, eta0=0.01, rho=2.0, grow=1.2, shrink=0.5, max_iter=200, return_grad=False):
+    """Violation relaxation of the movable residues of B structures of one complex (abx_relax; report columns:
+    abx_amd.relax.RELAX_COLUMNS).  atom14 (B,Lp,14,3) f32 with Lab <= Lp <= L (rows beyond Lp are the ground truth's and never move; a
+    batch-strided view is read in place), seq (B,>=Lab) int64 tokens; the complex as for design_scores, shared by the batch:
+    gt_atom14 (L,14,3), gt_seq (L), gt_exists (L,14), chain_id (L), residx (L) or None; movable (L) bool / uint8 (rows >= Lp are ignored);
+    mask (B,L,14) or None (None: the atoms of the residue types); res_mask (L) or None.  n_movable: the number of movable rows when
+    the caller knows it (None: counted here, one host synchronisation).
+    -> (atom14_relaxed (B,Lp,14,3) f32, report (B,11) float64[, generalised gradient (B,M,10) f32: g_t, torque, g_chi]).
+    max_iter = 0 evaluates once and returns the input coordinates.  No host synchronisation when n_movable is given."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = chain_id.shape[-1]
+    B, Lp = atom14.shape[0], atom14.shape[1]
+    Lab = int(seq.shape[1] if Lab is None else Lab)
+    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
+    assert tuple(gt_atom14.shape) == (L, 14, 3) and tuple(gt_exists.shape) == (L, 14) and tuple(gt_seq.shape) == (L,) and \
+        tuple(chain_id.shape) == (L,) and tuple(movable.shape) == (L,), 'complex tensors: (L,...) shared by the batch'
+    x = _f32(atom14)
+    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
+        x = x.contiguous()
+    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
+    keep = [x, sq]
+
+    def own(t, dtype):
+        t = t.to(dtype).contiguous()
+        keep.append(t)
+        return _p(t)
+
+    M = int(movable[:Lp].ne(0).sum()) if n_movable is None else int(n_movable)
+    a = AbxRelaxArgs()
+    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
+    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
+    if mask is not None:
+        assert tuple(mask.shape) == (B, L, 14), mask.shape
+        a.pred_mask = own(mask, torch.uint8)
+    if res_mask is not None:
+        assert tuple(res_mask.shape) == (L,), res_mask.shape
+        a.res_mask = own(res_mask, torch.uint8)
+    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
+    a.chain_id, a.movable = own(chain_id, torch.int32), own(movable, torch.uint8)
+    if residx is not None:
+        assert tuple(residx.shape) == (L,), residx.shape
+        a.residx = own(residx, torch.int32)
+    axis, group = chi_tables(dev)
+    a.radius, a.chi_axis, a.rigid_group = _p(vdw_radius_table(dev)), _p(axis), _p(group)
+    a.overlap_tolerance, a.between_chain_factor, a.bond_tolerance_factor = float(overlap_tolerance), float(between_chain_factor), float(bond_tolerance_factor)
+    a.w_clash, a.w_bond, a.w_angle = float(w_clash), float(w_bond), float(w_angle)
+    a.k_restraint, a.eta0, a.rho, a.grow, a.shrink, a.max_iter = float(k_restraint), float(eta0), float(rho), float(grow), float(shrink), int(max_iter)
+    out = torch.empty(B, Lp, 14, 3, device=dev)
+    report = torch.empty(B, _lib.RELAX_COLS, dtype=torch.float64, device=dev)
+    a.out_atom14, a.out_sb = _p(out), Lp * 42
+    a.report, a.report_stride = _p(report), _lib.RELAX_COLS
+    grad = None
+    if return_grad:
+        grad = torch.empty(B, max(M, 1), 10, device=dev)
+        a.gen_grad = _p(grad)
+    a.B, a.L, a.Lab, a.M = B, L, Lab, M
+    ws = torch.empty(max(int(lib.abx_relax_workspace_bytes(B, L, M)), 8), dtype=torch.uint8, device=dev)
+    check(lib.abx_relax(C.byref(a), _p(ws), _stream()), 'abx_relax')
+    return (out, report, grad) if return_grad else (out, report)

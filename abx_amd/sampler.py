@@ -24,7 +24,7 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None):
+              scorer=None, relaxer=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -34,7 +34,10 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     use_graph: record the step into two hipGraphs (abx_amd.graph.GraphedSteps) after one eager step and replay them; needs the
     device noise generator (noise_fn None) and gives the same results as the eager loop.
     scorer: None, or an abx_amd.metrics.DesignScorer of the complex: every record gets 'scores' (B, len(metrics.SCORE_COLUMNS)) float64,
-    rows of one table allocated before the loop; one launch pair per record, outside any captured step, no host synchronisation."""
+    rows of one table allocated before the loop; one launch pair per record, outside any captured step, no host synchronisation.
+    relaxer: None, or an abx_amd.relax.ViolationRelaxer of the complex: the LAST record (the designs; the earlier records of trajectory
+    mode are noisy states) gets 'atom14_relaxed' (B,Lab,14,3) and 'relax' (B, len(relax.RELAX_COLUMNS)) float64, and with a scorer
+    'scores_relaxed'; 'atom14_results' is left as it is.  One launch, outside any captured step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -99,6 +102,10 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 traj.append({kk: (v.clone() if torch.is_tensor(v) else v) for kk, v in rec.items()})
                 if scorer is not None:
                     traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
+                if relaxer is not None and k == len(steps) - 1:
+                    traj[-1]['atom14_relaxed'], traj[-1]['relax'] = relaxer.relax(traj[-1]['atom14_results'], traj[-1]['seq'])
+                    if scorer is not None:
+                        traj[-1]['scores_relaxed'] = scorer.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'])
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)

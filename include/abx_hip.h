@@ -567,6 +567,60 @@ long long abx_design_scores_workspace_bytes(int B, int L);
 int abx_design_scores(const AbxDesignScoreArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Violation relaxation of designed residues (the "relax" step between design and evaluation; upstream runs PyRosetta FastRelax,
+ * relax_pdb.py / abx/relax.py, which this project does not use): steepest descent with an adaptive step on
+ *   E = E_viol|M + k_restraint * sum_{r in M} |CA_r - CA_r(input)|^2
+ * in the space of rigid-body motions of every movable residue (translation t, rotation about its C-alpha as a unit quaternion) plus
+ * its side-chain chi angles.  E_viol|M is the energy of abx_clash_grad (the same fp32 expressions, pair rules and link rule)
+ * restricted to the terms that touch a movable residue: atom pairs with at least one atom in M (pairs inside M once) and the
+ * peptide terms of (l, l+1) when l or l+1 is in M.  Bond lengths and angles inside a residue never change; fixed rows never move.
+ * Atoms are rebuilt from the INPUT coordinates at every evaluation: local = x_in - CA_in; chi_k (k = 1..4, where chi_axis has one and
+ * both axis atoms exist) rotates the slots with rigid_group >= 3 + k about the axis through the two axis atoms; x = R local + CA_in + t.
+ * Generalised gradient of a residue from the atom gradients g_a: g_t = sum g_a (+ the restraint), tau = sum (x_a - CA) x g_a,
+ * g_chi_k = axis_k . sum_{a downstream of k} (x_a - p_k) x g_a.  Trial: t -= eta g_t, R <- exp(-eta tau / rho^2) R,
+ * chi_k -= eta g_chi_k / rho^2; accepted when E_trial < E (eta *= grow) else dropped (eta *= shrink); ends after max_iter energy
+ * evaluations or when E == 0.  E (fp64 sums of fp32 terms) never increases.  A structure without an accepted step is returned as
+ * a copy of its input; rows outside M are always copies.
+ * The structure and the complex are given as for abx_design_scores (pred_* rows < Lpred, ground truth beyond; pred_mask / res_mask /
+ * residx optional; the complex is shared by the B structures).  movable: (L) bytes, shared by the batch; the first M set rows below
+ * Lpred are the movable set (M: their number, counted by the caller once per complex).  chi_axis: [21][4][2] atom14 slots of the
+ * second and third atom of every chi definition (-1: the residue type has no such chi); rigid_group: [21][14] rigid group of every
+ * atom14 slot (4..7: moved by chi1..chi4).
+ * out_atom14 (B, Lpred, 14, 3) with the batch stride out_sb (floats); report: ABX_RELAX_COLS doubles per structure (row stride
+ * report_stride): E_clash, E_bond, E_angle of the input; E_clash, E_bond, E_angle, E_restraint of the output; evaluations used,
+ * accepted steps, final eta, largest C-alpha displacement (abx_amd.relax.RELAX_COLUMNS).
+ * max_iter = 0: one evaluation, out_atom14 = the input, and gen_grad (B, M, 10: g_t, tau, g_chi), when given, receives the generalised
+ * gradient of the input state (with max_iter > 0 it receives that of the returned state).
+ * One launch, one workgroup per structure, the structure's atom table resident in LDS: 232 L + 340 M + 1024 bytes must fit 160 KB
+ * (L = 352 with up to 238 movable residues), a larger problem is an argument error.  Every sum has a fixed order: a structure's
+ * result does not depend on its batch mates.  No allocation, no synchronisation; the workspace (abx_relax_workspace_bytes) is reserved
+ * for a global-memory atom table and may be empty today. */
+#define ABX_RELAX_COLS 11
+typedef struct AbxRelaxArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const int* chain_id;
+    const int* residx;                              /* optional residue numbers (L) */
+    const unsigned char* movable;                   /* (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs */
+    const int* chi_axis; const int* rigid_group;    /* [21][4][2], [21][14] */
+    float overlap_tolerance, between_chain_factor, bond_tolerance_factor, w_clash, w_bond, w_angle;
+    float k_restraint, eta0, rho, grow, shrink;
+    int max_iter;
+    float* out_atom14; long long out_sb;
+    double* report; long long report_stride;
+    float* gen_grad;                                /* optional (B,M,10) */
+    int B, L, Lab, M;
+} AbxRelaxArgs;
+long long abx_relax_workspace_bytes(int B, int L, int M);
+/* LDS bytes a structure of L rows with M movable ones needs (<= 163840 to be accepted) */
+long long abx_relax_lds_bytes(int L, int M);
+int abx_relax(const AbxRelaxArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
