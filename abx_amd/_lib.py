@@ -224,6 +224,25 @@ class AbxRelaxArgs(C.Structure):
     ]
 
 
+IFACE_COLS = 12           # ABX_IFACE_COLS
+
+
+class AbxInterfaceArgs(C.Structure):
+    _fields_ = [
+        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
+        ('pred_seq', c_f), ('pred_seq_sb', LL),
+        ('pred_mask', c_f), ('res_mask', c_f),
+        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+        ('region', c_f),
+        ('radius', c_f),
+        ('sphere', c_f), ('P', I),
+        ('probe', C.c_double), ('cutoff', C.c_double),
+        ('out', c_f), ('out_stride', LL),
+        ('points', c_f),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -280,6 +299,8 @@ _PROTOS = {
     'abx_relax_workspace_bytes': (LL, [I, I, I]),
     'abx_relax_lds_bytes': (LL, [I, I]),
     'abx_relax': (I, [C.POINTER(AbxRelaxArgs), c_f, _S]),
+    'abx_interface_scores_workspace_bytes': (LL, [I, I, I]),
+    'abx_interface_scores': (I, [C.POINTER(AbxInterfaceArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

@@ -424,7 +424,11 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
                     *reinterpret_cast<u32x2*>(cs + 48) = u32x2{a1, b1};
                 }
             } else if (!EDGE || m < g.M) {
+                // TWO instructions, as the plane columns issue and AsSched counts: left to itself the compiler merges the halves into one
+                // 16-byte store, the counted wait of the streaming wave then lets the last two DMA chunks of the next weight stage (its
+                // columns 64 - 127: the first plane columns of the q | k | v projection) stay in flight past the rendezvous
                 *reinterpret_cast<f32x2*>(cr + n) = (f32x2){o[0], o[1]};
+                asm volatile("" ::: "memory");
                 *reinterpret_cast<f32x2*>(cr + n + 2) = (f32x2){o[2], o[3]};
             }
         } else

@@ -35,6 +35,12 @@ violation energy of the designed residues (+ --relax_flank linked neighbours on 
 angles of those residues; <name>_relaxed.pdb is written beside every design (upstream's naming, which its eval_metric.py skips) and
 <output_dir>/<complex>_relax.tsv holds one line per sample: relax.RELAX_COLUMNS and, with --score, the scores of the relaxed structure.
 The design files and <complex>_designs.tsv are what they are without --relax.
+--interface: every design gets its interface row on the GPU after the last step (abx_amd.interface.InterfaceScorer, abx_interface_scores):
+solvent-accessible surface buried between the antibody and the featurised antigen (a cropped patch when the complex was cropped),
+interface residues and heavy-atom contacts, with the designed residues as the region.  <output_dir>/<complex>_interface.tsv holds a
+`wild` line (the input complex itself) and one line per sample: interface.INTERFACE_COLUMNS, then delta_<column> = design minus wild
+type for interface.DELTA_COLUMNS (the geometric analogue of upstream's ddG) and, with --relax, the columns of the relaxed structure
+suffixed _relaxed (nan on the wild line).  No other output file changes.
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -129,6 +135,22 @@ def _write_relax(out_dir, cname, rows, scored):
     return tsv
 
 
+def _write_interface(out_dir, cname, wild, rows, relaxed):
+    """<out_dir>/<complex>_interface.tsv: the `wild` line, then (sample id, values) per sample; values = the interface.INTERFACE_COLUMNS row
+    and, when relaxed, the row of the relaxed structure.  After the columns: delta_<column> = row minus wild for interface.DELTA_COLUMNS."""
+    from .interface import DELTA_COLUMNS, INTERFACE_COLUMNS, format_delta, format_interface
+    NI = len(INTERFACE_COLUMNS)
+    tsv = os.path.join(out_dir, f'{cname}_interface.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(INTERFACE_COLUMNS + tuple('delta_' + c for c in DELTA_COLUMNS) +
+                                       (tuple(c + '_relaxed' for c in INTERFACE_COLUMNS) if relaxed else ())) + '\n')
+        f.write('wild\t' + '\t'.join(format_interface(wild) + format_delta(wild, wild) + (['nan'] * NI if relaxed else [])) + '\n')
+        for i, v in rows:
+            f.write(f'{i}\t' + '\t'.join(format_interface(v[:NI]) + format_delta(v[:NI], wild) +
+                                          (format_interface(v[NI:2 * NI]) if relaxed else [])) + '\n')
+    return tsv
+
+
 def _relaunch_on_gpus(gpu_list, argv):
     """--gpu_list a b c ... outside torch.distributed.run: one rank per listed GPU on 127.0.0.1."""
     import socket
@@ -187,6 +209,12 @@ def build_parser():
     ap.add_argument('--relax_flank', type=int, default=0, help='--relax: linked neighbours on each side of the designed residues that move too')
     ap.add_argument('--relax_restraint', type=float, default=0.0, help='--relax: weight of the C-alpha restraint to the design (0: none; k > 0 '
                     'bounds the motion by k * sum |dCA|^2 <= the violation energy of the design)')
+    ap.add_argument('--interface', action='store_true', help='interface row of every design on the GPU (abx_interface_scores): buried '
+                    'solvent-accessible surface, interface residues and antibody-antigen contacts, and their difference to the input complex; '
+                    'writes <complex>_interface.tsv')
+    ap.add_argument('--interface_points', type=int, default=128, help='--interface: sphere points per atom (1..1024)')
+    ap.add_argument('--interface_probe', type=float, default=1.4, help='--interface: probe radius (Angstrom)')
+    ap.add_argument('--interface_cutoff', type=float, default=4.0, help='--interface: heavy-atom contact distance (Angstrom)')
     return ap
 
 
@@ -319,6 +347,12 @@ def main(argv=None):
     if a.relax:
         from .relax import RELAX_COLUMNS, ViolationRelaxer
         NR = len(RELAX_COLUMNS) + NS
+    NI = 0                                                      # --interface: the row (+ that of the relaxed structure) + the wild type's row
+    if a.interface:
+        from .interface import INTERFACE_COLUMNS, InterfaceScorer
+        if not 1 <= a.interface_points <= 1024 or a.interface_probe < 0 or a.interface_cutoff <= 0:
+            raise SystemExit('--interface_points must be in 1..1024, --interface_probe >= 0, --interface_cutoff > 0')
+        NI = len(INTERFACE_COLUMNS) * (3 if a.relax else 2)
 
     ref_written = set()
     for ji, ids in work:
@@ -361,13 +395,15 @@ def main(argv=None):
             batch['_shared_context'] = True
             diffuser.seed = a.seed
             writer = TrajectoryWriter(meta, out_dir, multi=a.mode == 'trajectory')
+            iface = InterfaceScorer(batch, n_points=a.interface_points, probe=a.interface_probe, cutoff=a.interface_cutoff) if a.interface else None
             torch.cuda.synchronize()
             t_feat = time.perf_counter()
             traj = sampler.sample_fn(batch, cfg, diffuser, model, mode=a.mode, num_t=a.num_t,
                                      sample_ids=torch.tensor(ids, device=dev, dtype=torch.int64), on_record=writer.submit, guidance=guide,
                                      **({'scorer': DesignScorer(batch)} if a.score else {}),
                                      **({'relaxer': ViolationRelaxer(batch, flank=a.relax_flank, max_iter=a.relax_iters,
-                                                                     k_restraint=a.relax_restraint)} if a.relax else {}))
+                                                                     k_restraint=a.relax_restraint)} if a.relax else {}),
+                                     **({'interface': iface} if a.interface else {}))
             torch.cuda.synchronize()
             t_samp = time.perf_counter()
             new_files = writer.close()
@@ -390,6 +426,9 @@ def main(argv=None):
                                                         for r in traj], 1)
             if a.relax:
                 local['relax'] = torch.cat([traj[-1]['relax']] + ([traj[-1]['scores_relaxed']] if a.score else []), 1)
+            if a.interface:                                     # the wild type's row rides along in every row: any rank can write the table
+                local['interface'] = torch.cat([traj[-1]['interface']] + ([traj[-1]['interface_relaxed']] if a.relax else []) +
+                                               [iface.wild().expand(n, -1)], 1)
         else:                                                   # more ranks than samples: join the gather with zero-row blocks
             local = {'seq': torch.zeros(0, Lab, dtype=torch.int64, device=dev), 'pLDDT': torch.zeros(0, Lab, device=dev)}
             if a.score:
@@ -398,8 +437,10 @@ def main(argv=None):
                     local['traj_scores'] = torch.zeros(0, n_rec, 1 + NS, dtype=torch.float64, device=dev)
             if a.relax:
                 local['relax'] = torch.zeros(0, NR, dtype=torch.float64, device=dev)
+            if a.interface:
+                local['interface'] = torch.zeros(0, NI, dtype=torch.float64, device=dev)
         if plan is not None:
-            row = torch.zeros(n, 4 + maxLab + NS + n_rec * (1 + NS) + NR, dtype=torch.float64)
+            row = torch.zeros(n, 4 + maxLab + NS + n_rec * (1 + NS) + NR + NI, dtype=torch.float64)
             row[:, 0], row[:, 1], row[:, 3] = ji, torch.tensor(ids, dtype=torch.float64), Lab
             row[:, 2] = local['pLDDT'].float().mean(1).double().cpu()       # (the float32 mean of the sample-sharded path: same TSV digits)
             row[:, 4:4 + Lab] = local['seq'].double().cpu()
@@ -408,7 +449,9 @@ def main(argv=None):
                 if n_rec:
                     row[:, 4 + maxLab + NS:4 + maxLab + NS + n_rec * (1 + NS)] = local['traj_scores'].reshape(n, -1).cpu()
             if a.relax:
-                row[:, row.shape[1] - NR:] = local['relax'].cpu()
+                row[:, row.shape[1] - NI - NR:row.shape[1] - NI] = local['relax'].cpu()
+            if a.interface:
+                row[:, row.shape[1] - NI:] = local['interface'].cpu()
             set_rows.append(row)
             continue
         if a.debug_one_gpu and world > 1:                       # gloo moves host tensors
@@ -422,9 +465,12 @@ def main(argv=None):
                 files.append(_write_trajectory_scores(out_dir, cname, res['traj_scores'].cpu()))
             if a.relax:
                 files.append(_write_relax(out_dir, cname, list(enumerate(res['relax'].tolist())), a.score))
+            if a.interface:
+                it = res['interface'].tolist()
+                files.append(_write_interface(out_dir, cname, it[0][NI - len(INTERFACE_COLUMNS):], list(enumerate(it)), a.relax))
     if plan is not None:
         # ---- the one collective of the set: every rank's rows of the designs table (counts known from the common plan)
-        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, 4 + maxLab + NS + n_rec * (1 + NS) + NR, dtype=torch.float64)
+        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, 4 + maxLab + NS + n_rec * (1 + NS) + NR + NI, dtype=torch.float64)
         if not (a.debug_one_gpu and world > 1):
             table = table.to(dev)
         counts = [sum(len(ids_) for _, ids_ in p) for p in plan]
@@ -441,7 +487,10 @@ def main(argv=None):
                     files.append(_write_trajectory_scores(jobs[ji][2], load_job(ji)['cname'],
                                                           rows[:, 4 + maxLab + NS:4 + maxLab + NS + n_rec * (1 + NS)].reshape(N, n_rec, 1 + NS)))
                 if a.relax:
-                    files.append(_write_relax(jobs[ji][2], load_job(ji)['cname'], [(int(r[1]), r[r.shape[0] - NR:].tolist()) for r in rows], a.score))
+                    files.append(_write_relax(jobs[ji][2], load_job(ji)['cname'], [(int(r[1]), r[r.shape[0] - NI - NR:r.shape[0] - NI].tolist()) for r in rows], a.score))
+                if a.interface:
+                    files.append(_write_interface(jobs[ji][2], load_job(ji)['cname'], rows[0, rows.shape[1] - len(INTERFACE_COLUMNS):].tolist(),
+                                                  [(int(r[1]), r[r.shape[0] - NI:].tolist()) for r in rows], a.relax))
     if world > 1 or a.force_collective:
         import torch.distributed as dist
         dist.barrier()

@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1179,3 +1179,63 @@ def relax(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, movable, Lab=None
     ws = torch.empty(max(int(lib.abx_relax_workspace_bytes(B, L, M)), 8), dtype=torch.uint8, device=dev)
     check(lib.abx_relax(C.byref(a), _p(ws), _stream()), 'abx_relax')
     return (out, report, grad) if return_grad else (out, report)
+
+
+def interface_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, Lab=None, region=None, mask=None, res_mask=None, probe=1.4,
+                     cutoff=4.0, out=None, points=None):
+    """Interface analysis of B structures of one complex (abx_interface_scores; columns: abx_amd.interface.INTERFACE_COLUMNS): buried
+    Shrake-Rupley surface, interface residues and antibody-antigen contacts between the rows < Lab and the rows >= Lab.
+    atom14 (B,Lp,14,3) f32 with Lab <= Lp <= L (rows beyond Lp take the ground-truth coordinates; a batch-strided view is read in
+    place), seq (B,>=Lab) int64 tokens; the complex, shared by the batch: gt_atom14 (L,14,3), gt_seq (L), gt_exists (L,14);
+    sphere (P,3) float64 unit vectors on the device (abx_amd.interface.sphere_points); region (L) bool / uint8 or None;
+    mask (B,L,14) or None (None: the atoms of the residue types); res_mask (L) or None.
+    out: (B, 12) float64 with unit column stride and any row stride, or None; points: (B,L,14,2) int32 contiguous to receive
+    acc_alone / acc_cplx of every slot, or None.  Three launches, no synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = gt_seq.shape[-1]
+    B, Lp = atom14.shape[0], atom14.shape[1]
+    Lab = int(seq.shape[1] if Lab is None else Lab)
+    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
+    assert tuple(gt_atom14.shape) == (L, 14, 3) and tuple(gt_exists.shape) == (L, 14) and tuple(gt_seq.shape) == (L,), \
+        'complex tensors: (L,...) shared by the batch'
+    assert sphere.dtype == torch.float64 and sphere.dim() == 2 and sphere.shape[1] == 3 and sphere.is_contiguous() and sphere.device == dev, \
+        'sphere: (P,3) float64 on the device of atom14'
+    x = _f32(atom14)
+    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
+        x = x.contiguous()
+    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
+    keep = [x, sq]
+
+    def own(t, dtype):
+        t = t.to(dtype).contiguous()
+        keep.append(t)
+        return _p(t)
+
+    a = AbxInterfaceArgs()
+    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
+    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
+    if mask is not None:
+        assert tuple(mask.shape) == (B, L, 14), mask.shape
+        a.pred_mask = own(mask, torch.uint8)
+    if res_mask is not None:
+        assert tuple(res_mask.shape) == (L,), res_mask.shape
+        a.res_mask = own(res_mask, torch.uint8)
+    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
+    if region is not None:
+        assert tuple(region.shape) == (L,), region.shape
+        a.region = own(region.ne(0), torch.uint8)
+    a.radius = _p(vdw_radius_table(dev))
+    a.sphere, a.P = _p(sphere), int(sphere.shape[0])
+    a.probe, a.cutoff = float(probe), float(cutoff)
+    if out is None:
+        out = torch.empty(B, _lib.IFACE_COLS, dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (B, _lib.IFACE_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (B, 12) float64 rows'
+    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else _lib.IFACE_COLS
+    if points is not None:
+        assert points.dtype == torch.int32 and tuple(points.shape) == (B, L, 14, 2) and points.is_contiguous() and points.is_cuda, 'points: (B,L,14,2) int32'
+        a.points = _p(points)
+    a.B, a.L, a.Lab = B, L, Lab
+    ws = torch.empty(max(int(lib.abx_interface_scores_workspace_bytes(B, L, a.P)), 16), dtype=torch.uint8, device=dev)
+    check(lib.abx_interface_scores(C.byref(a), _p(ws), _stream()), 'abx_interface_scores')
+    return out

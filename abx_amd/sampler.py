@@ -24,7 +24,7 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None, relaxer=None):
+              scorer=None, relaxer=None, interface=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -37,7 +37,10 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     rows of one table allocated before the loop; one launch pair per record, outside any captured step, no host synchronisation.
     relaxer: None, or an abx_amd.relax.ViolationRelaxer of the complex: the LAST record (the designs; the earlier records of trajectory
     mode are noisy states) gets 'atom14_relaxed' (B,Lab,14,3) and 'relax' (B, len(relax.RELAX_COLUMNS)) float64, and with a scorer
-    'scores_relaxed'; 'atom14_results' is left as it is.  One launch, outside any captured step, no host synchronisation."""
+    'scores_relaxed'; 'atom14_results' is left as it is.  One launch, outside any captured step, no host synchronisation.
+    interface: None, or an abx_amd.interface.InterfaceScorer of the complex: the LAST record gets 'interface' (B, len(interface.
+    INTERFACE_COLUMNS)) float64 - buried surface, interface residues, antibody-antigen contacts of the designs - and with a relaxer
+    'interface_relaxed' of the relaxed structures.  Three launches each, outside any captured step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -106,6 +109,10 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                     traj[-1]['atom14_relaxed'], traj[-1]['relax'] = relaxer.relax(traj[-1]['atom14_results'], traj[-1]['seq'])
                     if scorer is not None:
                         traj[-1]['scores_relaxed'] = scorer.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'])
+                if interface is not None and k == len(steps) - 1:
+                    traj[-1]['interface'] = interface.score(traj[-1]['atom14_results'], traj[-1]['seq'])
+                    if relaxer is not None:
+                        traj[-1]['interface_relaxed'] = interface.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'])
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)

@@ -621,6 +621,55 @@ long long abx_relax_lds_bytes(int L, int M);
 int abx_relax(const AbxRelaxArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Interface analysis of designs: the geometric half of what upstream takes from PyRosetta's InterfaceAnalyzerMover for every written
+ * PDB and for the wild type (abx/metric.py:28-59, eval/traj_evaluate.py:242-261, the _energy.csv tables of eval/metric_scripts): buried
+ * solvent-accessible surface (dSASA_int), interface residues (nres_int) and antibody-antigen contacts.  No energies (dG / ddG need a
+ * force field, which this project does not have), no hydrogens.  One row of ABX_IFACE_COLS float64 values per structure of a batch
+ * of B designs of ONE complex (abx_amd.interface.INTERFACE_COLUMNS).
+ * Side A: the rows < Lab (antibody); side B: the rows >= Lab (the FEATURISED antigen: a cropped patch when the complex was cropped).
+ * Atoms: the existing atom14 slots whose radius in `radius` is positive; inflated radius R_a = (double)r_a + probe.
+ * Shrake-Rupley surface on the P unit vectors of `sphere` ((P,3) float64, 1 <= P <= 1024, built by the caller: the golden spiral
+ * z = 1 - (2k+1)/P, r = sqrt(1 - z^2), phi = k pi (3 - sqrt 5); the kernel evaluates no trigonometry).  Point p of atom a is occluded
+ * by atom b != a iff |c_a + R_a u_p - c_b|^2 < R_b^2, in float64 from the float32 coordinates, without fused multiply-add, in this order:
+ *   px = (double)x_a + R_a * ux;  dx = px - (double)x_b;  d2 = (dx*dx + dy*dy) + dz*dz;  d2 < R_b * R_b
+ * so the point counts are exact integers that a host evaluation of the same IEEE operations reproduces (abx_amd.interface.
+ * interface_host).  Per atom: acc_alone = points occluded by no atom of its own side, acc_cplx = those of them occluded by no atom of
+ * the other side either: one pass gives the complex and both separated partners.  Area of a count: 4 pi R_a^2 count / P.
+ *   0 sasa_complex        sum area(acc_cplx), all atoms          6 n_res_int_antibody  side-A residues with an atom acc_alone > acc_cplx
+ *   1 sasa_antibody       sum area(acc_alone), side A            7 n_res_int_antigen   the same, side B
+ *   2 sasa_antigen        sum area(acc_alone), side B            8 n_res_int_region    the same, rows with region != 0
+ *   3 dsasa_int           sum area(acc_alone - acc_cplx), all    9 n_contact           cross-side atom pairs with d^2 < cutoff^2 (float64,
+ *   4 dsasa_antibody      the side-A part of 3                                         dx = (double)x_a - (double)x_b, the same order)
+ *   5 dsasa_region        the part of 3 of rows with region != 0 10 n_contact_region   those of 9 whose side-A atom is in a region row
+ *                                                                11 n_atoms            atoms counted
+ * The structure and the complex are given as for abx_design_scores (pred_* rows < Lpred, ground truth beyond, residue types of rows
+ * < Lab from pred_seq; pred_mask / res_mask optional: res_mask = 0 removes a row from both sides; the complex is shared by the B
+ * structures).  No link rule enters: chain ids and residue numbers are not read.  region: (L) bytes shared by the batch, optional
+ * (NULL: columns 5, 8 and 10 are 0).  out / out_stride as in AbxDesignScoreArgs (out_stride >= ABX_IFACE_COLS).
+ * points: optional (B, L, 14, 2) int32, acc_alone and acc_cplx of every slot (0 for absent slots).
+ * Three launches - the compacted atom table of every structure; the point counts, one wave per atom with the structure's table in
+ * LDS (20 bytes per atom14 slot + 12 KB must fit 160 KB: L <= 541, a larger problem is an argument error); the fixed-order
+ * reduction to the row - no atomics, no allocation, no synchronisation: a structure's row depends on nothing but its own inputs.
+ * The caller allocates the workspace (abx_interface_scores_workspace_bytes). */
+#define ABX_IFACE_COLS 12
+typedef struct AbxInterfaceArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const unsigned char* region;                    /* optional (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs */
+    const double* sphere; int P;                    /* (P,3) unit vectors */
+    double probe, cutoff;                           /* probe radius (1.4), contact distance (4.0), Angstrom */
+    double* out; long long out_stride;
+    int* points;                                    /* optional (B,L,14,2) */
+    int B, L, Lab;
+} AbxInterfaceArgs;
+long long abx_interface_scores_workspace_bytes(int B, int L, int P);
+int abx_interface_scores(const AbxInterfaceArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
