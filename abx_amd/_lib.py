@@ -243,6 +243,33 @@ class AbxInterfaceArgs(C.Structure):
     ]
 
 
+ENS_COLS = 10             # ABX_ENS_COLS
+ENS_MAX_POINTS = 512      # ABX_ENS_MAX_POINTS
+ENS_MAX_N = 1024          # ABX_ENS_MAX_N
+
+
+class AbxEnsemblePairsArgs(C.Structure):
+    _fields_ = [
+        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
+        ('pred_seq', c_f), ('pred_seq_sb', LL),
+        ('region', c_f),
+        ('atoms', I), ('M', I),
+        ('planes', c_f), ('plane_stride', LL),
+        ('N', I),
+    ]
+
+
+class AbxEnsembleClusterArgs(C.Structure):
+    _fields_ = [
+        ('planes', c_f), ('plane_stride', LL),
+        ('metric', I),
+        ('cutoff', C.c_double),
+        ('out', c_f), ('out_stride', LL),
+        ('centres', c_f), ('n_clusters', c_f),
+        ('N', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -301,6 +328,9 @@ _PROTOS = {
     'abx_relax': (I, [C.POINTER(AbxRelaxArgs), c_f, _S]),
     'abx_interface_scores_workspace_bytes': (LL, [I, I, I]),
     'abx_interface_scores': (I, [C.POINTER(AbxInterfaceArgs), c_f, _S]),
+    'abx_ensemble_pairs_workspace_bytes': (LL, [I, I]),
+    'abx_ensemble_pairs': (I, [C.POINTER(AbxEnsemblePairsArgs), c_f, _S]),
+    'abx_ensemble_cluster': (I, [C.POINTER(AbxEnsembleClusterArgs), _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

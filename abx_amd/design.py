@@ -41,6 +41,12 @@ interface residues and heavy-atom contacts, with the designed residues as the re
 `wild` line (the input complex itself) and one line per sample: interface.INTERFACE_COLUMNS, then delta_<column> = design minus wild
 type for interface.DELTA_COLUMNS (the geometric analogue of upstream's ddG) and, with --relax, the columns of the relaxed structure
 suffixed _relaxed (nan on the wild line).  No other output file changes.
+--ensemble: the N designs of a complex are compared with each other on the GPU (abx_amd.ensemble.EnsembleAnalyzer, abx_ensemble_pairs +
+abx_ensemble_cluster) by the rank that writes the tables, after the gather: the backbone of the designed antibody travels with the other
+fields.  <output_dir>/<complex>_ensemble.tsv holds an `all` line (clusters, unique sequences, mean pairwise RMSD and sequence identity)
+and one line per sample: ensemble.ENSEMBLE_COLUMNS and `representative`, the sample id of the centre of the sample's cluster - the few
+files worth the expensive evaluation.  --ensemble_matrix also writes <complex>_ensemble_rmsd.npy, the (3, N, N) planes rmsd_fit,
+rmsd_frame, seq_diff.  With --relax the analysis still describes the designs as written.  No other output file changes.
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -151,6 +157,23 @@ def _write_interface(out_dir, cname, wild, rows, relaxed):
     return tsv
 
 
+def _write_ensemble(out_dir, cname, summ, rows, centres):
+    """<out_dir>/<complex>_ensemble.tsv: the `all` line, then (sample id, ensemble.ENSEMBLE_COLUMNS values) per sample in row order.
+    summ: ensemble.summary of the table; centres: the rows' positions of the cluster centres in order of discovery.  Columns: the row,
+    `representative` (sample id of the centre of the row's cluster), then the summary's own columns prefixed all_ (nan on sample
+    lines); the three means of the summary stand in their ENSEMBLE_COLUMNS on the `all` line."""
+    from .ensemble import ENSEMBLE_COLUMNS, format_ensemble, format_summary
+    own = [c for c in summ if c not in ENSEMBLE_COLUMNS]
+    fs = dict(zip(summ, format_summary(summ)))
+    tsv = os.path.join(out_dir, f'{cname}_ensemble.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(ENSEMBLE_COLUMNS + ('representative',) + tuple('all_' + c for c in own)) + '\n')
+        f.write('all\t' + '\t'.join([fs.get(c, 'nan') for c in ENSEMBLE_COLUMNS] + ['nan'] + [fs[c] for c in own]) + '\n')
+        for i, v in rows:
+            f.write(f'{i}\t' + '\t'.join(format_ensemble(v) + [str(rows[centres[int(v[0])]][0])] + ['nan'] * len(own)) + '\n')
+    return tsv
+
+
 def _relaunch_on_gpus(gpu_list, argv):
     """--gpu_list a b c ... outside torch.distributed.run: one rank per listed GPU on 127.0.0.1."""
     import socket
@@ -215,6 +238,14 @@ def build_parser():
     ap.add_argument('--interface_points', type=int, default=128, help='--interface: sphere points per atom (1..1024)')
     ap.add_argument('--interface_probe', type=float, default=1.4, help='--interface: probe radius (Angstrom)')
     ap.add_argument('--interface_cutoff', type=float, default=4.0, help='--interface: heavy-atom contact distance (Angstrom)')
+    ap.add_argument('--ensemble', action='store_true', help='compare the designs of a complex with each other on the GPU (abx_ensemble_pairs, '
+                    'abx_ensemble_cluster): pairwise RMSD of the designed residues, Daura clusters and their centres; writes <complex>_ensemble.tsv')
+    ap.add_argument('--ensemble_cutoff', type=float, default=1.0, help='--ensemble: neighbour distance of the clusters (Angstrom)')
+    ap.add_argument('--ensemble_metric', default='fit', choices=['fit', 'frame'], help='--ensemble: cluster on the RMSD after superposition '
+                    '(fit: shape) or in the frame of the complex (frame: placement)')
+    ap.add_argument('--ensemble_atoms', default='backbone', choices=['ca', 'backbone'], help='--ensemble: compared atoms of the designed residues')
+    ap.add_argument('--ensemble_matrix', action='store_true', help='--ensemble: also write <complex>_ensemble_rmsd.npy, the (3, N, N) planes '
+                    'rmsd_fit, rmsd_frame, seq_diff')
     return ap
 
 
@@ -353,6 +384,36 @@ def main(argv=None):
         if not 1 <= a.interface_points <= 1024 or a.interface_probe < 0 or a.interface_cutoff <= 0:
             raise SystemExit('--interface_points must be in 1..1024, --interface_probe >= 0, --interface_cutoff > 0')
         NI = len(INTERFACE_COLUMNS) * (3 if a.relax else 2)
+    NE = 0                                                      # --ensemble, set-level rows: the antibody backbone (maxLab, 4, 3), f32 values
+    analyzers = {}                                              # --ensemble: job -> EnsembleAnalyzer (the compared rows of the complex)
+    if a.ensemble:
+        from . import ensemble
+        if not 1 <= N <= ensemble.MAX_N or not a.ensemble_cutoff >= 0:
+            raise SystemExit(f'--ensemble compares 1..{ensemble.MAX_N} samples of a complex, --ensemble_cutoff must be >= 0')
+        NE = 12 * maxLab
+    E0 = 4 + maxLab + NS + n_rec * (1 + NS)                     # set-level rows: the backbone columns follow the scores
+    WIDTH = E0 + NE + NR + NI
+
+    def analyze_ensemble(ji, out_dir, cname, ids, seq, backbone):
+        """The ensemble tables of job ji from the gathered tokens (N, Lab) and backbone (N, Lab, 4, 3) in the order of `ids`."""
+        import numpy as np
+        if ji not in analyzers:                                 # a complex this rank did not sample: its features give the compared rows
+            J = load_job(ji)
+            raw = {k: v.to(dev) for k, v in J['one'].items()}
+            fb = features.build_features(raw, diffuser, generate_area=a.generate_area, opt_step=jobs[ji][3] if a.mode == 'optimize' else None,
+                                         noise=features.per_sample_init_noise([0], J['L'], a.seed, dev))
+            analyzers[ji] = ensemble.EnsembleAnalyzer(fb, atoms=a.ensemble_atoms, metric=a.ensemble_metric, cutoff=a.ensemble_cutoff)
+        an = analyzers[ji]
+        x = torch.zeros(seq.shape[0], an.Lab, 14, 3, dtype=torch.float32, device=dev)
+        x[:, :, :4] = backbone.to(dev)
+        res = an.analyze(x, seq.to(dev).long())
+        table = res['table'].cpu().numpy()
+        centres = res['centres'].cpu().tolist()[:int(res['n_clusters'])]
+        out = [_write_ensemble(out_dir, cname, ensemble.summary(table, an.n_region), list(zip(ids, table.tolist())), centres)]
+        if a.ensemble_matrix:
+            out.append(os.path.join(out_dir, f'{cname}_ensemble_rmsd.npy'))
+            np.save(out[-1], res['planes'].cpu().numpy())
+        return out
 
     ref_written = set()
     for ji, ids in work:
@@ -396,6 +457,8 @@ def main(argv=None):
             diffuser.seed = a.seed
             writer = TrajectoryWriter(meta, out_dir, multi=a.mode == 'trajectory')
             iface = InterfaceScorer(batch, n_points=a.interface_points, probe=a.interface_probe, cutoff=a.interface_cutoff) if a.interface else None
+            if a.ensemble and ji not in analyzers:
+                analyzers[ji] = ensemble.EnsembleAnalyzer(batch, atoms=a.ensemble_atoms, metric=a.ensemble_metric, cutoff=a.ensemble_cutoff)
             torch.cuda.synchronize()
             t_feat = time.perf_counter()
             traj = sampler.sample_fn(batch, cfg, diffuser, model, mode=a.mode, num_t=a.num_t,
@@ -429,6 +492,8 @@ def main(argv=None):
             if a.interface:                                     # the wild type's row rides along in every row: any rank can write the table
                 local['interface'] = torch.cat([traj[-1]['interface']] + ([traj[-1]['interface_relaxed']] if a.relax else []) +
                                                [iface.wild().expand(n, -1)], 1)
+            if a.ensemble:                                      # N, CA, C, O of the antibody rows: what the comparison reads
+                local['backbone'] = traj[-1]['atom14_results'][:, :, :4].float().contiguous()
         else:                                                   # more ranks than samples: join the gather with zero-row blocks
             local = {'seq': torch.zeros(0, Lab, dtype=torch.int64, device=dev), 'pLDDT': torch.zeros(0, Lab, device=dev)}
             if a.score:
@@ -439,8 +504,10 @@ def main(argv=None):
                 local['relax'] = torch.zeros(0, NR, dtype=torch.float64, device=dev)
             if a.interface:
                 local['interface'] = torch.zeros(0, NI, dtype=torch.float64, device=dev)
+            if a.ensemble:
+                local['backbone'] = torch.zeros(0, Lab, 4, 3, dtype=torch.float32, device=dev)
         if plan is not None:
-            row = torch.zeros(n, 4 + maxLab + NS + n_rec * (1 + NS) + NR + NI, dtype=torch.float64)
+            row = torch.zeros(n, WIDTH, dtype=torch.float64)
             row[:, 0], row[:, 1], row[:, 3] = ji, torch.tensor(ids, dtype=torch.float64), Lab
             row[:, 2] = local['pLDDT'].float().mean(1).double().cpu()       # (the float32 mean of the sample-sharded path: same TSV digits)
             row[:, 4:4 + Lab] = local['seq'].double().cpu()
@@ -448,6 +515,8 @@ def main(argv=None):
                 row[:, 4 + maxLab:4 + maxLab + NS] = local['scores'].cpu()
                 if n_rec:
                     row[:, 4 + maxLab + NS:4 + maxLab + NS + n_rec * (1 + NS)] = local['traj_scores'].reshape(n, -1).cpu()
+            if a.ensemble:                                      # f32 values are exact in float64
+                row[:, E0:E0 + 12 * Lab] = local['backbone'].reshape(n, -1).double().cpu()
             if a.relax:
                 row[:, row.shape[1] - NI - NR:row.shape[1] - NI] = local['relax'].cpu()
             if a.interface:
@@ -468,9 +537,11 @@ def main(argv=None):
             if a.interface:
                 it = res['interface'].tolist()
                 files.append(_write_interface(out_dir, cname, it[0][NI - len(INTERFACE_COLUMNS):], list(enumerate(it)), a.relax))
+            if a.ensemble:
+                files += analyze_ensemble(ji, out_dir, cname, list(range(N)), res['seq'], res['backbone'])
     if plan is not None:
         # ---- the one collective of the set: every rank's rows of the designs table (counts known from the common plan)
-        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, 4 + maxLab + NS + n_rec * (1 + NS) + NR + NI, dtype=torch.float64)
+        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, WIDTH, dtype=torch.float64)
         if not (a.debug_one_gpu and world > 1):
             table = table.to(dev)
         counts = [sum(len(ids_) for _, ids_ in p) for p in plan]
@@ -491,6 +562,10 @@ def main(argv=None):
                 if a.interface:
                     files.append(_write_interface(jobs[ji][2], load_job(ji)['cname'], rows[0, rows.shape[1] - len(INTERFACE_COLUMNS):].tolist(),
                                                   [(int(r[1]), r[r.shape[0] - NI:].tolist()) for r in rows], a.relax))
+                if a.ensemble:
+                    lab = int(rows[0, 3])
+                    files += analyze_ensemble(ji, jobs[ji][2], load_job(ji)['cname'], [int(r[1]) for r in rows], rows[:, 4:4 + lab].long(),
+                                              rows[:, E0:E0 + 12 * lab].float().reshape(N, lab, 4, 3))
     if world > 1 or a.force_collective:
         import torch.distributed as dist
         dist.barrier()

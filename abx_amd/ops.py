@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1239,3 +1239,55 @@ def interface_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, Lab=None
     ws = torch.empty(max(int(lib.abx_interface_scores_workspace_bytes(B, L, a.P)), 16), dtype=torch.uint8, device=dev)
     check(lib.abx_interface_scores(C.byref(a), _p(ws), _stream()), 'abx_interface_scores')
     return out
+
+
+def ensemble_pairs(atom14, seq, region, atoms=4, n_region=None, out=None):
+    """All pairs of N structures of one complex (abx_ensemble_pairs): (3, N, N) float64 planes rmsd_fit (after the optimal proper
+    rotation), rmsd_frame (no superposition) and seq_diff (differing region residues) over the set rows of `region`.
+    atom14 (N,Lp,14,3) f32 (a batch-strided view is read in place), seq (N,>=Lp) int64 tokens, region (>=Lp) bool / uint8 on the
+    device, atoms 1 (C-alpha) or 4 (N, CA, C, O).  n_region: the number of set rows below Lp (None: counted here, one host
+    synchronisation; abx_amd.ensemble.EnsembleAnalyzer counts once per complex).  out: (3,N,N) float64 contiguous, or None.
+    One launch, no synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    N, Lp = atom14.shape[0], atom14.shape[1]
+    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == N and seq.shape[1] >= Lp, (atom14.shape, seq.shape)
+    assert region.dim() == 1 and region.shape[0] >= Lp, region.shape
+    x = _f32(atom14)
+    if not x[0].is_contiguous():
+        x = x.contiguous()
+    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
+    rg = region if (region.dtype == torch.uint8 and region.is_contiguous()) else region.ne(0).to(torch.uint8).contiguous()
+    M = int(rg[:Lp].ne(0).sum()) if n_region is None else int(n_region)
+    if out is None:
+        out = torch.empty(3, N, N, dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (3, N, N) and out.is_contiguous() and out.is_cuda, 'out: (3,N,N) float64'
+    a = AbxEnsemblePairsArgs()
+    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0) if N > 1 else Lp * 42, Lp
+    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0) if N > 1 else sq.shape[1]
+    a.region, a.atoms, a.M = _p(rg), int(atoms), M
+    a.planes, a.plane_stride, a.N = _p(out), N * N, N
+    check(lib.abx_ensemble_pairs(C.byref(a), None, _stream()), 'abx_ensemble_pairs')
+    return out
+
+
+def ensemble_cluster(planes, metric=0, cutoff=1.0, out=None):
+    """Daura / GROMOS clusters on plane `metric` (0 rmsd_fit, 1 rmsd_frame) of the (3,N,N) float64 planes of ensemble_pairs and one row
+    of abx_amd.ensemble.ENSEMBLE_COLUMNS per design (abx_ensemble_cluster).  -> (table (N,10) float64, centres (N) int32 padded with
+    -1, n_clusters (1) int32), all on the device.  out: (N,10) float64 rows with unit column stride and any row stride, or None.
+    One launch, no synchronisation."""
+    lib = _lib.load()
+    dev = planes.device
+    N = planes.shape[1]
+    assert planes.dtype == torch.float64 and tuple(planes.shape) == (3, N, N) and planes.is_contiguous() and planes.is_cuda, 'planes: (3,N,N) float64'
+    if out is None:
+        out = torch.empty(N, _lib.ENS_COLS, dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (N, _lib.ENS_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (N, 10) float64 rows'
+    centres = torch.empty(N, dtype=torch.int32, device=dev)
+    n_clusters = torch.empty(1, dtype=torch.int32, device=dev)
+    a = AbxEnsembleClusterArgs()
+    a.planes, a.plane_stride, a.metric, a.cutoff = _p(planes), N * N, int(metric), float(cutoff)
+    a.out, a.out_stride = _p(out), out.stride(0) if N > 1 else _lib.ENS_COLS
+    a.centres, a.n_clusters, a.N = _p(centres), _p(n_clusters), N
+    check(lib.abx_ensemble_cluster(C.byref(a), _stream()), 'abx_ensemble_cluster')
+    return out, centres, n_clusters

@@ -670,6 +670,67 @@ long long abx_interface_scores_workspace_bytes(int B, int L, int P);
 int abx_interface_scores(const AbxInterfaceArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Ensemble analysis of the N designs of ONE complex: what a design is to the other designs (how many different loops are these, which
+ * are the same answer twice, which few go on to the expensive evaluation).  Two calls: all pairs, then clusters and a summary row.
+ *
+ * abx_ensemble_pairs.  The structures are given as for abx_design_scores: pred_atom14 (N, Lpred, 14, 3) f32 with the structure stride
+ * pred_sb (floats; the [:, :Lab] view of a longer tensor is read in place), pred_seq (N, >= Lpred) int64 with the row stride
+ * pred_seq_sb.  region: (>= Lpred) bytes shared by the batch; the first M set rows below Lpred are the compared residues (M: their
+ * number, counted by the caller once per complex).  atoms: 1 = C-alpha only (atom14 slot 1), 4 = backbone N, CA, C, O (slots 0-3).
+ * Points per structure P = M * atoms in residue order, 1 <= P <= ABX_ENS_MAX_POINTS.
+ * planes: three (N, N) float64 planes, plane p at planes + p * plane_stride (plane_stride >= N * N doubles), each symmetric with a
+ * zero diagonal:
+ *   0 rmsd_fit    sqrt(sum_p |R (a_p - ca) - (b_p - cb)|^2 / P) with ca, cb the centroids and R the optimal PROPER rotation of the
+ *                 centred sets (the Kabsch convention of abx/utils.py:444-465, no reflection): the difference in shape
+ *   1 rmsd_frame  sqrt(sum_p |a_p - b_p|^2 / P), no superposition: all designs share the complex's frame, the difference in placement
+ *   2 seq_diff    the number of compared rows whose tokens differ (an exact integer)
+ * Arithmetic: float64 from the float32 coordinates; centroid of a structure, covariance and both deviations of a pair as sums over the
+ * points in index order; R from Horn's quaternion matrix by cyclic Jacobi rotations (any eigenvector of a degenerate largest
+ * eigenvalue is optimal: collinear and planar point sets give their well-defined RMSD); the deviation of plane 0 is summed in a second
+ * pass over the points with R, never formed as G_a + G_b - 2 lambda (which cancels for close structures).  (i, j) with i < j is
+ * computed once and written to both entries; a pair reads nothing but its two structures, so its value does not depend on N or on
+ * its neighbours in the batch.  One launch, no atomics, no allocation, no synchronisation; the workspace is empty today
+ * (abx_ensemble_pairs_workspace_bytes returns 0 and a NULL workspace is accepted).
+ *
+ * abx_ensemble_cluster.  planes / plane_stride: the three planes above (symmetric: row i is read as column i).  Clusters by the
+ * Daura / GROMOS rule on plane `metric` (0 rmsd_fit, 1 rmsd_frame) with `cutoff`: the neighbours of i are the j != i with d[i][j] <=
+ * cutoff; the unassigned design with the most unassigned neighbours (ties: the lowest index) becomes a centre and forms the next
+ * cluster with them; repeated until none is left.  N <= ABX_ENS_MAX_N (the neighbour bits of all designs stay in the LDS of one
+ * workgroup); a larger N is an argument error, nothing is truncated.
+ * out: ABX_ENS_COLS doubles per design (row stride out_stride >= ABX_ENS_COLS; abx_amd.ensemble.ENSEMBLE_COLUMNS):
+ *   0 cluster          cluster index in order of discovery   5 rmsd_frame_mean  over the other N - 1 designs
+ *   1 is_centre        0 / 1                                 6 rmsd_frame_min
+ *   2 n_neighbours     others within the cutoff on the       7 seq_diff_mean    mean number of differing compared residues
+ *                      clustering plane (all designs)        8 n_same_seq       others with seq_diff == 0
+ *   3 rmsd_fit_mean    over the other N - 1 designs          9 first_same_seq   lowest index with seq_diff == 0 to this design
+ *   4 rmsd_fit_min                                                              (its own index: the first of its sequence)
+ * Sums run over the other designs in index order; N = 1: means and minima are NaN, counts 0.  centres: (N) int32, the centres in
+ * order of discovery, padded with -1; n_clusters: one int32.  One launch of two workgroups (the clusters; the summary rows, one
+ * thread per design), no atomics, no allocation, no synchronisation. */
+#define ABX_ENS_MAX_POINTS 512
+#define ABX_ENS_MAX_N 1024
+#define ABX_ENS_COLS 10
+typedef struct AbxEnsemblePairsArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* region;                    /* (>= Lpred) */
+    int atoms, M;
+    double* planes; long long plane_stride;
+    int N;
+} AbxEnsemblePairsArgs;
+long long abx_ensemble_pairs_workspace_bytes(int N, int P);
+int abx_ensemble_pairs(const AbxEnsemblePairsArgs* a, void* workspace, hipStream_t stream);
+typedef struct AbxEnsembleClusterArgs {
+    const double* planes; long long plane_stride;
+    int metric;
+    double cutoff;
+    double* out; long long out_stride;
+    int* centres; int* n_clusters;
+    int N;
+} AbxEnsembleClusterArgs;
+int abx_ensemble_cluster(const AbxEnsembleClusterArgs* a, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
