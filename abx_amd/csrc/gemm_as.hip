@@ -131,14 +131,10 @@ __device__ __forceinline__ void as_conv_init(AsConv& c, const AbxGemm& g) {
     c.ln = g.ln_csum != nullptr;
     c.relu = g.a_relu != 0;
 }
+// (xv: the lane's 8 k values of its row, read from the landing image by the caller)
 template <bool FIRST>
-__device__ __forceinline__ void as_conv_ktile(AsConv& c, char* img) {
+__device__ __forceinline__ void as_conv_values(AsConv& c, float (&xv)[8], char* img) {
     const int lane = threadIdx.x & 63;
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(img + c.rd0);
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(img + c.rd1);
-    float xv[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { xv[e] = lo[e]; xv[4 + e] = hi[e]; }
     if (c.ln) {
         if (FIRST) c.lshift = __shfl(xv[0], lane & 31, 64);      // the row's first element
         const f32x2 sh2 = {c.lshift, c.lshift};
@@ -162,13 +158,21 @@ __device__ __forceinline__ void as_conv_ktile(AsConv& c, char* img) {
     *reinterpret_cast<u32x4*>(img + c.wr) = u32x4{q0[0], q0[1], q0[2], q0[3]};
     *reinterpret_cast<u32x4*>(img + c.wr + 1024) = u32x4{q1[0], q1[1], q1[2], q1[3]};
 }
+template <bool FIRST>
+__device__ __forceinline__ void as_conv_ktile(AsConv& c, char* img) {
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(img + c.rd0);
+    const f32x4 hi = *reinterpret_cast<const f32x4*>(img + c.rd1);
+    float xv[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { xv[e] = lo[e]; xv[4 + e] = hi[e]; }
+    as_conv_values<FIRST>(c, xv, img);
+}
 // (mean - shift, rstd * cs) of the wave's 32 rows -> st.  cs = the accumulator scale 2^-(a_exp + b_exp) of the split-f16 product: the
 // epilogues compute (rstd cs) (acc - dmean (csum / cs)) instead of rstd (acc cs - dmean csum) - the same bits (every scaling by the
 // power of two is exact and commutes with the roundings), one multiplication less per element
-__device__ __forceinline__ void as_conv_finish(const AsConv& c, float* st, int wm, float eps, float cs) {
+__device__ __forceinline__ void as_conv_finish(const AsConv& c, float* st, int wm, float eps, float cs, float invK = 1.0f / (float)(AS_NK * 16)) {
     const int lane = threadIdx.x & 63;
     const float ls = c.ls2[0] + c.ls2[1], lq = c.lq2[0] + c.lq2[1];
-    const float invK = 1.0f / (float)(AS_NK * 16);
     const float sm = ls + __shfl_xor(ls, 32, 64), sq = lq + __shfl_xor(lq, 32, 64);
     if (lane < 32) {
         const float dm = sm * invK;
@@ -682,6 +686,391 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(const AbxGemm g, const 
     probe.finish();
 }
 
+
+// ---- the TriangleMultiplication tail as an A-stationary dual GEMM ----------------------------------------------------------------------
+//     out = (LN(product) W_out + b) * sigmoid(LN(z) W_gate + b_g) + z                                              (seqformer.py:496-503)
+// gemm3_dual_kernel<128, 96, ...> gives every 128-row tile two blocks (one per column half) that each walk the product rows (K = 128) AND
+// the z rows (K2 = 192): the A side of both main loops is paid twice per row.  Here a block owns 64 rows and all 192 columns:
+//   gate walk     the z rows arrive in one burst and are split in place exactly as in as_block (statistics + split of k-tile s + 2 ride in
+//                 step s); 12 k-steps against the final-gate planes into one accumulator set (wave tile 32 x 96: 48 registers), turned in
+//                 registers into the gate VALUES sigmoid(.) and kept;
+//   product       channel-major rows: k-tile t is requested at step t + 4 of the gate walk into the 4 KB slot the z k-tile t + 4 has just left
+//                 (landing image per row half [16 k][32 rows] fp32, in place -> pieces [2][32][16]); statistics as gemm3_mainloop<AMODE 1>
+//                 forms them (lane = (row, k half), shift = the row's element at k = 0, k-tiles in order);
+//   output walk   8 k-steps against the proj_out planes into a second accumulator set; epilogue in registers (the 4 x 4 quad transpose of
+//                 plain_slice): folded LayerNorm, bias, x the kept gate value, + z (read again from global memory: the pieces are 23-bit
+//                 images), 16-byte stores.
+// The weight planes of both GEMMs stream as ONE sequence of 20 k-tiles [2][192][16] (12 KB).  Two stages fit behind the A region; the
+// slots of the z k-tiles 0 .. 2 become a third stage once those are in registers (ad_wslot), so from step 2 on the tile of step s + 3 is
+// requested when step s starts, with a counted wait.  Roles as in as_block: the column-0 waves own the A side, the column-1 waves the weights.  Every accumulator receives the products of gemm3_dual_kernel in the same order, the
+// statistics and both epilogue expressions are the same code: results are bit-identical to the tile kernel.
+constexpr int AD_BN = 192, AD_NK2 = 12, AD_NK1 = 8, AD_NS = AD_NK2 + AD_NK1;
+constexpr int AD_PLANE = AD_BN * 32;                                 // one plane of a weight k-tile [192][16] f16: 6 144
+constexpr int AD_STAGE = 2 * AD_PLANE;                               // 12 288
+constexpr int AD_OFF_RING = AS_A;
+constexpr int AD_OFF_ST = AD_OFF_RING + 2 * AD_STAGE;                // [4][64]: z (mean - shift | rstd cs2), product (mean - shift | rstd cs)
+constexpr int AD_OFF_CONST = AD_OFF_ST + 4 * 64 * 4;                 // [4][192]: ln2_csum | bias2 | ln_csum | bias
+constexpr int AD_LDS = AD_OFF_CONST + 4 * AD_BN * 4;                 // 77 824 (61 granules of 1 280: two blocks per CU)
+static_assert(AD_LDS <= 81920, "two blocks per CU");
+constexpr int AD_P0 = 4;                                             // slot of the product k-tile 0 in the A region (k-tile t: slot AD_P0 + t)
+// LDS offset of the weight tile of step t.  Two stages behind the A region serve the steps 0 .. 3; from step 2 on the slots 0 .. 2 of the A
+// region (12 KB: the z k-tiles 0 .. 2, in registers by then) are a THIRD stage and the ring is three deep: tile t + 3 is requested when step
+// t starts, two steps of matrix work ahead of its first read
+constexpr int ad_wslot(int t) { return t < 4 ? AD_OFF_RING + (t & 1) * AD_STAGE : ((t - 4) % 3 == 0 ? AD_OFF_RING : ((t - 4) % 3 == 1 ? 0 : AD_OFF_RING + AD_STAGE)); }
+
+// the z burst of a column-0 wave: as_issue_a for the operand A2 (rows of the UNpadded pair tensor when pair_Lp > 0)
+__device__ __forceinline__ void ad_issue_z(const AbxGemm& g, char* lds, int m0, int b, int wm) {
+    const int lane = threadIdx.x & 63;
+    const bool remap = g.pair_Lp > 0;
+    const long long row0 = remap ? 0 : m0;
+    const char* baseA = reinterpret_cast<const char*>(g.A2 + (long long)b * g.sA2b + row0 * g.sA2m);
+    unsigned offA[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r = 16 * i + (lane >> 2), p = lane & 3;
+        const int kq = p ^ ((r >> 2) & 3);
+        const int gri = min(m0 + wm * 32 + r, g.M - 1);
+        long long gr = gri;
+        if (remap) {
+            const int pi = gri / g.pair_Lp, pj = min(gri - pi * g.pair_Lp, g.pair_L - 1);
+            gr = (long long)pi * g.pair_L + pj;
+        }
+        offA[i] = (unsigned)(((gr - row0) * g.sA2m + kq * 4) * 4);
+    }
+    char* dst = lds + wm * AS_HALF;
+#pragma unroll
+    for (int kt = 0; kt < AD_NK2; ++kt)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) as_glds16(baseA + kt * 64 + as_vgpr32(offA[i]), dst + kt * AS_KT + i * 1024);
+}
+
+// statistics + split of one (k-tile, row half) of the channel-major product: landing image [16 k][32 rows] fp32
+template <bool FIRST>
+__device__ __forceinline__ void ad_conv_ptile(AsConv& c, char* img) {
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    float xv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) xv[e] = *reinterpret_cast<const float*>(img + (8 * h + e) * 128 + r * 4);
+    as_conv_values<FIRST>(c, xv, img);
+}
+
+__device__ __forceinline__ void ad_rendezvous(u32x4 (&fa)[2], u32x4 (&fb)[3][2]) {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier"
+                 : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]), "+v"(fb[2][0]), "+v"(fb[2][1])
+                 :
+                 : "memory");
+}
+// the streaming waves: the weight tile of the next step has landed (the newest N instructions - the tile after it - may stay in flight)
+template <int N>
+__device__ __forceinline__ void ad_rendezvous_vm(u32x4 (&fa)[2], u32x4 (&fb)[3][2]) {
+    asm volatile("s_waitcnt vmcnt(%8) lgkmcnt(0)\n\ts_barrier"
+                 : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]), "+v"(fb[2][0]), "+v"(fb[2][1])
+                 : "n"(N)
+                 : "memory");
+}
+
+template <bool EDGE>
+__device__ __forceinline__ void as_dual_block(const AbxGemm& g, char* lds, int mt, int b) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave >> 1, wn = wave & 1, h = lane >> 5;
+    const int m0 = mt * AS_BM;
+    float* st = reinterpret_cast<float*>(lds + AD_OFF_ST);
+    const float* cc = reinterpret_cast<const float*>(lds + AD_OFF_CONST);
+
+    // ---- weight operands: wave (wm, 1) fetches plane wm of a stage, six 1 KB chunks of 32 columns
+    const char* wbase2 = reinterpret_cast<const char*>(g.B2_split);
+    const char* wbase1 = reinterpret_cast<const char*>(g.B_split + (long long)b * g.sB3b);
+    const long long wk2 = g.sB23k * 2, wk1 = g.sB3k * 2;
+    const unsigned wchunk2 = (unsigned)(32 * g.sB23n * 2), wchunk1 = (unsigned)(32 * g.sB3n * 2);
+    unsigned woff2, woff1;
+    {
+        const int row = lane >> 1, half = (lane & 1) ^ ((row >> 3) & 1);
+        woff2 = (unsigned)((wm * g.sB23p + (long long)row * g.sB23n + 8 * half) * 2);
+        woff1 = (unsigned)((wm * g.sB3p + (long long)row * g.sB3n + 8 * half) * 2);
+    }
+    // weight tile of step s (0 .. 11: the gate planes, 12 .. 19: the proj_out planes) -> its stage (ad_wslot)
+    auto issue_w = [&](auto s_) __attribute__((always_inline)) {
+        constexpr int s = decltype(s_)::value;
+        char* dst = lds + ad_wslot(s) + wm * AD_PLANE;
+        if constexpr (s < AD_NK2) {
+            const char* src = wbase2 + s * wk2;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) as_glds16(src + i * wchunk2 + as_vgpr32(woff2), dst + i * 1024);
+        } else {
+            const char* src = wbase1 + (s - AD_NK2) * wk1;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) as_glds16(src + i * wchunk1 + as_vgpr32(woff1), dst + i * 1024);
+        }
+    };
+
+    // ---- product operand: wave (wm, 0) fetches its row half of a k-tile, two instructions of 8 k x 32 rows (M % 4 == 0: the dispatch)
+    const char* pbase = reinterpret_cast<const char*>(g.A + (long long)b * g.sAb + m0);
+    const long long pk = 16LL * g.sAk * 4;
+    unsigned poff[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int kl = 8 * i + (lane >> 3);
+        const int gm = min(m0 + wm * 32 + 4 * (lane & 7), g.M - 4) - m0;
+        poff[i] = (unsigned)(((long long)kl * g.sAk + gm) * 4);
+    }
+    auto issue_p = [&](int kt) __attribute__((always_inline)) {
+        char* dst = lds + (AD_P0 + kt) * AS_KT + wm * AS_HALF;
+        const char* src = pbase + kt * pk;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) as_glds16(src + as_vgpr32(poff[i]), dst + i * 1024);
+    };
+
+    // ---- prologue.  Column 0: the z burst, statistics + split of its first two k-tiles.  Column 1: column constants, two weight stages
+    const float cs2 = __builtin_ldexpf(1.0f, -ABX_F16_A_EXP - g.b2_exp), inv_cs2 = __builtin_ldexpf(1.0f, ABX_F16_A_EXP + g.b2_exp);
+    const float cs1 = __builtin_ldexpf(1.0f, -ABX_F16_A_EXP - g.b_exp), inv_cs1 = __builtin_ldexpf(1.0f, ABX_F16_A_EXP + g.b_exp);
+    AsConv cz, cp;
+    char* a_half = lds + wm * AS_HALF;
+    if (wn == 0) {
+        ad_issue_z(g, lds, m0, b, wm);
+        as_conv_init(cz, g);
+        cz.ln = true;
+        cz.relu = false;
+        cp = cz;
+        as_wait_vm<20>();
+        as_conv_ktile<true>(cz, a_half);
+        as_conv_ktile<false>(cz, a_half + AS_KT);
+    } else {
+        const float* c0 = wm ? g.ln_csum : g.ln2_csum;
+        const float* c1 = wm ? g.bias : g.bias2;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                char* dst = lds + AD_OFF_CONST + (2 * wm + a) * (AD_BN * 4) + i * 256;
+                __builtin_amdgcn_global_load_lds((glb_ptr_t)((a ? c1 : c0) + i * 64 + lane), (lds_ptr_t)dst, 4, 0, 0);
+            }
+        issue_w(IC<0>{});
+        issue_w(IC<1>{});
+        as_wait_vm<6>();                                        // the constants and stage 0 have landed
+    }
+    __syncthreads();
+
+    // ---- fragments
+    const int offAf = wm * AS_HALF + as_plane_off<32>(0, lane & 31, h);                       // + kt * AS_KT + p * 1024
+    const int offBf = as_plane_off<AD_BN>(0, wn * 96 + (lane & 31), h);                       // + ad_wslot + p * AD_PLANE + j * 1024
+    u32x4 fa[2][2], fb[2][3][2];
+    auto read_frags = [&](int set, int kt, int wslot) __attribute__((always_inline)) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) fa[set][p] = *reinterpret_cast<const u32x4*>(lds + kt * AS_KT + offAf + p * 1024);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) fb[set][j][p] = *reinterpret_cast<const u32x4*>(lds + offBf + wslot + p * AD_PLANE + j * 1024);
+    };
+
+    f32x16 gatev[3], acc[3];
+    const float* st_w = st + wm * 32 + 4 * h;                   // + 8 rq: this lane's rows 8 rq + 4 h + c of the wave's 32
+    // the gate accumulators -> gate values (gemm_epilogue.h, the acc2 expression; st holds rstd cs2, the column sums go in as csum / cs2)
+    auto gate_values = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int n = wn * 96 + j * 32 + (lane & 31);
+            const float csum2 = cc[n] * inv_cs2, bias2 = cc[AD_BN + n];
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const f32x4 dm4 = *reinterpret_cast<const f32x4*>(st_w + 8 * rq), rs4 = *reinterpret_cast<const f32x4*>(st_w + 64 + 8 * rq);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float gv = rs4[c] * (gatev[j][4 * rq + c] - dm4[c] * csum2) + bias2;
+                    gatev[j][4 * rq + c] = sigmoidf_(gv);
+                }
+            }
+        }
+    };
+
+    // rows of the epilogue: after the quad transpose a lane holds row 8 rq + 4 h + (lane & 3), four consecutive columns per sub-tile
+    f32x4 rv[4][3];
+    long long row_off_c[4];
+    bool row_ok[4];
+    auto load_resid = [&]() __attribute__((always_inline)) {
+        const float* rd = g.resid + (long long)b * g.sRb;
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+            const int m = m0 + wm * 32 + 8 * rq + 4 * h + (lane & 3);
+            bool ok = !EDGE || m < g.M;
+            long long mo = m;
+            if (g.c_pair) {                                     // padded pair position -> unpadded pair row; pad columns are not stored
+                const int pi = m / g.pair_Lp, pj = m - pi * g.pair_Lp;
+                ok = ok && pj < g.pair_L;
+                mo = (long long)pi * g.pair_L + pj;
+            }
+            row_ok[rq] = ok;
+            row_off_c[rq] = mo * g.sCm;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int n = wn * 96 + j * 32 + ((lane & 31) >> 2) * 4;
+                rv[rq][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (ok) rv[rq][j] = *reinterpret_cast<const f32x4*>(rd + mo * g.sRm + n);
+            }
+        }
+    };
+
+    // ---- one k-step of the 20; set = s & 1 holds its fragments
+    auto step = [&](auto s_, auto role_) __attribute__((always_inline)) {
+        constexpr int s = decltype(s_)::value, role = decltype(role_)::value, set = s & 1;
+        // the weight tile of step s + 1 has landed; once the ring is three deep the tile of step s + 2 (six instructions) may be in flight
+        if constexpr (role == 0) ad_rendezvous(fa[set], fb[set]);
+        else ad_rendezvous_vm<(s >= 3 && s + 2 < AD_NS) ? 6 : 0>(fa[set], fb[set]);
+        if constexpr (role == 1) {
+            if constexpr (s < 2) issue_w(IC<s + 2>{});
+            else if constexpr (s == 2) { issue_w(IC<4>{}); issue_w(IC<5>{}); }
+            else if constexpr (s + 3 < AD_NS) issue_w(IC<s + 3>{});
+        } else {
+            // the vector-memory queue of a column-0 wave: the z burst (24), then two instructions per product k-tile, issued at the steps 4 .. 11
+            constexpr int np = s < AD_P0 ? 0 : (s - AD_P0 + 1 < AD_NK1 ? s - AD_P0 + 1 : AD_NK1);      // product k-tiles requested so far
+            if constexpr (s >= AD_P0 && s < AD_P0 + AD_NK1) issue_p(s - AD_P0);       // (the fragments of z k-tile s are in registers: its slot is free)
+            if constexpr (s < AD_NK2 - 2) {
+                as_wait_vm<(24 - 2 * (s + 3)) + 2 * np>();
+                as_conv_ktile<false>(cz, a_half + (s + 2) * AS_KT);
+                if constexpr (s == AD_NK2 - 3) as_conv_finish(cz, st, wm, g.ln_eps, cs2);
+            } else if constexpr (s < AD_NK2) {                  // steps 10, 11: the product k-tiles 0, 1
+                as_wait_vm<2 * (np - 1 - (s - 10))>();
+                ad_conv_ptile<s == 10>(cp, a_half + (AD_P0 + s - 10) * AS_KT);
+            } else if constexpr (s - AD_NK2 + 2 < AD_NK1) {     // output step t: the product k-tile t + 2
+                constexpr int kp = s - AD_NK2 + 2;
+                as_wait_vm<2 * (AD_NK1 - 1 - kp)>();
+                ad_conv_ptile<false>(cp, a_half + (AD_P0 + kp) * AS_KT);
+                if constexpr (kp == AD_NK1 - 1) as_conv_finish(cp, st + 128, wm, g.ln_eps, cs1, 1.0f / (float)(AD_NK1 * 16));
+            }
+        }
+        if constexpr (s + 1 < AD_NS) read_frags((s + 1) & 1, (s + 1) < AD_NK2 ? s + 1 : s + 1 - AD_NK2 + AD_P0, ad_wslot(s + 1));
+        u32x4 p2[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) p2[j] = f16x8_lo(fb[set][j][0]);
+        // a1 p2, a0 p1, a0 p0 (smallest first); the first term of a GEMM starts from zero
+        if constexpr (s < AD_NK2) {
+            if constexpr (s == 0) {
+                const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < 3; ++j) gatev[j] = mfma_split(fa[set][1], p2[j], z);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) gatev[j] = mfma_split(fa[set][1], p2[j], gatev[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gatev[j] = mfma_split(fa[set][0], fb[set][j][1], gatev[j]);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gatev[j] = mfma_split(fa[set][0], fb[set][j][0], gatev[j]);
+        } else {
+            if constexpr (s == AD_NK2) {
+                const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[j] = mfma_split(fa[set][1], p2[j], z);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[j] = mfma_split(fa[set][1], p2[j], acc[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[j] = mfma_split(fa[set][0], fb[set][j][1], acc[j]);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[j] = mfma_split(fa[set][0], fb[set][j][0], acc[j]);
+        }
+        // (the z statistics were written at step 9; the VALU work runs under the first MFMAs of the output walk)
+        if constexpr (s == AD_NK2) gate_values();
+    };
+
+    read_frags(0, 0, ad_wslot(0));
+    auto walk = [&](auto role_) __attribute__((always_inline)) { as_static_for<0, AD_NS>([&](auto s_) { step(s_, role_); }); };
+    if (wn == 0) walk(IC<0>{});
+    else walk(IC<1>{});
+
+    // ---- epilogue: gemm_epilogue for the dual case, in registers (the product statistics were written at step 17)
+    float* Cb = g.C + (long long)b * g.sCb;
+    bool bad = false;
+    load_resid();                                               // (all twelve 16-byte loads of the lane in flight before the arithmetic)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int nl = wn * 96 + j * 32 + (lane & 31);
+        const float csum1 = cc[2 * AD_BN + nl] * inv_cs1, bias1 = cc[3 * AD_BN + nl];
+        const int n = wn * 96 + j * 32 + ((lane & 31) >> 2) * 4;
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+            const f32x4 dm4 = *reinterpret_cast<const f32x4*>(st_w + 128 + 8 * rq), rs4 = *reinterpret_cast<const f32x4*>(st_w + 192 + 8 * rq);
+            float x[4], o[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float v = rs4[c] * (acc[j][4 * rq + c] - dm4[c] * csum1);
+                v = v + bias1;
+                x[c] = v * gatev[j][4 * rq + c];
+            }
+            as_quad_transpose(x, o);
+            f32x4 ov;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                ov[c] = o[c] + rv[rq][j][c];
+                bad |= row_ok[rq] && __builtin_amdgcn_classf(ov[c], 0x207);
+            }
+            if (row_ok[rq]) *reinterpret_cast<f32x4*>(Cb + row_off_c[rq] + n) = ov;
+        }
+    }
+    if (g.range_flag && __any(bad) && lane == 0) atomicOr(g.range_flag, g.range_tag);
+}
+
+__global__ __launch_bounds__(256, 2) void gemm_as_dual_kernel(const AbxGemm g) {
+    extern __shared__ __attribute__((aligned(16))) float as_smem[];
+    char* lds = reinterpret_cast<char*>(as_smem);
+    const ClockProbe probe(g.clock_probe);
+    const unsigned ntm = (unsigned)((g.M + AS_BM - 1) / AS_BM);
+    const unsigned nwg = gridDim.x, bid = blockIdx.x;
+    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
+    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const int b = (int)(wgid / ntm), mt = (int)(wgid - (unsigned)b * ntm);
+    if ((mt + 1) * AS_BM > g.M) as_dual_block<true>(g, lds, mt, b);
+    else as_dual_block<false>(g, lds, mt, b);
+    probe.finish();
+}
+
+// The dual descriptor of the TriangleMultiplication tail -> gemm_as_dual_kernel.  Returns 1 when the tile kernel (gemm3_dual_kernel) keeps it.
+int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    static const bool off = [] {
+        const char* e = getenv("ABX_NO_DUAL_AS");               // (A / B measurements: the tile kernel everywhere)
+        return e != nullptr && !(e[0] == '0' && e[1] == 0);
+    }();
+    if (off) return 1;
+    if (g.exact == 1 || g.K != AD_NK1 * 16 || g.K2 != AD_NK2 * 16 || g.N != AD_BN) return 1;
+    if (!g.A || g.A_split || g.sAm != 1 || g.M % 4 != 0 || g.M < 4 || !g.B_split || !g.B2_split || !g.b_f16) return 1;
+    if (!g.ln_csum || g.ln_stats || !g.ln2_csum || !g.bias || !g.bias2 || !g.resid || !g.C) return 1;
+    if (g.act != 0 || g.alpha != 1.0f || g.gate || g.mlp || g.glu || g.rowscale || g.out_ln_w || g.C_split || g.c_transposed || g.a_relu ||
+        g.a_pair_transpose > 0 || g.a_pair || g.c_split_tile || g.batch_inner || g.c_planes_from)
+        return 1;
+    if (!g.c_vec_ok || !g.r_vec_ok) return 1;
+    // out of place: a block stores its rows while it still reads them as the residual, and other launches may share z
+    const long long rows_c = g.c_pair ? (long long)g.pair_L * g.pair_L : g.M;
+    auto overlaps = [&](const float* p, long long sb, long long sm) {
+        const float* c1 = g.C + (g.batch - 1) * g.sCb + (rows_c - 1) * g.sCm + AD_BN;
+        const float* p1 = p + (g.batch - 1) * sb + (rows_c - 1) * sm + AD_BN;
+        return g.C < p1 && p < c1;
+    };
+    if (overlaps(g.A2, g.sA2b, g.sA2m) || overlaps(g.resid, g.sRb, g.sRm)) return 1;
+    if (!al16(g.A) || g.sAk % 4 != 0 || g.sAb % 4 != 0 || !al16(g.A2) || g.sA2m % 4 != 0 || g.sA2b % 4 != 0) return 1;
+    if (!al16(g.B_split) || g.sB3n % 8 != 0 || g.sB3p % 8 != 0 || g.sB3k % 8 != 0 || g.sB3b % 8 != 0) return 1;
+    if (!al16(g.B2_split) || g.sB23n % 8 != 0 || g.sB23p % 8 != 0 || g.sB23k % 8 != 0) return 1;
+    if (g.b_exp < -100 || g.b_exp > 100 || g.b2_exp < -100 || g.b2_exp > 100) return 1;
+    // 32-bit per-lane DMA offsets: the z rows (from the batch base under the pair-row map), the product columns, the weight planes
+    if ((g.pair_Lp > 0 ? (long long)g.pair_L * g.pair_L * g.sA2m : 64LL * g.sA2m) >= (1LL << 30)) return 1;
+    if (16LL * g.sAk + g.M >= (1LL << 30)) return 1;
+    if (g.sB3p + AD_BN * g.sB3n >= (1LL << 30) || g.sB23p + AD_BN * g.sB23n >= (1LL << 30)) return 1;
+    if ((long long)AD_NK1 * g.sB3k >= (1LL << 31) || (long long)AD_NK2 * g.sB23k >= (1LL << 31)) return 1;
+    const long long ntm = ((long long)g.M + AS_BM - 1) / AS_BM;
+    if (ntm * g.batch >= (1LL << 31)) return 1;
+    // the launch-size rule of the walk below (and its INVARIANT: bit-identical to the tile kernel, test_gpu_tri_mul_tail_as.py);
+    // tune bit 14 forces the kernel on an eligible shape of any size
+    if (!(g.tune & 16384) && ntm * g.batch < 1024) return 1;
+    if (int e = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm_as_dual_kernel), AD_LDS, "abx_gemm(as, dual)")) {
+        *rc = e;
+        return 0;
+    }
+    hipLaunchKernelGGL(gemm_as_dual_kernel, dim3((unsigned)(ntm * g.batch)), dim3(256), AD_LDS, st, g);
+    *rc = abx_check_launch("abx_gemm(as, dual)");
+    return 0;
+}
+
 }  // namespace
 
 // Called by abx_gemm / abx_gemm_side (gemm.hip) with validated descriptors (vector flags filled).  side == nullptr: no side GEMM.
@@ -690,6 +1079,7 @@ int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, 
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     static const bool off = getenv("ABX_NO_GEMM_AS") != nullptr;          // (A / B measurements: always the tile kernels)
     if (off || (g.tune & 2048)) return 1;                       // tune bit 11: the tile kernels for this call
+    if (g.A2) return side ? 1 : as_dual_dispatch(g, st, rc);    // the TriangleMultiplication tail
     if (g.exact == 1 || !g.B_split || !g.b_f16 || g.A_split || !g.A || g.sAk != 1 || g.K != AS_NK * 16) return 1;
     if (g.A2 || g.out_ln_w || g.mlp || g.ln_stats || g.gate || g.resid || g.batch_inner || !g.ln_csum || !g.bias) return 1;
     if (g.act != 0 || g.alpha != 1.0f) return 1;

@@ -91,6 +91,12 @@ def gemm_kernel_name(M, N, K, batch, a_kcontig=True, b_ncontig=True, transposed=
     csrc/gemm3.hip); used by bench.py to aggregate per KERNEL exactly like `rocprofv3 --stats` does."""
     b = lambda x: 'true' if x else 'false'
     if dual:
+        # the tri-mul tail (K2 = 192 gate rows next to the K = 128 channel-major product): from 1 024 blocks of 64 rows on the A-stationary
+        # dual kernel of csrc/gemm_as.hip (mirror of as_dual_dispatch; GEMM_TUNE bit 11 keeps the tile kernel, bit 14 forces the new one)
+        tune = GEMM_TUNE or 0
+        if (not GEMM_EXACT and int(exact or 0) != 1 and not (tune & 2048) and N == 192 and K == 128 and not a_kcontig and M % 4 == 0
+                and not transposed and split and (((M + 63) // 64) * batch >= 1024 or (tune & 16384))):
+            return 'gemm_as_dual_kernel'
         return 'gemm3_dual_kernel<128, 96, 32, 96, 3>'
     if out_ln:
         return 'gemm3_oln_kernel<128, 128, 32, 128, 4>'

@@ -162,7 +162,13 @@ typedef struct AbxGemm {
                                                       independent of the batch size fix the arithmetic per op with 1 or 2 */
     /* float16 weight planes: see "Split-f16 operands" above.  b_exp / b2_exp: exponents of B_split / B2_split (|.| <= 100) */
     int b_f16, b_exp, b2_exp;
-    int tune;                                      /* 0 = library default; kernel-variant selector for benchmarking */
+    int tune;                                      /* 0 = library default; kernel-variant selector for benchmarking.  Bit 11 (2048): the tile
+                                                      kernels of gemm3.hip for this call, never an A-stationary kernel of gemm_as.hip.
+                                                      Bit 14 (16384): the dual descriptor of the TriangleMultiplication tail (A2, K = 128
+                                                      channel-major, K2 = 192, N = 192, out of place) takes gemm_as_dual_kernel also below its
+                                                      launch-size threshold of 1 024 blocks of 64 rows (tests; the results are bit-identical to
+                                                      the tile kernel's either way).  Environment: ABX_NO_DUAL_AS set and not "0" keeps
+                                                      gemm3_dual_kernel for every dual descriptor of the process (A / B measurements) */
     int c_planes_from, c_planes_group;             /* plain store, c_planes_from > 0: the output columns n >= c_planes_from leave as the B-side
                                                       OPERAND IMAGE of a following split-f16 product instead of fp32 - two float16 planes of
                                                       16 x value (p0 = f16(x'), p1 = f16(x' - p0): the same 4 bytes per element) in groups of

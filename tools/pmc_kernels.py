@@ -4,7 +4,8 @@
 which: qkvg (LN -> 768, gemm3 128x128 tiles: tune 2048)  qkv (round 5: LN -> q | k | v 576 + pair-bias side, A-stationary kernel)
        gtail (gated tail of the triangle attention, AbxGemm.mlp = 2)  mlp (fused transition)  trans2 (768 -> 192 + resid, gemm3 128x192)  glu (LN -> glu planes, transposed store)
        contract (plane x plane)  projout (channel-major A, gate, resid)  tri (triangle attention)  ipa (IPA attention)
-       trif / trif1 (row-fused triangle attention on the z rows, slot order (b, row, h) / (b, h, row))  pairbias (the 4-column pair-bias projection alone)"""
+       trif / trif1 (row-fused triangle attention on the z rows, slot order (b, row, h) / (b, h, row))  pairbias (the 4-column pair-bias projection alone)
+       dualas / dualtile (the tri-mul tail as a dual GEMM: the A-stationary kernel forced, tune 16384 / the 128 x 96 tile kernel, tune 2048)"""
 import os
 import sys
 
@@ -85,6 +86,13 @@ elif which == 'pairbias':
     bT, bp, csp, Wp3 = torch.empty(Bc, 4, LL, device=DEV), r(4), Wp.sum(0).contiguous(), ops.split_weights(Wp)
     for _ in range(REPS):
         ops.gemm(z, Wp, bT.transpose(1, 2), bias=bp, ln=(None, csp), B3=Wp3, exact=2, alpha=ops.TRI_BIAS_LOG2)
+elif which in ('dualas', 'dualtile'):
+    tt, z, out = r(Bc, 128, LL), r(Bc, LL, 192), torch.empty(Bc, LL, 192, device=DEV)
+    Wo, Wg = r(128, 192) / 11, r(192, 192) / 14
+    Wo3, Wg3 = ops.split_weights(Wo), ops.split_weights(Wg)
+    for _ in range(REPS):
+        ops.gemm(tt.transpose(1, 2), Wo, out, bias=r(192), ln=(None, Wo.sum(0).contiguous()), B3=Wo3, resid=z,
+                 dual=(z, Wg3, Wg.sum(0).contiguous(), r(192)), exact=2, tune=16384 if which == 'dualas' else 2048)
 elif which == 'ipa':
     M1 = Bc * L
     qp, kp, vp = r(ops.ipa_qpack_numel(Bc, L)), r(M1 * 12 * 28), r(M1 * 12 * 40)
