@@ -270,6 +270,26 @@ class AbxEnsembleClusterArgs(C.Structure):
     ]
 
 
+DISTO_CHANNELS, DISTO_BINS, DISTO_COLS, DISTO_ROWSUMS = 192, 64, 10, 10     # ABX_DISTO_*
+DISTO_ANTIBODY, DISTO_ANTIGEN, DISTO_DESIGNED = 1, 2, 4
+
+
+class AbxDistogramArgs(C.Structure):
+    _fields_ = [
+        ('z', c_f),
+        ('W', c_f), ('bias', c_f),
+        ('breaks', c_f), ('sq_breaks', c_f), ('num_breaks', I),
+        ('pb', c_f),
+        ('classes', c_f), ('valid', c_f),
+        ('cutoff', F),
+        ('table', c_f), ('table_stride', LL),
+        ('rows', c_f),
+        ('p_contact', c_f), ('exp_dist', c_f),
+        ('rowsums', c_f),
+        ('B', I), ('L', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -331,6 +351,8 @@ _PROTOS = {
     'abx_ensemble_pairs_workspace_bytes': (LL, [I, I]),
     'abx_ensemble_pairs': (I, [C.POINTER(AbxEnsemblePairsArgs), c_f, _S]),
     'abx_ensemble_cluster': (I, [C.POINTER(AbxEnsembleClusterArgs), _S]),
+    'abx_distogram_scores': (I, [C.POINTER(AbxDistogramArgs), _S]),
+    'abx_distogram_logits': (I, [C.POINTER(AbxDistogramArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

@@ -47,6 +47,14 @@ fields.  <output_dir>/<complex>_ensemble.tsv holds an `all` line (clusters, uniq
 and one line per sample: ensemble.ENSEMBLE_COLUMNS and `representative`, the sample id of the centre of the sample's cluster - the few
 files worth the expensive evaluation.  --ensemble_matrix also writes <complex>_ensemble_rmsd.npy, the (3, N, N) planes rmsd_fit,
 rmsd_frame, seq_diff.  With --relax the analysis still describes the designs as written.  No other output file changes.
+--confidence: every design gets its confidence row on the GPU right after the last network call (abx_amd.confidence.DistogramScorer,
+abx_distogram_scores): the checkpoint's distogram head on the pair representation of that call - the network's own distribution over
+every pseudo-beta distance - against the structure it emitted.  <output_dir>/<complex>_confidence.tsv holds a `wild` line (the input
+complex's own coordinates against the same predictions, the mean over the designs), one line per sample: confidence.CONFIDENCE_COLUMNS,
+then delta_<column> = design minus the wild type under the SAME design's prediction for confidence.DELTA_COLUMNS and, with --relax, the
+columns of the relaxed structure suffixed _relaxed (nan on the wild line).  --confidence_planes also writes
+<complex>_confidence_contacts.npy, the mean predicted contact probability over the designs, (L, L) (sample-sharded runs only: the planes
+of a set-level schedule would travel as 8 L^2 bytes per sample).  No other output file changes.
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -157,6 +165,25 @@ def _write_interface(out_dir, cname, wild, rows, relaxed):
     return tsv
 
 
+def _write_confidence(out_dir, cname, rows, relaxed):
+    """<out_dir>/<complex>_confidence.tsv: the `wild` line, then (sample id, values) per sample; values = the confidence.CONFIDENCE_COLUMNS
+    row, when relaxed the row of the relaxed structure, and last the sample's own wild row (the input complex's coordinates against the
+    sample's prediction).  wild line: the mean of the wild rows.  After the columns: delta_<column> = row minus the sample's wild row."""
+    from .confidence import CONFIDENCE_COLUMNS, DELTA_COLUMNS, format_confidence, format_delta
+    NC = len(CONFIDENCE_COLUMNS)
+    tsv = os.path.join(out_dir, f'{cname}_confidence.tsv')
+    wilds = [v[len(v) - NC:] for _, v in rows]
+    wild = [sum(w[k] for w in wilds) / max(len(wilds), 1) for k in range(NC)]
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(CONFIDENCE_COLUMNS + tuple('delta_' + c for c in DELTA_COLUMNS) +
+                                       (tuple(c + '_relaxed' for c in CONFIDENCE_COLUMNS) if relaxed else ())) + '\n')
+        f.write('wild\t' + '\t'.join(format_confidence(wild) + format_delta(wild, wild) + (['nan'] * NC if relaxed else [])) + '\n')
+        for (i, v), w in zip(rows, wilds):
+            f.write(f'{i}\t' + '\t'.join(format_confidence(v[:NC]) + format_delta(v[:NC], w) +
+                                          (format_confidence(v[NC:2 * NC]) if relaxed else [])) + '\n')
+    return tsv
+
+
 def _write_ensemble(out_dir, cname, summ, rows, centres):
     """<out_dir>/<complex>_ensemble.tsv: the `all` line, then (sample id, ensemble.ENSEMBLE_COLUMNS values) per sample in row order.
     summ: ensemble.summary of the table; centres: the rows' positions of the cluster centres in order of discovery.  Columns: the row,
@@ -238,6 +265,12 @@ def build_parser():
     ap.add_argument('--interface_points', type=int, default=128, help='--interface: sphere points per atom (1..1024)')
     ap.add_argument('--interface_probe', type=float, default=1.4, help='--interface: probe radius (Angstrom)')
     ap.add_argument('--interface_cutoff', type=float, default=4.0, help='--interface: heavy-atom contact distance (Angstrom)')
+    ap.add_argument('--confidence', action='store_true', help='confidence row of every design on the GPU (abx_distogram_scores): the distogram '
+                    'head of the last network call against the emitted structure - negative log-likelihood of the realised distances, entropy, '
+                    'expected and realised antigen contacts of the designed residues; writes <complex>_confidence.tsv')
+    ap.add_argument('--confidence_cutoff', type=float, default=8.0, help='--confidence: contact distance of the pseudo-beta atoms (Angstrom)')
+    ap.add_argument('--confidence_planes', action='store_true', help='--confidence: also write <complex>_confidence_contacts.npy, the mean '
+                    'predicted contact probability over the designs, (L, L)')
     ap.add_argument('--ensemble', action='store_true', help='compare the designs of a complex with each other on the GPU (abx_ensemble_pairs, '
                     'abx_ensemble_cluster): pairwise RMSD of the designed residues, Daura clusters and their centres; writes <complex>_ensemble.tsv')
     ap.add_argument('--ensemble_cutoff', type=float, default=1.0, help='--ensemble: neighbour distance of the clusters (Angstrom)')
@@ -384,6 +417,16 @@ def main(argv=None):
         if not 1 <= a.interface_points <= 1024 or a.interface_probe < 0 or a.interface_cutoff <= 0:
             raise SystemExit('--interface_points must be in 1..1024, --interface_probe >= 0, --interface_cutoff > 0')
         NI = len(INTERFACE_COLUMNS) * (3 if a.relax else 2)
+    NCF = 0                                                     # --confidence: the row (+ that of the relaxed structure) + the sample's wild row
+    if a.confidence:
+        from .confidence import CONFIDENCE_COLUMNS, DistogramScorer
+        if not a.confidence_cutoff > 0:
+            raise SystemExit('--confidence_cutoff must be > 0')
+        if a.confidence_planes and plan is not None:
+            raise SystemExit('--confidence_planes needs the sample-sharded schedule (--shard_samples): a set-level run gathers one table only')
+        NCF = len(CONFIDENCE_COLUMNS) * (3 if a.relax else 2)
+    elif a.confidence_planes:
+        raise SystemExit('--confidence_planes needs --confidence')
     NE = 0                                                      # --ensemble, set-level rows: the antibody backbone (maxLab, 4, 3), f32 values
     analyzers = {}                                              # --ensemble: job -> EnsembleAnalyzer (the compared rows of the complex)
     if a.ensemble:
@@ -392,7 +435,7 @@ def main(argv=None):
             raise SystemExit(f'--ensemble compares 1..{ensemble.MAX_N} samples of a complex, --ensemble_cutoff must be >= 0')
         NE = 12 * maxLab
     E0 = 4 + maxLab + NS + n_rec * (1 + NS)                     # set-level rows: the backbone columns follow the scores
-    WIDTH = E0 + NE + NR + NI
+    WIDTH = E0 + NE + NCF + NR + NI                             # (the confidence columns sit between the backbone and the relax report)
 
     def analyze_ensemble(ji, out_dir, cname, ids, seq, backbone):
         """The ensemble tables of job ji from the gathered tokens (N, Lab) and backbone (N, Lab, 4, 3) in the order of `ids`."""
@@ -457,6 +500,10 @@ def main(argv=None):
             diffuser.seed = a.seed
             writer = TrajectoryWriter(meta, out_dir, multi=a.mode == 'trajectory')
             iface = InterfaceScorer(batch, n_points=a.interface_points, probe=a.interface_probe, cutoff=a.interface_cutoff) if a.interface else None
+            conf = None
+            if a.confidence:
+                conf = DistogramScorer(batch, model, cutoff=a.confidence_cutoff, conf=cfg.model.heads.distogram)
+                conf.want_planes = a.confidence_planes
             if a.ensemble and ji not in analyzers:
                 analyzers[ji] = ensemble.EnsembleAnalyzer(batch, atoms=a.ensemble_atoms, metric=a.ensemble_metric, cutoff=a.ensemble_cutoff)
             torch.cuda.synchronize()
@@ -466,7 +513,8 @@ def main(argv=None):
                                      **({'scorer': DesignScorer(batch)} if a.score else {}),
                                      **({'relaxer': ViolationRelaxer(batch, flank=a.relax_flank, max_iter=a.relax_iters,
                                                                      k_restraint=a.relax_restraint)} if a.relax else {}),
-                                     **({'interface': iface} if a.interface else {}))
+                                     **({'interface': iface} if a.interface else {}),
+                                     **({'confidence': conf} if a.confidence else {}))
             torch.cuda.synchronize()
             t_samp = time.perf_counter()
             new_files = writer.close()
@@ -492,6 +540,11 @@ def main(argv=None):
             if a.interface:                                     # the wild type's row rides along in every row: any rank can write the table
                 local['interface'] = torch.cat([traj[-1]['interface']] + ([traj[-1]['interface_relaxed']] if a.relax else []) +
                                                [iface.wild().expand(n, -1)], 1)
+            if a.confidence:                                    # every sample's own wild row rides along: any rank can write the table
+                local['confidence'] = torch.cat([traj[-1]['confidence']] + ([traj[-1]['confidence_relaxed']] if a.relax else []) +
+                                                [traj[-1]['confidence_wild']], 1)
+                if a.confidence_planes:
+                    local['confidence_contacts'] = traj[-1]['confidence_planes'][0]
             if a.ensemble:                                      # N, CA, C, O of the antibody rows: what the comparison reads
                 local['backbone'] = traj[-1]['atom14_results'][:, :, :4].float().contiguous()
         else:                                                   # more ranks than samples: join the gather with zero-row blocks
@@ -504,6 +557,10 @@ def main(argv=None):
                 local['relax'] = torch.zeros(0, NR, dtype=torch.float64, device=dev)
             if a.interface:
                 local['interface'] = torch.zeros(0, NI, dtype=torch.float64, device=dev)
+            if a.confidence:
+                local['confidence'] = torch.zeros(0, NCF, dtype=torch.float64, device=dev)
+                if a.confidence_planes:
+                    local['confidence_contacts'] = torch.zeros(0, L, L, dtype=torch.float32, device=dev)
             if a.ensemble:
                 local['backbone'] = torch.zeros(0, Lab, 4, 3, dtype=torch.float32, device=dev)
         if plan is not None:
@@ -517,6 +574,8 @@ def main(argv=None):
                     row[:, 4 + maxLab + NS:4 + maxLab + NS + n_rec * (1 + NS)] = local['traj_scores'].reshape(n, -1).cpu()
             if a.ensemble:                                      # f32 values are exact in float64
                 row[:, E0:E0 + 12 * Lab] = local['backbone'].reshape(n, -1).double().cpu()
+            if a.confidence:
+                row[:, E0 + NE:E0 + NE + NCF] = local['confidence'].cpu()
             if a.relax:
                 row[:, row.shape[1] - NI - NR:row.shape[1] - NI] = local['relax'].cpu()
             if a.interface:
@@ -537,6 +596,12 @@ def main(argv=None):
             if a.interface:
                 it = res['interface'].tolist()
                 files.append(_write_interface(out_dir, cname, it[0][NI - len(INTERFACE_COLUMNS):], list(enumerate(it)), a.relax))
+            if a.confidence:
+                files.append(_write_confidence(out_dir, cname, list(enumerate(res['confidence'].tolist())), a.relax))
+                if a.confidence_planes:
+                    import numpy as np
+                    files.append(os.path.join(out_dir, f'{cname}_confidence_contacts.npy'))
+                    np.save(files[-1], res['confidence_contacts'].double().mean(0).float().cpu().numpy())
             if a.ensemble:
                 files += analyze_ensemble(ji, out_dir, cname, list(range(N)), res['seq'], res['backbone'])
     if plan is not None:
@@ -562,6 +627,8 @@ def main(argv=None):
                 if a.interface:
                     files.append(_write_interface(jobs[ji][2], load_job(ji)['cname'], rows[0, rows.shape[1] - len(INTERFACE_COLUMNS):].tolist(),
                                                   [(int(r[1]), r[r.shape[0] - NI:].tolist()) for r in rows], a.relax))
+                if a.confidence:
+                    files.append(_write_confidence(jobs[ji][2], load_job(ji)['cname'], [(int(r[1]), r[E0 + NE:E0 + NE + NCF].tolist()) for r in rows], a.relax))
                 if a.ensemble:
                     lab = int(rows[0, 3])
                     files += analyze_ensemble(ji, jobs[ji][2], load_job(ji)['cname'], [int(r[1]) for r in rows], rows[:, 4:4 + lab].long(),

@@ -3,7 +3,8 @@
 Follows the reference's ScoreNetworkIteration.forward (abx/model/abx.py:42-63): EmbeddingAndSeqformer
 (abx/model/seqformer.py:170-226, block :569-606) -> IpaScore (abx/model/score_network.py:83-196) -> SequenceHead
 (abx/model/head.py:162-201) -> PredictedLDDTHead (:222-226), plus get_prev's distogram (abx/model/abx.py:17-26).
-Distogram / metric / TM-score heads are not computed (unused by sampling).
+Metric / TM-score heads are not computed (unused by sampling); the distogram head is not part of a pass either: it
+is evaluated on request from the returned pair representation (abx_amd.confidence.DistogramScorer, abx_distogram_scores).
 
 Memory plan for B samples of one complex (fp32): two ping-pong (B,L,L,192) pair representations (the previous one is the
 self-conditioning input), and a per-chunk workspace of L^2 * 1187 floats per sample that is reused by every stage.

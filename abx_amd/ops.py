@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxDistogramArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1297,3 +1297,78 @@ def ensemble_cluster(planes, metric=0, cutoff=1.0, out=None):
     a.centres, a.n_clusters, a.N = _p(centres), _p(n_clusters), N
     check(lib.abx_ensemble_cluster(C.byref(a), _stream()), 'abx_ensemble_cluster')
     return out, centres, n_clusters
+
+
+def distogram_pack_weight(weight):
+    """impl.distogram.proj.weight (64, 192) -> the MFMA B-fragment image abx_distogram_* read (include/abx_hip.h, AbxDistogramArgs.W):
+    out[k // 4][n // 16][k % 4][n % 16] = weight[n][k], (12288,) fp32 contiguous on the weight's device.  Packed once per scorer."""
+    N, K = _lib.DISTO_BINS, _lib.DISTO_CHANNELS
+    assert tuple(weight.shape) == (N, K), weight.shape
+    return weight.detach().to(torch.float32).t().reshape(K // 4, 4, N // 16, 16).permute(0, 2, 1, 3).contiguous().reshape(-1)
+
+
+def _distogram_common(a, z, w_packed, bias, keep):
+    B, L = z.shape[0], z.shape[1]
+    assert z.dim() == 4 and z.shape[2] == L and z.shape[3] == _lib.DISTO_CHANNELS, z.shape
+    z = _f32(z)
+    if not z.is_contiguous():
+        z = z.contiguous()
+    assert w_packed.dtype == torch.float32 and w_packed.numel() == _lib.DISTO_BINS * _lib.DISTO_CHANNELS and w_packed.is_contiguous(), \
+        'w_packed: ops.distogram_pack_weight(weight)'
+    bias = bias.detach().to(torch.float32).contiguous()
+    assert bias.numel() == _lib.DISTO_BINS, bias.shape
+    keep += [z, bias]
+    a.z, a.W, a.bias, a.B, a.L = _p(z), _p(w_packed), _p(bias), B, L
+    return B, L
+
+
+def distogram_scores(z, w_packed, bias, breaks, sq_breaks, pb, classes, valid, cutoff=8.0, table=None, rows=True, planes=False):
+    """Confidence of B designs from the distogram head (abx_distogram_scores; columns: abx_amd.confidence.CONFIDENCE_COLUMNS).
+    z (B,L,L,192) f32 pair representation, w_packed = distogram_pack_weight(weight), bias (64), breaks / sq_breaks (63) f32,
+    pb (B,L,3) f32 pseudo-beta coordinates, classes (L) uint8 class bits, valid (B,L) bool / uint8, all on z's device.
+    -> (table (B,10) float64, rows (B,L,4) float64 or None, (p_contact, exp_dist) (B,L,L) f32 or None).  table: rows to write into
+    (unit column stride, any row stride) or None.  Two launches, no synchronisation; the logits never exist in memory."""
+    lib = _lib.load()
+    dev = z.device
+    keep = []
+    a = AbxDistogramArgs()
+    B, L = _distogram_common(a, z, w_packed, bias, keep)
+
+    def own(t, dtype, shape):
+        assert tuple(t.shape) == shape, (tuple(t.shape), shape)
+        t = t.to(dtype).contiguous()
+        keep.append(t)
+        return _p(t)
+
+    nb = _lib.DISTO_BINS - 1
+    a.breaks, a.sq_breaks, a.num_breaks = own(breaks, torch.float32, (nb,)), own(sq_breaks, torch.float32, (nb,)), nb
+    a.pb = own(pb, torch.float32, (B, L, 3))
+    a.classes, a.valid = own(classes, torch.uint8, (L,)), own(valid.ne(0), torch.uint8, (B, L))
+    a.cutoff = float(cutoff)
+    if table is None:
+        table = torch.empty(B, _lib.DISTO_COLS, dtype=torch.float64, device=dev)
+    assert table.dtype == torch.float64 and tuple(table.shape) == (B, _lib.DISTO_COLS) and table.stride(1) == 1 and table.is_cuda, \
+        'table: (B, 10) float64 rows'
+    a.table, a.table_stride = _p(table), table.stride(0) if B > 1 else _lib.DISTO_COLS
+    rows_t = torch.empty(B, L, 4, dtype=torch.float64, device=dev) if rows else None
+    a.rows = _p(rows_t)
+    pl = None
+    if planes:
+        pl = (torch.empty(B, L, L, device=dev), torch.empty(B, L, L, device=dev))
+        a.p_contact, a.exp_dist = _p(pl[0]), _p(pl[1])
+    ws = torch.empty(B, L, _lib.DISTO_ROWSUMS, dtype=torch.float64, device=dev)
+    a.rowsums = _p(ws)
+    check(lib.abx_distogram_scores(C.byref(a), _stream()), 'abx_distogram_scores')
+    return table, rows_t, pl
+
+
+def distogram_logits(z, w_packed, bias):
+    """The reference's heads['distogram']['logits'] (head.py:39-44) of n designs: z (n,L,L,192) f32 -> (n,L,L,64) f32, by the kernel
+    body whose values distogram_scores reduces (abx_distogram_logits: the same bits).  One launch, no synchronisation."""
+    lib = _lib.load()
+    keep = []
+    a = AbxDistogramArgs()
+    B, L = _distogram_common(a, z, w_packed, bias, keep)
+    out = torch.empty(B, L, L, _lib.DISTO_BINS, device=z.device)
+    check(lib.abx_distogram_logits(C.byref(a), _p(out), _stream()), 'abx_distogram_logits')
+    return out

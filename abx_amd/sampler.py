@@ -24,7 +24,7 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None, relaxer=None, interface=None):
+              scorer=None, relaxer=None, interface=None, confidence=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -40,7 +40,13 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     'scores_relaxed'; 'atom14_results' is left as it is.  One launch, outside any captured step, no host synchronisation.
     interface: None, or an abx_amd.interface.InterfaceScorer of the complex: the LAST record gets 'interface' (B, len(interface.
     INTERFACE_COLUMNS)) float64 - buried surface, interface residues, antibody-antigen contacts of the designs - and with a relaxer
-    'interface_relaxed' of the relaxed structures.  Three launches each, outside any captured step, no host synchronisation."""
+    'interface_relaxed' of the relaxed structures.  Three launches each, outside any captured step, no host synchronisation.
+    confidence: None, or an abx_amd.confidence.DistogramScorer of the complex: the LAST record (in trajectory mode too) gets 'confidence'
+    (B, len(confidence.CONFIDENCE_COLUMNS)) float64 and 'confidence_rows' (B, L, 4) - the distogram head of the last network call
+    against the designs it emitted - 'confidence_wild' (the input complex's own coordinates against the same predictions), with a
+    relaxer 'confidence_relaxed', and with `confidence.want_planes` 'confidence_planes' = (p_contact, exp_dist).  The scorer reads
+    out['representations']['pair'] right after the last model call (the next call overwrites that buffer: model/abx.py:16-18); two
+    launches per table, outside any captured step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -113,6 +119,15 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                     traj[-1]['interface'] = interface.score(traj[-1]['atom14_results'], traj[-1]['seq'])
                     if relaxer is not None:
                         traj[-1]['interface_relaxed'] = interface.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'])
+                if confidence is not None and k == len(steps) - 1:
+                    pair = out['representations']['pair']       # of the call just made: nothing between it and here runs the network
+                    got = confidence.score(pair, traj[-1]['atom14_results'], traj[-1]['seq'], planes=bool(getattr(confidence, 'want_planes', False)))
+                    traj[-1]['confidence'], traj[-1]['confidence_rows'] = got[0], got[1]
+                    if len(got) > 2:
+                        traj[-1]['confidence_planes'] = got[2]
+                    traj[-1]['confidence_wild'] = confidence.wild(pair)[0]
+                    if relaxer is not None:
+                        traj[-1]['confidence_relaxed'] = confidence.score(pair, traj[-1]['atom14_relaxed'], traj[-1]['seq'])[0]
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)

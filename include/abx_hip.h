@@ -737,6 +737,62 @@ typedef struct AbxEnsembleClusterArgs {
 int abx_ensemble_cluster(const AbxEnsembleClusterArgs* a, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Distogram head of designs: what the network's own pair representation predicts about a design (abx/model/head.py:26-44,
+ * DistogramHead.forward: x = proj(pair), logits = 0.5 (x + x^T); head.py:99-102, MetricDictHead: pred = sum softmax(logits)[..., :t+1]
+ * with t = #{breaks <= cutoff}).  The projection is linear, so the OPERAND is symmetrised: zs[i][j] = 0.5f * (z[i][j] + z[j][i]) in fp32
+ * (commutative: (i, j) and (j, i) hold equal bits), logits[i][j] = zs[i][j] W + b by the exact fp32 MFMA, k ascending.
+ * z (B, L, L, ABX_DISTO_CHANNELS) fp32 contiguous, 16-byte aligned (representations['pair'] of a network call).
+ * W: impl.distogram.proj.weight [64][192] packed once by the caller into MFMA B fragments, 16-byte aligned:
+ *   W[(((k / 4) * 4 + n / 16) * 4 + k % 4) * 16 + n % 16] = weight[n][k]   (abx_amd.ops.distogram_pack_weight)
+ * bias [64].  breaks [num_breaks = 63] ascending (linspace(first_break, last_break, 63)), sq_breaks their fp32 squares (host).
+ *
+ * abx_distogram_scores.  pb (B, L, 3) fp32 pseudo-beta coordinates of the designs; classes (L) bytes shared by the batch
+ * (ABX_DISTO_ANTIBODY | ABX_DISTO_ANTIGEN | ABX_DISTO_DESIGNED); valid (B, L) bytes; cutoff (8.0).  Per ordered pair i != j of valid rows:
+ *   d2 = (dx*dx + dy*dy) + dz*dz, dx = pb_i.x - pb_j.x, ... in fp32, every operation rounded on its own (the order of abx_prev_pos)
+ *   bin_real = sum_k (d2 > sq_breaks[k]);  realised contact: d2 < cutoff * cutoff (fp32)
+ *   p = softmax(logits) with max subtraction: e_k = expf(l_k - max) (the difference exact in float64, rounded to fp32 for expf),
+ *   every sum after it in float64.  nll = -ln p[bin_real];  entropy = -sum p ln p;  p_contact as above;
+ *   E[d] = sum p_k c_k, c_k = midpoint of bin k (breaks[k-1], breaks[k]], the two open end bins extended by half a step.
+ * table: ABX_DISTO_COLS doubles per design (row stride table_stride; abx_amd.confidence.CONFIDENCE_COLUMNS), an empty set gives 0:
+ *   0 nll_all               mean nll, all pairs                    5 entropy_region               mean entropy, i designed
+ *   1 nll_antibody_antigen  i antibody, j antigen                  6 exp_contacts_region_antigen  sum p_contact, i designed, j antigen
+ *   2 nll_region            i designed                             7 n_contacts_region_antigen    realised contacts in that set
+ *   3 nll_region_antigen    i designed, j antigen                  8 p_on_contacts_region_antigen mean p_contact over those contacts
+ *   4 dist_err_region       mean |E[d] - sqrt(d2)|, i designed,    9 n_pairs_region               pairs with i designed
+ *                           bin_real < 63 (d within the last break)
+ * rows: optional (B, L, 4) doubles per residue i: mean nll over its valid partners, sum_{j antigen} p_contact, realised antigen
+ * contacts, mean entropy.  p_contact / exp_dist: optional (B, L, L) fp32 planes of every pair (validity not applied), exactly
+ * symmetric.  rowsums: caller scratch of B * L * ABX_DISTO_ROWSUMS doubles, fully written by the first launch before the second
+ * reads it.  Two launches: grid (L, B), a workgroup walks the j tiles of its row in ascending order (per-row float64 sums in tile
+ * order, then lane order); one wave per design sums the rows in ascending i.  No atomics, no allocation, no synchronisation: the
+ * bits of a design depend on neither B nor its place in the batch.
+ *
+ * abx_distogram_logits.  The same kernel body stores the logits (B, L, L, 64) fp32 instead of reducing them (the reference's
+ * heads['distogram']['logits']; 4 * B * L * L * 64 bytes: for a few designs, not for a batch).  Reads z, W, bias, B, L only. */
+#define ABX_DISTO_CHANNELS 192
+#define ABX_DISTO_BINS 64
+#define ABX_DISTO_COLS 10
+#define ABX_DISTO_ROWSUMS 10
+#define ABX_DISTO_ANTIBODY 1
+#define ABX_DISTO_ANTIGEN 2
+#define ABX_DISTO_DESIGNED 4
+typedef struct AbxDistogramArgs {
+    const float* z;
+    const float* W; const float* bias;
+    const float* breaks; const float* sq_breaks; int num_breaks;
+    const float* pb;
+    const unsigned char* classes; const unsigned char* valid;
+    float cutoff;
+    double* table; long long table_stride;
+    double* rows;                                   /* optional (B,L,4) */
+    float* p_contact; float* exp_dist;              /* optional (B,L,L) */
+    double* rowsums;                                /* scratch (B,L,ABX_DISTO_ROWSUMS) */
+    int B, L;
+} AbxDistogramArgs;
+int abx_distogram_scores(const AbxDistogramArgs* a, hipStream_t stream);
+int abx_distogram_logits(const AbxDistogramArgs* a, float* logits, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
