@@ -290,6 +290,25 @@ class AbxDistogramArgs(C.Structure):
     ]
 
 
+ACC_COLS = 21             # ABX_ACC_COLS
+
+
+class AbxAccuracyArgs(C.Structure):
+    _fields_ = [
+        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
+        ('pred_seq', c_f), ('pred_seq_sb', LL),
+        ('pred_mask', c_f), ('res_mask', c_f),
+        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+        ('region', c_f),
+        ('radius', c_f),
+        ('plddt', c_f), ('plddt_sb', LL),
+        ('lddt_radius', C.c_double), ('contact', C.c_double),
+        ('out', c_f), ('out_stride', LL),
+        ('rows', c_f), ('counts', c_f), ('contacts', c_f),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -353,6 +372,8 @@ _PROTOS = {
     'abx_ensemble_cluster': (I, [C.POINTER(AbxEnsembleClusterArgs), _S]),
     'abx_distogram_scores': (I, [C.POINTER(AbxDistogramArgs), _S]),
     'abx_distogram_logits': (I, [C.POINTER(AbxDistogramArgs), c_f, _S]),
+    'abx_accuracy_scores_workspace_bytes': (LL, [I, I]),
+    'abx_accuracy_scores': (I, [C.POINTER(AbxAccuracyArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

@@ -55,6 +55,14 @@ then delta_<column> = design minus the wild type under the SAME design's predict
 columns of the relaxed structure suffixed _relaxed (nan on the wild line).  --confidence_planes also writes
 <complex>_confidence_contacts.npy, the mean predicted contact probability over the designs, (L, L) (sample-sharded runs only: the planes
 of a set-level schedule would travel as 8 L^2 bytes per sample).  No other output file changes.
+--accuracy: every design is compared with the input crystal structure on the GPU after the last step (abx_amd.accuracy.AccuracyScorer,
+abx_accuracy_scores): all-atom / backbone / C-alpha lDDT (the quantity pLDDT predicts) with the designed residues as the region, the
+calibration of the per-residue pLDDT of the last network call, TM-score / GDT-TS / GDT-HA / RMSD of the C-alpha (upstream's TMscoreHead)
+and the native antibody-antigen residue contacts that survive (DockQ's Fnat).  <output_dir>/<complex>_accuracy.tsv holds a `wild` line
+(the input complex against itself: every lDDT and fnat 1, rmsd_ca 0) and one line per sample: accuracy.ACCURACY_COLUMNS and, with
+--relax, the columns of the relaxed structure suffixed _relaxed (nan on the wild line), then delta_<column> = relaxed minus design for
+accuracy.DELTA_COLUMNS.  --accuracy_rows also writes <complex>_accuracy_rows.npy, the per-residue lDDT (N, L, 4: accuracy.ROW_COLUMNS;
+sample-sharded runs only).  No other output file changes.
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -165,6 +173,22 @@ def _write_interface(out_dir, cname, wild, rows, relaxed):
     return tsv
 
 
+def _write_accuracy(out_dir, cname, wild, rows, relaxed):
+    """<out_dir>/<complex>_accuracy.tsv: the `wild` line, then (sample id, values) per sample; values = the accuracy.ACCURACY_COLUMNS row
+    and, when relaxed, the row of the relaxed structure followed by delta_<column> = relaxed minus design for accuracy.DELTA_COLUMNS."""
+    from .accuracy import ACCURACY_COLUMNS, DELTA_COLUMNS, format_accuracy, format_delta
+    NA = len(ACCURACY_COLUMNS)
+    tsv = os.path.join(out_dir, f'{cname}_accuracy.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(ACCURACY_COLUMNS + ((tuple(c + '_relaxed' for c in ACCURACY_COLUMNS) +
+                                                             tuple('delta_' + c for c in DELTA_COLUMNS)) if relaxed else ())) + '\n')
+        f.write('wild\t' + '\t'.join(format_accuracy(wild) + (['nan'] * (NA + len(DELTA_COLUMNS)) if relaxed else [])) + '\n')
+        for i, v in rows:
+            f.write(f'{i}\t' + '\t'.join(format_accuracy(v[:NA]) +
+                                          ((format_accuracy(v[NA:2 * NA]) + format_delta(v[NA:2 * NA], v[:NA])) if relaxed else [])) + '\n')
+    return tsv
+
+
 def _write_confidence(out_dir, cname, rows, relaxed):
     """<out_dir>/<complex>_confidence.tsv: the `wild` line, then (sample id, values) per sample; values = the confidence.CONFIDENCE_COLUMNS
     row, when relaxed the row of the relaxed structure, and last the sample's own wild row (the input complex's coordinates against the
@@ -271,6 +295,13 @@ def build_parser():
     ap.add_argument('--confidence_cutoff', type=float, default=8.0, help='--confidence: contact distance of the pseudo-beta atoms (Angstrom)')
     ap.add_argument('--confidence_planes', action='store_true', help='--confidence: also write <complex>_confidence_contacts.npy, the mean '
                     'predicted contact probability over the designs, (L, L)')
+    ap.add_argument('--accuracy', action='store_true', help='accuracy row of every design on the GPU (abx_accuracy_scores): lDDT against the '
+                    'input structure and the calibration of pLDDT, TM-score / GDT / RMSD of the C-alpha, native antibody-antigen residue '
+                    'contacts kept (Fnat); writes <complex>_accuracy.tsv')
+    ap.add_argument('--accuracy_radius', type=float, default=15.0, help='--accuracy: lDDT inclusion radius (Angstrom)')
+    ap.add_argument('--accuracy_contact', type=float, default=5.0, help='--accuracy: heavy-atom distance of a residue contact (Angstrom)')
+    ap.add_argument('--accuracy_rows', action='store_true', help='--accuracy: also write <complex>_accuracy_rows.npy, the per-residue lDDT '
+                    '(all atoms, backbone, C-alpha) and pair count of every sample, (N, L, 4)')
     ap.add_argument('--ensemble', action='store_true', help='compare the designs of a complex with each other on the GPU (abx_ensemble_pairs, '
                     'abx_ensemble_cluster): pairwise RMSD of the designed residues, Daura clusters and their centres; writes <complex>_ensemble.tsv')
     ap.add_argument('--ensemble_cutoff', type=float, default=1.0, help='--ensemble: neighbour distance of the clusters (Angstrom)')
@@ -427,6 +458,16 @@ def main(argv=None):
         NCF = len(CONFIDENCE_COLUMNS) * (3 if a.relax else 2)
     elif a.confidence_planes:
         raise SystemExit('--confidence_planes needs --confidence')
+    NA = 0                                                      # --accuracy: the row (+ that of the relaxed structure) + the wild type's row
+    if a.accuracy:
+        from .accuracy import ACCURACY_COLUMNS, AccuracyScorer
+        if not a.accuracy_radius > 0 or not a.accuracy_contact > 0:
+            raise SystemExit('--accuracy_radius and --accuracy_contact must be > 0')
+        if a.accuracy_rows and plan is not None:
+            raise SystemExit('--accuracy_rows needs the sample-sharded schedule (--shard_samples): a set-level run gathers one table only')
+        NA = len(ACCURACY_COLUMNS) * (3 if a.relax else 2)
+    elif a.accuracy_rows:
+        raise SystemExit('--accuracy_rows needs --accuracy')
     NE = 0                                                      # --ensemble, set-level rows: the antibody backbone (maxLab, 4, 3), f32 values
     analyzers = {}                                              # --ensemble: job -> EnsembleAnalyzer (the compared rows of the complex)
     if a.ensemble:
@@ -435,7 +476,7 @@ def main(argv=None):
             raise SystemExit(f'--ensemble compares 1..{ensemble.MAX_N} samples of a complex, --ensemble_cutoff must be >= 0')
         NE = 12 * maxLab
     E0 = 4 + maxLab + NS + n_rec * (1 + NS)                     # set-level rows: the backbone columns follow the scores
-    WIDTH = E0 + NE + NCF + NR + NI                             # (the confidence columns sit between the backbone and the relax report)
+    WIDTH = E0 + NE + NCF + NA + NR + NI                        # (the confidence and accuracy columns sit between the backbone and the relax report)
 
     def analyze_ensemble(ji, out_dir, cname, ids, seq, backbone):
         """The ensemble tables of job ji from the gathered tokens (N, Lab) and backbone (N, Lab, 4, 3) in the order of `ids`."""
@@ -504,6 +545,7 @@ def main(argv=None):
             if a.confidence:
                 conf = DistogramScorer(batch, model, cutoff=a.confidence_cutoff, conf=cfg.model.heads.distogram)
                 conf.want_planes = a.confidence_planes
+            acc = AccuracyScorer(batch, radius=a.accuracy_radius, contact=a.accuracy_contact) if a.accuracy else None
             if a.ensemble and ji not in analyzers:
                 analyzers[ji] = ensemble.EnsembleAnalyzer(batch, atoms=a.ensemble_atoms, metric=a.ensemble_metric, cutoff=a.ensemble_cutoff)
             torch.cuda.synchronize()
@@ -514,7 +556,8 @@ def main(argv=None):
                                      **({'relaxer': ViolationRelaxer(batch, flank=a.relax_flank, max_iter=a.relax_iters,
                                                                      k_restraint=a.relax_restraint)} if a.relax else {}),
                                      **({'interface': iface} if a.interface else {}),
-                                     **({'confidence': conf} if a.confidence else {}))
+                                     **({'confidence': conf} if a.confidence else {}),
+                                     **({'accuracy': acc} if a.accuracy else {}))
             torch.cuda.synchronize()
             t_samp = time.perf_counter()
             new_files = writer.close()
@@ -545,6 +588,11 @@ def main(argv=None):
                                                 [traj[-1]['confidence_wild']], 1)
                 if a.confidence_planes:
                     local['confidence_contacts'] = traj[-1]['confidence_planes'][0]
+            if a.accuracy:                                      # the wild type's row rides along in every row: any rank can write the table
+                local['accuracy'] = torch.cat([traj[-1]['accuracy']] + ([traj[-1]['accuracy_relaxed']] if a.relax else []) +
+                                              [acc.wild().expand(n, -1)], 1)
+                if a.accuracy_rows:
+                    local['accuracy_rows'] = traj[-1]['accuracy_rows']
             if a.ensemble:                                      # N, CA, C, O of the antibody rows: what the comparison reads
                 local['backbone'] = traj[-1]['atom14_results'][:, :, :4].float().contiguous()
         else:                                                   # more ranks than samples: join the gather with zero-row blocks
@@ -561,6 +609,10 @@ def main(argv=None):
                 local['confidence'] = torch.zeros(0, NCF, dtype=torch.float64, device=dev)
                 if a.confidence_planes:
                     local['confidence_contacts'] = torch.zeros(0, L, L, dtype=torch.float32, device=dev)
+            if a.accuracy:
+                local['accuracy'] = torch.zeros(0, NA, dtype=torch.float64, device=dev)
+                if a.accuracy_rows:
+                    local['accuracy_rows'] = torch.zeros(0, L, 4, dtype=torch.float64, device=dev)
             if a.ensemble:
                 local['backbone'] = torch.zeros(0, Lab, 4, 3, dtype=torch.float32, device=dev)
         if plan is not None:
@@ -576,6 +628,8 @@ def main(argv=None):
                 row[:, E0:E0 + 12 * Lab] = local['backbone'].reshape(n, -1).double().cpu()
             if a.confidence:
                 row[:, E0 + NE:E0 + NE + NCF] = local['confidence'].cpu()
+            if a.accuracy:
+                row[:, E0 + NE + NCF:E0 + NE + NCF + NA] = local['accuracy'].cpu()
             if a.relax:
                 row[:, row.shape[1] - NI - NR:row.shape[1] - NI] = local['relax'].cpu()
             if a.interface:
@@ -602,6 +656,13 @@ def main(argv=None):
                     import numpy as np
                     files.append(os.path.join(out_dir, f'{cname}_confidence_contacts.npy'))
                     np.save(files[-1], res['confidence_contacts'].double().mean(0).float().cpu().numpy())
+            if a.accuracy:
+                at = res['accuracy'].tolist()
+                files.append(_write_accuracy(out_dir, cname, at[0][NA - len(ACCURACY_COLUMNS):], list(enumerate(at)), a.relax))
+                if a.accuracy_rows:
+                    import numpy as np
+                    files.append(os.path.join(out_dir, f'{cname}_accuracy_rows.npy'))
+                    np.save(files[-1], res['accuracy_rows'].cpu().numpy())
             if a.ensemble:
                 files += analyze_ensemble(ji, out_dir, cname, list(range(N)), res['seq'], res['backbone'])
     if plan is not None:
@@ -629,6 +690,10 @@ def main(argv=None):
                                                   [(int(r[1]), r[r.shape[0] - NI:].tolist()) for r in rows], a.relax))
                 if a.confidence:
                     files.append(_write_confidence(jobs[ji][2], load_job(ji)['cname'], [(int(r[1]), r[E0 + NE:E0 + NE + NCF].tolist()) for r in rows], a.relax))
+                if a.accuracy:
+                    A0 = E0 + NE + NCF
+                    files.append(_write_accuracy(jobs[ji][2], load_job(ji)['cname'], rows[0, A0 + NA - len(ACCURACY_COLUMNS):A0 + NA].tolist(),
+                                                 [(int(r[1]), r[A0:A0 + NA].tolist()) for r in rows], a.relax))
                 if a.ensemble:
                     lab = int(rows[0, 3])
                     files += analyze_ensemble(ji, jobs[ji][2], load_job(ji)['cname'], [int(r[1]) for r in rows], rows[:, 4:4 + lab].long(),

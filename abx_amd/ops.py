@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxDistogramArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1244,6 +1244,69 @@ def interface_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, Lab=None
     a.B, a.L, a.Lab = B, L, Lab
     ws = torch.empty(max(int(lib.abx_interface_scores_workspace_bytes(B, L, a.P)), 16), dtype=torch.uint8, device=dev)
     check(lib.abx_interface_scores(C.byref(a), _p(ws), _stream()), 'abx_interface_scores')
+    return out
+
+
+def accuracy_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, Lab=None, region=None, mask=None, res_mask=None, plddt=None, radius=15.0,
+                    contact=5.0, out=None, rows=None, counts=None, contacts=None):
+    """Accuracy of B designs of one complex against its crystal structure (abx_accuracy_scores; columns: abx_amd.accuracy.
+    ACCURACY_COLUMNS): all-atom / backbone / C-alpha lDDT, the pLDDT calibration, TM-score / GDT / RMSD of the C-alpha and the native
+    antibody-antigen residue contacts that survive.
+    atom14 (B,Lp,14,3) f32 with Lp = Lab or L (rows beyond Lp take the ground-truth coordinates; a batch-strided view is read in
+    place), seq (B,>=Lab) int64 tokens; the complex, shared by the batch: gt_atom14 (L,14,3), gt_seq (L), gt_exists (L,14);
+    region (L) bool / uint8 or None; mask (B,L,14) or None (None: the atoms of the residue types); res_mask (L) or None;
+    plddt (B,L) f32 per-residue pLDDT of the call that produced the designs, or None.
+    out: (B, 21) float64 with unit column stride and any row stride, or None; rows (B,L,4) float64, counts (B,L,3,5) int32, contacts
+    (B,Lab,L-Lab) uint8: contiguous tensors to receive the optional outputs, or None.  Two launches, no synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = gt_seq.shape[-1]
+    B, Lp = atom14.shape[0], atom14.shape[1]
+    Lab = int(seq.shape[1] if Lab is None else Lab)
+    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
+    assert tuple(gt_atom14.shape) == (L, 14, 3) and tuple(gt_exists.shape) == (L, 14) and tuple(gt_seq.shape) == (L,), \
+        'complex tensors: (L,...) shared by the batch'
+    x = _f32(atom14)
+    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
+        x = x.contiguous()
+    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
+    keep = [x, sq]
+
+    def own(t, dtype):
+        t = t.to(dtype).contiguous()
+        keep.append(t)
+        return _p(t)
+
+    a = AbxAccuracyArgs()
+    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
+    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
+    if mask is not None:
+        assert tuple(mask.shape) == (B, L, 14), mask.shape
+        a.pred_mask = own(mask, torch.uint8)
+    if res_mask is not None:
+        assert tuple(res_mask.shape) == (L,), res_mask.shape
+        a.res_mask = own(res_mask, torch.uint8)
+    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
+    if region is not None:
+        assert tuple(region.shape) == (L,), region.shape
+        a.region = own(region.ne(0), torch.uint8)
+    a.radius = _p(vdw_radius_table(dev))
+    if plddt is not None:
+        assert tuple(plddt.shape) == (B, L), plddt.shape
+        a.plddt, a.plddt_sb = own(plddt, torch.float32), L
+    a.lddt_radius, a.contact = float(radius), float(contact)
+    if out is None:
+        out = torch.empty(B, _lib.ACC_COLS, dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (B, _lib.ACC_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (B, 21) float64 rows'
+    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else _lib.ACC_COLS
+    for name, t, dtype, shape in (('rows', rows, torch.float64, (B, L, 4)), ('counts', counts, torch.int32, (B, L, 3, 5)),
+                                  ('contacts', contacts, torch.uint8, (B, Lab, L - Lab))):
+        if t is not None:
+            assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.is_cuda, f'{name}: {shape} {dtype}'
+            setattr(a, name, _p(t))
+    a.B, a.L, a.Lab = B, L, Lab
+    ws = torch.empty(max(int(lib.abx_accuracy_scores_workspace_bytes(B, L)), 16), dtype=torch.uint8, device=dev)
+    check(lib.abx_accuracy_scores(C.byref(a), _p(ws), _stream()), 'abx_accuracy_scores')
     return out
 
 

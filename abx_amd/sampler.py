@@ -24,7 +24,7 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None, relaxer=None, interface=None, confidence=None):
+              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -46,7 +46,12 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     against the designs it emitted - 'confidence_wild' (the input complex's own coordinates against the same predictions), with a
     relaxer 'confidence_relaxed', and with `confidence.want_planes` 'confidence_planes' = (p_contact, exp_dist).  The scorer reads
     out['representations']['pair'] right after the last model call (the next call overwrites that buffer: model/abx.py:16-18); two
-    launches per table, outside any captured step, no host synchronisation."""
+    launches per table, outside any captured step, no host synchronisation.
+    accuracy: None, or an abx_amd.accuracy.AccuracyScorer of the complex: the LAST record gets 'accuracy' (B, len(accuracy.
+    ACCURACY_COLUMNS)) float64 - lDDT, TM-score / GDT and native-contact recovery of the designs against the crystal structure, and the
+    calibration of the per-residue pLDDT of the last network call (before it is averaged into the record's 'pLDDT') - 'accuracy_rows'
+    (B, L, 4) per residue, and with a relaxer 'accuracy_relaxed'.  Two launches per table, outside any captured step, no host
+    synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -102,8 +107,8 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 seq_t = out['heads']['sequence_module']['seq_0']
             batch['rigids_t'] = rigids_t
             batch['seq_t'] = seq_t
-            pl = out['heads']['predicted_lddt']['pLDDT']
-            pl = torch.sum(pl * dm_f, dim=1) / torch.sum(dm_f, dim=1)
+            pl_res = out['heads']['predicted_lddt']['pLDDT']
+            pl = torch.sum(pl_res * dm_f, dim=1) / torch.sum(dm_f, dim=1)
             rec = {'seq': torch.clamp(seq_t[:, :Lab], min=0, max=19).long(),
                    'atom14_results': out['heads']['folding']['final_atom14_positions'][:, :Lab],
                    'pLDDT': torch.tile(pl[:, None], (1, Lab)), 'time': float(t), 'rigids_t': rigids_t, 'seq_t': seq_t}
@@ -128,6 +133,10 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                     traj[-1]['confidence_wild'] = confidence.wild(pair)[0]
                     if relaxer is not None:
                         traj[-1]['confidence_relaxed'] = confidence.score(pair, traj[-1]['atom14_relaxed'], traj[-1]['seq'])[0]
+                if accuracy is not None and k == len(steps) - 1:
+                    traj[-1]['accuracy'], traj[-1]['accuracy_rows'] = accuracy.score(traj[-1]['atom14_results'], traj[-1]['seq'], plddt=pl_res, rows=True)[:2]
+                    if relaxer is not None:
+                        traj[-1]['accuracy_relaxed'] = accuracy.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'], plddt=pl_res)
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)

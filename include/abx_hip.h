@@ -793,6 +793,68 @@ int abx_distogram_scores(const AbxDistogramArgs* a, hipStream_t stream);
 int abx_distogram_logits(const AbxDistogramArgs* a, float* logits, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Accuracy of designs against the crystal structure: the lDDT that pLDDT predicts (abx/model/utils.py:102-155, lddt, the target of
+ * predicted_lddt_loss), the TM block of TMscoreHead (abx/model/head.py:116-141; Kabsch, TMscore, GDT of abx/utils.py:562-578,
+ * 525-560, 703-763) and the recovery of the native antibody-antigen residue contacts (DockQ's Fnat).  One row of ABX_ACC_COLS
+ * float64 values per structure of a batch of B designs of ONE complex (abx_amd.accuracy.ACCURACY_COLUMNS).
+ * The design and the complex are given as for abx_design_scores (pred_* rows < Lpred, Lpred = Lab or L, ground truth beyond, residue
+ * types of rows < Lab from pred_seq, clamped to 0..20; pred_mask NULL: the design's rows < Lpred have the atoms of their residue type,
+ * `radius` [21][14] > 0; res_mask = 0 removes a row from both structures; the complex is shared by the B structures).  The wild type
+ * is gt_atom14 / gt_exists / gt_seq.
+ * Scored atoms: slot a of row i when it exists in the wild type and in the design and (the two tokens are equal or a <= 4: N, CA, C,
+ * O, CB): a mutated residue is compared on its backbone and CB.  Atoms related by a side-chain symmetry (Asp OD1 / OD2, the Phe
+ * ring, ...) are NOT renamed: a flipped ring counts as a deviation.
+ * lDDT (Mariani et al. 2013): the ordered pair (p, q) of scored atoms of different rows is included iff d2_wild < radius * radius, and
+ * preserved at t in {0.5, 1, 2, 4} iff fabs(sqrt(d2_wild) - sqrt(d2_design)) < t; all in float64 from the float32 coordinates, without
+ * fused multiply-add:  dx = (double)x_p - (double)x_q;  d2 = (dx*dx + dy*dy) + dz*dz.  Classes: 0 all, 1 bb (both slots <= 4), 2 ca (both
+ * slots == 1: upstream's lddt on the C-alpha).  Per row and class five integers (counts): n_pairs and n_preserved at 0.5, 1, 2, 4,
+ * over the pairs with p in that row.  lDDT of a row = (sum_t n_preserved_t) / (4 n_pairs), NaN without pairs; of a row set the same
+ * with both sums over its rows (pair-pooled, upstream's per_residue=False).
+ * Native contacts: the (antibody row i < Lab, antigen row j >= Lab) pairs with any two existing atoms (of each structure's own
+ * atoms and coordinates; the scored-atom rule does not apply) with d2 < contact * contact: bit 0 in the wild type, bit 1 in the design.
+ * TM block: the rows with a wild-type C-alpha; optimal proper rotation of the centred sets (Horn's quaternion, cyclic Jacobi, float64);
+ * d_i the distances after it, N their number: tm_score = mean 1 / (1 + (d_i / d0)^2), d0 = 1.24 cbrt(max(21, N) - 15) - 1.8;
+ * gdt_ts / gdt_ha = #{(i, c): d_i <= c} / (4 N) over c in {1, 2, 4, 8} / {0.5, 1, 2, 4}; rmsd_ca = sqrt(sum d_i^2 / N).  N = 0: NaN.
+ *   0 lddt_all         all rows                          11 rmsd_ca
+ *   1 lddt_antibody    rows < Lab                        12 n_native           residue pairs with bit 0
+ *   2 lddt_region      rows with region != 0             13 n_kept             with both bits
+ *   3 lddt_bb_region   class bb, region rows             14 fnat               13 / 12, NaN at 0 native
+ *   4 lddt_ca_all      class ca, all rows                15 n_new              with bit 1 only
+ *   5 lddt_ca_region   class ca, region rows             16 n_native_region    columns 12, 13 and 14 over the pairs whose
+ *   6 plddt_region     mean plddt over the region rows   17 n_kept_region      antibody row is a region row
+ *   7 plddt_err_region mean |plddt_i - 100 lDDT-ca_i|    18 fnat_region
+ *                      over the region rows with pairs   19 n_pairs_region     n_pairs of class all over the region rows
+ *   8 tm_score   9 gdt_ts   10 gdt_ha                    20 n_atoms_scored
+ * region: (L) bytes shared by the batch, optional (NULL: no row is a region row); a row removed by res_mask is no region row.
+ * plddt: optional (B, L) fp32 with the row stride plddt_sb (NULL: columns 6 and 7 are NaN).  out / out_stride as in
+ * AbxDesignScoreArgs (out_stride >= ABX_ACC_COLS).  rows: optional (B, L, 4) doubles: lDDT all, bb, ca and n_pairs of class all.
+ * counts: optional (B, L, 3, 5) int32.  contacts: optional (B, Lab, L - Lab) bytes.
+ * Two launches: grid (16-row tile, structure), one thread per row atom, the column tiles of both structures streamed through LDS,
+ * 15 integer counters per thread, reduced to the row with integer LDS adds (contact bits: integer LDS or); one block per structure
+ * for the superposition, the pooled sums and the row.  No floating-point atomics, every float sum in a fixed order, no allocation,
+ * no synchronisation: the bits of a structure depend on nothing but its own inputs.  The caller allocates the workspace
+ * (abx_accuracy_scores_workspace_bytes). */
+#define ABX_ACC_COLS 21
+typedef struct AbxAccuracyArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const unsigned char* region;                    /* optional (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs (> 0: the type has the slot) */
+    const float* plddt; long long plddt_sb;         /* optional (B,L) */
+    double lddt_radius, contact;                    /* inclusion radius (15.0), residue contact distance (5.0), Angstrom */
+    double* out; long long out_stride;
+    double* rows;                                   /* optional (B,L,4) */
+    int* counts;                                    /* optional (B,L,3,5) */
+    unsigned char* contacts;                        /* optional (B,Lab,L-Lab) */
+    int B, L, Lab;
+} AbxAccuracyArgs;
+long long abx_accuracy_scores_workspace_bytes(int B, int L);
+int abx_accuracy_scores(const AbxAccuracyArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
