@@ -309,6 +309,29 @@ class AbxAccuracyArgs(C.Structure):
     ]
 
 
+POLAR_COLS = 14           # ABX_POLAR_COLS
+POLAR_DONOR, POLAR_ACCEPTOR, POLAR_CATION, POLAR_ANION, POLAR_ELEMENT = 1, 2, 4, 8, 16     # ABX_POLAR_*
+
+
+class AbxPolarArgs(C.Structure):
+    _fields_ = [
+        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
+        ('pred_seq', c_f), ('pred_seq_sb', LL),
+        ('pred_mask', c_f), ('res_mask', c_f),
+        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+        ('region', c_f),
+        ('radius', c_f),
+        ('table', c_f),
+        ('points', c_f), ('P', I), ('probe', C.c_double),
+        ('hb_min', C.c_double), ('hb_max', C.c_double),
+        ('hb_angle', C.c_double), ('hb_cos2', C.c_double),
+        ('salt', C.c_double),
+        ('out', c_f), ('out_stride', LL),
+        ('bonds', c_f), ('rows', c_f),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -374,6 +397,9 @@ _PROTOS = {
     'abx_distogram_logits': (I, [C.POINTER(AbxDistogramArgs), c_f, _S]),
     'abx_accuracy_scores_workspace_bytes': (LL, [I, I]),
     'abx_accuracy_scores': (I, [C.POINTER(AbxAccuracyArgs), c_f, _S]),
+    'abx_polar_scores_workspace_bytes': (LL, [I, I]),
+    'abx_polar_scores_lds_bytes': (LL, [I]),
+    'abx_polar_scores': (I, [C.POINTER(AbxPolarArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

@@ -63,6 +63,14 @@ and the native antibody-antigen residue contacts that survive (DockQ's Fnat).  <
 --relax, the columns of the relaxed structure suffixed _relaxed (nan on the wild line), then delta_<column> = relaxed minus design for
 accuracy.DELTA_COLUMNS.  --accuracy_rows also writes <complex>_accuracy_rows.npy, the per-residue lDDT (N, L, 4: accuracy.ROW_COLUMNS;
 sample-sharded runs only).  No other output file changes.
+--polar: every design gets its polar row on the GPU after the last step (abx_amd.polar.PolarScorer, abx_polar_scores): heavy-atom hydrogen
+bonds and salt bridges between the antibody and the featurised antigen, the hydrogen bonds that hold the designed loop, and the polar
+atoms that binding buries without a partner (from the point counts of the interface analysis; with --interface the surface kernel runs
+once for both tables).  <output_dir>/<complex>_polar.tsv holds a `wild` line (the input complex itself) and one line per sample:
+polar.POLAR_COLUMNS, then delta_<column> = design minus wild type for polar.DELTA_COLUMNS and, with --relax, the columns of the relaxed
+structure suffixed _relaxed (nan on the wild line).  --polar_rows also writes <complex>_polar_rows.npy, (N, L, 4) int16 per residue:
+cross-side and same-side hydrogen bonds, salt bridges, unsatisfied atoms (polar.ROW_COLUMNS; sample-sharded runs only).  No other output
+file changes.
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -170,6 +178,22 @@ def _write_interface(out_dir, cname, wild, rows, relaxed):
         for i, v in rows:
             f.write(f'{i}\t' + '\t'.join(format_interface(v[:NI]) + format_delta(v[:NI], wild) +
                                           (format_interface(v[NI:2 * NI]) if relaxed else [])) + '\n')
+    return tsv
+
+
+def _write_polar(out_dir, cname, wild, rows, relaxed):
+    """<out_dir>/<complex>_polar.tsv: the `wild` line, then (sample id, values) per sample; values = the polar.POLAR_COLUMNS row and, when
+    relaxed, the row of the relaxed structure.  After the columns: delta_<column> = row minus wild for polar.DELTA_COLUMNS."""
+    from .polar import DELTA_COLUMNS, POLAR_COLUMNS, format_delta, format_polar
+    NP = len(POLAR_COLUMNS)
+    tsv = os.path.join(out_dir, f'{cname}_polar.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(POLAR_COLUMNS + tuple('delta_' + c for c in DELTA_COLUMNS) +
+                                       (tuple(c + '_relaxed' for c in POLAR_COLUMNS) if relaxed else ())) + '\n')
+        f.write('wild\t' + '\t'.join(format_polar(wild) + format_delta(wild, wild) + (['nan'] * NP if relaxed else [])) + '\n')
+        for i, v in rows:
+            f.write(f'{i}\t' + '\t'.join(format_polar(v[:NP]) + format_delta(v[:NP], wild) +
+                                          (format_polar(v[NP:2 * NP]) if relaxed else [])) + '\n')
     return tsv
 
 
@@ -302,6 +326,14 @@ def build_parser():
     ap.add_argument('--accuracy_contact', type=float, default=5.0, help='--accuracy: heavy-atom distance of a residue contact (Angstrom)')
     ap.add_argument('--accuracy_rows', action='store_true', help='--accuracy: also write <complex>_accuracy_rows.npy, the per-residue lDDT '
                     '(all atoms, backbone, C-alpha) and pair count of every sample, (N, L, 4)')
+    ap.add_argument('--polar', action='store_true', help='polar row of every design on the GPU (abx_polar_scores): heavy-atom hydrogen bonds '
+                    'and salt bridges across the interface, polar atoms buried by binding without a partner, and their difference to the input '
+                    'complex; writes <complex>_polar.tsv')
+    ap.add_argument('--polar_hb_max', type=float, default=3.5, help='--polar: largest donor-acceptor distance of a hydrogen bond (Angstrom, >= 2.0)')
+    ap.add_argument('--polar_hb_angle', type=float, default=90.0, help='--polar: smallest antecedent-atom...partner angle (degrees, [90, 180))')
+    ap.add_argument('--polar_salt', type=float, default=4.0, help='--polar: cation-anion distance of a salt bridge (Angstrom)')
+    ap.add_argument('--polar_rows', action='store_true', help='--polar: also write <complex>_polar_rows.npy, (N, L, 4) int16 per residue: '
+                    'cross-side and same-side hydrogen bonds, salt bridges, unsatisfied atoms')
     ap.add_argument('--ensemble', action='store_true', help='compare the designs of a complex with each other on the GPU (abx_ensemble_pairs, '
                     'abx_ensemble_cluster): pairwise RMSD of the designed residues, Daura clusters and their centres; writes <complex>_ensemble.tsv')
     ap.add_argument('--ensemble_cutoff', type=float, default=1.0, help='--ensemble: neighbour distance of the clusters (Angstrom)')
@@ -468,6 +500,18 @@ def main(argv=None):
         NA = len(ACCURACY_COLUMNS) * (3 if a.relax else 2)
     elif a.accuracy_rows:
         raise SystemExit('--accuracy_rows needs --accuracy')
+    NP = 0                                                      # --polar: the row (+ that of the relaxed structure) + the wild type's row
+    if a.polar:
+        from .polar import POLAR_COLUMNS, PolarScorer
+        if not a.polar_hb_max >= 2.0 or not 90.0 <= a.polar_hb_angle < 180.0 or not a.polar_salt >= 0:
+            raise SystemExit('--polar_hb_max must be >= 2.0 (the smallest donor-acceptor distance), --polar_hb_angle in [90, 180), --polar_salt >= 0')
+        if not 1 <= a.interface_points <= 1024 or a.interface_probe < 0:
+            raise SystemExit('--interface_points must be in 1..1024, --interface_probe >= 0')
+        if a.polar_rows and plan is not None:
+            raise SystemExit('--polar_rows needs the sample-sharded schedule (--shard_samples): a set-level run gathers one table only')
+        NP = len(POLAR_COLUMNS) * (3 if a.relax else 2)
+    elif a.polar_rows:
+        raise SystemExit('--polar_rows needs --polar')
     NE = 0                                                      # --ensemble, set-level rows: the antibody backbone (maxLab, 4, 3), f32 values
     analyzers = {}                                              # --ensemble: job -> EnsembleAnalyzer (the compared rows of the complex)
     if a.ensemble:
@@ -476,7 +520,7 @@ def main(argv=None):
             raise SystemExit(f'--ensemble compares 1..{ensemble.MAX_N} samples of a complex, --ensemble_cutoff must be >= 0')
         NE = 12 * maxLab
     E0 = 4 + maxLab + NS + n_rec * (1 + NS)                     # set-level rows: the backbone columns follow the scores
-    WIDTH = E0 + NE + NCF + NA + NR + NI                        # (the confidence and accuracy columns sit between the backbone and the relax report)
+    WIDTH = E0 + NE + NCF + NA + NP + NR + NI                   # (the confidence, accuracy and polar columns sit between the backbone and the relax report)
 
     def analyze_ensemble(ji, out_dir, cname, ids, seq, backbone):
         """The ensemble tables of job ji from the gathered tokens (N, Lab) and backbone (N, Lab, 4, 3) in the order of `ids`."""
@@ -546,6 +590,11 @@ def main(argv=None):
                 conf = DistogramScorer(batch, model, cutoff=a.confidence_cutoff, conf=cfg.model.heads.distogram)
                 conf.want_planes = a.confidence_planes
             acc = AccuracyScorer(batch, radius=a.accuracy_radius, contact=a.accuracy_contact) if a.accuracy else None
+            pol = None
+            if a.polar:                                         # (with --interface: one surface call per structure set serves both tables)
+                pol = PolarScorer(batch, hb_max=a.polar_hb_max, hb_angle=a.polar_hb_angle, salt=a.polar_salt, n_points=a.interface_points,
+                                  probe=a.interface_probe, interface=iface)
+                pol.want_rows = a.polar_rows
             if a.ensemble and ji not in analyzers:
                 analyzers[ji] = ensemble.EnsembleAnalyzer(batch, atoms=a.ensemble_atoms, metric=a.ensemble_metric, cutoff=a.ensemble_cutoff)
             torch.cuda.synchronize()
@@ -557,7 +606,8 @@ def main(argv=None):
                                                                      k_restraint=a.relax_restraint)} if a.relax else {}),
                                      **({'interface': iface} if a.interface else {}),
                                      **({'confidence': conf} if a.confidence else {}),
-                                     **({'accuracy': acc} if a.accuracy else {}))
+                                     **({'accuracy': acc} if a.accuracy else {}),
+                                     **({'polar': pol} if a.polar else {}))
             torch.cuda.synchronize()
             t_samp = time.perf_counter()
             new_files = writer.close()
@@ -580,9 +630,10 @@ def main(argv=None):
                                                         for r in traj], 1)
             if a.relax:
                 local['relax'] = torch.cat([traj[-1]['relax']] + ([traj[-1]['scores_relaxed']] if a.score else []), 1)
+            wild_pts = pol.new_points(1) if (a.polar and a.interface) else None      # the wild type's point counts serve both tables too
             if a.interface:                                     # the wild type's row rides along in every row: any rank can write the table
                 local['interface'] = torch.cat([traj[-1]['interface']] + ([traj[-1]['interface_relaxed']] if a.relax else []) +
-                                               [iface.wild().expand(n, -1)], 1)
+                                               [iface.wild(points=wild_pts).expand(n, -1)], 1)
             if a.confidence:                                    # every sample's own wild row rides along: any rank can write the table
                 local['confidence'] = torch.cat([traj[-1]['confidence']] + ([traj[-1]['confidence_relaxed']] if a.relax else []) +
                                                 [traj[-1]['confidence_wild']], 1)
@@ -593,6 +644,11 @@ def main(argv=None):
                                               [acc.wild().expand(n, -1)], 1)
                 if a.accuracy_rows:
                     local['accuracy_rows'] = traj[-1]['accuracy_rows']
+            if a.polar:                                         # the wild type's row rides along in every row: any rank can write the table
+                local['polar'] = torch.cat([traj[-1]['polar']] + ([traj[-1]['polar_relaxed']] if a.relax else []) +
+                                           [pol.wild(points=wild_pts).expand(n, -1)], 1)
+                if a.polar_rows:
+                    local['polar_rows'] = traj[-1]['polar_rows']
             if a.ensemble:                                      # N, CA, C, O of the antibody rows: what the comparison reads
                 local['backbone'] = traj[-1]['atom14_results'][:, :, :4].float().contiguous()
         else:                                                   # more ranks than samples: join the gather with zero-row blocks
@@ -613,6 +669,10 @@ def main(argv=None):
                 local['accuracy'] = torch.zeros(0, NA, dtype=torch.float64, device=dev)
                 if a.accuracy_rows:
                     local['accuracy_rows'] = torch.zeros(0, L, 4, dtype=torch.float64, device=dev)
+            if a.polar:
+                local['polar'] = torch.zeros(0, NP, dtype=torch.float64, device=dev)
+                if a.polar_rows:
+                    local['polar_rows'] = torch.zeros(0, L, 4, dtype=torch.int32, device=dev)
             if a.ensemble:
                 local['backbone'] = torch.zeros(0, Lab, 4, 3, dtype=torch.float32, device=dev)
         if plan is not None:
@@ -630,6 +690,8 @@ def main(argv=None):
                 row[:, E0 + NE:E0 + NE + NCF] = local['confidence'].cpu()
             if a.accuracy:
                 row[:, E0 + NE + NCF:E0 + NE + NCF + NA] = local['accuracy'].cpu()
+            if a.polar:
+                row[:, E0 + NE + NCF + NA:E0 + NE + NCF + NA + NP] = local['polar'].cpu()
             if a.relax:
                 row[:, row.shape[1] - NI - NR:row.shape[1] - NI] = local['relax'].cpu()
             if a.interface:
@@ -663,6 +725,13 @@ def main(argv=None):
                     import numpy as np
                     files.append(os.path.join(out_dir, f'{cname}_accuracy_rows.npy'))
                     np.save(files[-1], res['accuracy_rows'].cpu().numpy())
+            if a.polar:
+                pt = res['polar'].tolist()
+                files.append(_write_polar(out_dir, cname, pt[0][NP - len(POLAR_COLUMNS):], list(enumerate(pt)), a.relax))
+                if a.polar_rows:
+                    import numpy as np
+                    files.append(os.path.join(out_dir, f'{cname}_polar_rows.npy'))
+                    np.save(files[-1], res['polar_rows'].cpu().numpy().astype(np.int16))
             if a.ensemble:
                 files += analyze_ensemble(ji, out_dir, cname, list(range(N)), res['seq'], res['backbone'])
     if plan is not None:
@@ -694,6 +763,10 @@ def main(argv=None):
                     A0 = E0 + NE + NCF
                     files.append(_write_accuracy(jobs[ji][2], load_job(ji)['cname'], rows[0, A0 + NA - len(ACCURACY_COLUMNS):A0 + NA].tolist(),
                                                  [(int(r[1]), r[A0:A0 + NA].tolist()) for r in rows], a.relax))
+                if a.polar:
+                    P0 = E0 + NE + NCF + NA
+                    files.append(_write_polar(jobs[ji][2], load_job(ji)['cname'], rows[0, P0 + NP - len(POLAR_COLUMNS):P0 + NP].tolist(),
+                                              [(int(r[1]), r[P0:P0 + NP].tolist()) for r in rows], a.relax))
                 if a.ensemble:
                     lab = int(rows[0, 3])
                     files += analyze_ensemble(ji, jobs[ji][2], load_job(ji)['cname'], [int(r[1]) for r in rows], rows[:, 4:4 + lab].long(),

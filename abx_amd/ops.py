@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1244,6 +1244,70 @@ def interface_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, Lab=None
     a.B, a.L, a.Lab = B, L, Lab
     ws = torch.empty(max(int(lib.abx_interface_scores_workspace_bytes(B, L, a.P)), 16), dtype=torch.uint8, device=dev)
     check(lib.abx_interface_scores(C.byref(a), _p(ws), _stream()), 'abx_interface_scores')
+    return out
+
+
+def polar_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, table, Lab=None, region=None, mask=None, res_mask=None, points=None, n_points=128,
+                 probe=1.4, hb_min=2.0, hb_max=3.5, hb_angle=90.0, salt=4.0, out=None, bonds=None, rows=None):
+    """Polar contacts of B structures of one complex (abx_polar_scores; columns: abx_amd.polar.POLAR_COLUMNS): heavy-atom hydrogen bonds
+    and salt bridges between the rows < Lab and the rows >= Lab, and the polar atoms buried by binding without a partner.
+    atom14, seq, the complex, region, mask, res_mask as for interface_scores; table (21,14) int32 on the device (abx_amd.polar.
+    polar_table); points (B,L,14,2) int32 contiguous, the acc_alone / acc_cplx that interface_scores returned for the SAME structures with
+    n_points sphere points and `probe`, or None (columns 6-11 are -1).  hb_angle in degrees, [90, 180).
+    out: (B, 14) float64 with unit column stride and any row stride, or None; bonds: (B,L,14,2) int32 contiguous to receive the same-side /
+    cross-side bonds of every slot, or None; rows: (B,L,4) int32 contiguous to receive abx_amd.polar.ROW_COLUMNS of every row, or None.  One launch, no synchronisation."""
+    from abx_amd.polar import cos2_of
+    lib = _lib.load()
+    dev = atom14.device
+    L = gt_seq.shape[-1]
+    B, Lp = atom14.shape[0], atom14.shape[1]
+    Lab = int(seq.shape[1] if Lab is None else Lab)
+    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
+    assert tuple(gt_atom14.shape) == (L, 14, 3) and tuple(gt_exists.shape) == (L, 14) and tuple(gt_seq.shape) == (L,), \
+        'complex tensors: (L,...) shared by the batch'
+    assert table.dtype == torch.int32 and tuple(table.shape) == (21, 14) and table.is_contiguous() and table.device == dev, \
+        'table: (21,14) int32 on the device of atom14'
+    x = _f32(atom14)
+    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
+        x = x.contiguous()
+    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
+    keep = [x, sq]
+
+    def own(t, dtype):
+        t = t.to(dtype).contiguous()
+        keep.append(t)
+        return _p(t)
+
+    a = AbxPolarArgs()
+    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
+    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
+    if mask is not None:
+        assert tuple(mask.shape) == (B, L, 14), mask.shape
+        a.pred_mask = own(mask, torch.uint8)
+    if res_mask is not None:
+        assert tuple(res_mask.shape) == (L,), res_mask.shape
+        a.res_mask = own(res_mask, torch.uint8)
+    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
+    if region is not None:
+        assert tuple(region.shape) == (L,), region.shape
+        a.region = own(region.ne(0), torch.uint8)
+    a.radius, a.table = _p(vdw_radius_table(dev)), _p(table)
+    if points is not None:
+        assert points.dtype == torch.int32 and tuple(points.shape) == (B, L, 14, 2) and points.is_contiguous() and points.device == dev, 'points: (B,L,14,2) int32'
+        a.points, a.P, a.probe = _p(points), int(n_points), float(probe)
+    a.hb_min, a.hb_max, a.hb_angle, a.hb_cos2, a.salt = float(hb_min), float(hb_max), float(hb_angle), cos2_of(hb_angle), float(salt)
+    if out is None:
+        out = torch.empty(B, _lib.POLAR_COLS, dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (B, _lib.POLAR_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (B, 14) float64 rows'
+    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else _lib.POLAR_COLS
+    if bonds is not None:
+        assert bonds.dtype == torch.int32 and tuple(bonds.shape) == (B, L, 14, 2) and bonds.is_contiguous() and bonds.is_cuda, 'bonds: (B,L,14,2) int32'
+        a.bonds = _p(bonds)
+    if rows is not None:
+        assert rows.dtype == torch.int32 and tuple(rows.shape) == (B, L, 4) and rows.is_contiguous() and rows.is_cuda, 'rows: (B,L,4) int32'
+        a.rows = _p(rows)
+    a.B, a.L, a.Lab = B, L, Lab
+    check(lib.abx_polar_scores(C.byref(a), None, _stream()), 'abx_polar_scores')
     return out
 
 

@@ -24,7 +24,7 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None):
+              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -51,7 +51,12 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     ACCURACY_COLUMNS)) float64 - lDDT, TM-score / GDT and native-contact recovery of the designs against the crystal structure, and the
     calibration of the per-residue pLDDT of the last network call (before it is averaged into the record's 'pLDDT') - 'accuracy_rows'
     (B, L, 4) per residue, and with a relaxer 'accuracy_relaxed'.  Two launches per table, outside any captured step, no host
-    synchronisation."""
+    synchronisation.
+    polar: None, or an abx_amd.polar.PolarScorer of the complex: the LAST record gets 'polar' (B, len(polar.POLAR_COLUMNS)) float64 -
+    hydrogen bonds and salt bridges across the interface, polar atoms buried without a partner - with a relaxer 'polar_relaxed', and
+    with `polar.want_rows` 'polar_bonds' (B, L, 14, 2) and 'polar_rows' (B, L, 4) int32 of the designs.  When `interface` is the
+    scorer's own InterfaceScorer, its point counts serve both tables: the surface kernel runs once per structure set.  One launch per
+    table, outside any captured step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -120,10 +125,23 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                     traj[-1]['atom14_relaxed'], traj[-1]['relax'] = relaxer.relax(traj[-1]['atom14_results'], traj[-1]['seq'])
                     if scorer is not None:
                         traj[-1]['scores_relaxed'] = scorer.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'])
+                pts = pts_relaxed = None                        # point counts of the interface call, when the polar scorer shares it
                 if interface is not None and k == len(steps) - 1:
-                    traj[-1]['interface'] = interface.score(traj[-1]['atom14_results'], traj[-1]['seq'])
+                    if polar is not None and polar.interface is interface:
+                        pts = polar.new_points(B)
+                        pts_relaxed = polar.new_points(B) if relaxer is not None else None
+                    traj[-1]['interface'] = interface.score(traj[-1]['atom14_results'], traj[-1]['seq'], points=pts)
                     if relaxer is not None:
-                        traj[-1]['interface_relaxed'] = interface.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'])
+                        traj[-1]['interface_relaxed'] = interface.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'], points=pts_relaxed)
+                if polar is not None and k == len(steps) - 1:
+                    rows = bool(getattr(polar, 'want_rows', False))
+                    if rows:
+                        traj[-1]['polar_bonds'] = torch.empty(B, polar.L, 14, 2, dtype=torch.int32, device=device)
+                        traj[-1]['polar_rows'] = torch.empty(B, polar.L, 4, dtype=torch.int32, device=device)
+                    traj[-1]['polar'] = polar.score(traj[-1]['atom14_results'], traj[-1]['seq'], points=pts,
+                                                    bonds=traj[-1].get('polar_bonds'), rows=traj[-1].get('polar_rows'))
+                    if relaxer is not None:
+                        traj[-1]['polar_relaxed'] = polar.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'], points=pts_relaxed)
                 if confidence is not None and k == len(steps) - 1:
                     pair = out['representations']['pair']       # of the call just made: nothing between it and here runs the network
                     got = confidence.score(pair, traj[-1]['atom14_results'], traj[-1]['seq'], planes=bool(getattr(confidence, 'want_planes', False)))

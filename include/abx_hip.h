@@ -855,6 +855,84 @@ long long abx_accuracy_scores_workspace_bytes(int B, int L);
 int abx_accuracy_scores(const AbxAccuracyArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Polar interface contacts of designs: the chemical columns upstream takes from InterfaceAnalyzerMover beside dG and dSASA
+ * (hbonds_int, delta_unsatHbonds; abx/metric.py:28-59, eval/traj_evaluate.py:233-261) that need no force field: hydrogen bonds and salt
+ * bridges across the interface, and the polar atoms that binding buries without giving them a partner.  Heavy atoms only (no
+ * hydrogens, no energies, no His protonation, no water).  One row of ABX_POLAR_COLS float64 values per structure of a batch of B
+ * designs of ONE complex (abx_amd.polar.POLAR_COLUMNS).
+ * table: [21][14] int32 per (residue type, atom14 slot), built by the caller from the atom names (abx_amd.polar.polar_table):
+ * ABX_POLAR_DONOR | ABX_POLAR_ACCEPTOR | ABX_POLAR_CATION | ABX_POLAR_ANION role bits, ABX_POLAR_ELEMENT (the name starts with N or O:
+ * splits the buried area only), and in bits 8-11 the atom14 slot of one bonded heavy atom, the antecedent.  A POLAR ATOM is a slot
+ * with a donor or acceptor bit whose slot and antecedent slot both exist; at most 5 per residue type (Arg: N, O, NE, NH1, NH2; a table
+ * with more is cut to 5 L atoms per structure).
+ * Every decision in float64 from the float32 coordinates, without fused multiply-add, in this order, so every count is an exact
+ * integer that a host evaluation of the same IEEE operations reproduces (abx_amd.polar.polar_host).  Per unordered pair (a, b) of
+ * polar atoms of DIFFERENT rows, a before b in (row, slot) order:
+ *   dx = (double)x_b - (double)x_a (likewise y, z);  d2 = (dx*dx + dy*dy) + dz*dz
+ * Hydrogen bond (one a donor, the other an acceptor):  hb_min*hb_min <= d2 <= hb_max*hb_max  and, with u = ante_a - a, v = ante_b - b
+ * (component-wise in float64),
+ *   ta = (u.x*dx + u.y*dy) + u.z*dz;  uu = (u.x*u.x + u.y*u.y) + u.z*u.z;  ta <= 0  and  ta*ta >= cos2 * (uu * d2)
+ *   tb = (v.x*dx + v.y*dy) + v.z*dz;  vv likewise;                         tb >= 0  and  tb*tb >= cos2 * (vv * d2)
+ * i.e. both angles antecedent - atom ... partner are at least hb_angle (90 degrees: the HBPLUS heavy-atom rule).  hb_angle in
+ * [90, 180) degrees; hb_cos2 = cos^2(hb_angle) is computed by the caller (checked here to 1e-12; exactly 0 is used at 90 degrees): no
+ * square root, no trigonometry on the device.  The test is symmetric under exchange of a and b bit for bit.  No link rule: the
+ * backbone C-O ... N(i+1) angle is about 30 degrees and fails; chain ids and residue numbers are not read.
+ * Salt bridge: a pair of rows on DIFFERENT sides counts once when a cation atom of one and an anion atom of the other have
+ * d2 <= salt*salt, however many atom pairs qualify.
+ * Burial, from `points` ((B, L, 14, 2) int32: acc_alone, acc_cplx of every slot, the output of abx_interface_scores for the same
+ * structures with P sphere points and `probe`): a polar atom is AT THE INTERFACE if acc_alone > acc_cplx, BURIED BY BINDING if
+ * acc_alone > 0 and acc_cplx == 0, UNSATISFIED if buried by binding and in no hydrogen bond (same side or cross).  Area of a count:
+ * 4 pi R_a^2 count / P, R_a = (double)r_a + probe, over the existing slots with a positive radius.
+ *   0 n_hbond_int           bonds between side A and side B         7 n_polar_buried  polar atoms buried by binding
+ *   1 n_hbond_int_bb        those of 0 between two backbone atoms   8 n_unsat         buried and unsatisfied
+ *                           (slots 0-3)                             9 n_unsat_region  those of 8 in region rows
+ *   2 n_hbond_region        those of 0 with an atom in a region row 10 dsasa_polar    area(acc_alone - acc_cplx), ABX_POLAR_ELEMENT slots
+ *   3 n_hbond_intra_region  same-side bonds with an atom in a       11 dsasa_apolar   the same over all other atoms (10 + 11 = dsasa_int)
+ *                           region row                              12 n_hbond_total  all bonds of the structure
+ *   4 n_salt_int            cross-side salt-bridged row pairs       13 n_polar        polar atoms counted
+ *   5 n_salt_region         those of 4 with a region row
+ *   6 n_polar_int           polar atoms at the interface
+ * points NULL: columns 6-11 are -1 (P and probe are not read).  region NULL: columns 2, 3, 5 and 9 are 0.
+ * The structure and the complex are given as for abx_interface_scores (pred_* rows < Lpred, ground truth beyond, residue types of rows
+ * < Lab from pred_seq; pred_mask / res_mask optional; side A = rows < Lab; region (L) bytes shared by the batch).
+ * bonds: optional (B, L, 14, 2) int32, the same-side and cross-side bonds of every slot (0 for absent or non-polar slots; its sum over
+ * a structure is 2 x column 12).  rows: optional (B, L, 4) int32 per row: its cross-side bonds, its same-side bonds, the rows it is
+ * salt-bridged to across the interface (sum: 2 x column 4), its unsatisfied atoms (-1 without points).
+ * One launch, one workgroup per structure: the polar atoms compacted in slot order into LDS (216 bytes per row + 512 must fit 160 KB:
+ * L <= 756, a larger problem is an argument error), the pairs dealt to the waves in a fixed pattern, integer LDS atomics for the
+ * counters (integers commute), the two areas in a fixed order.  No global atomics, no allocation, no synchronisation: a structure's
+ * row depends on nothing but its own inputs.  The workspace is empty today (abx_polar_scores_workspace_bytes returns 0 and a NULL
+ * workspace is accepted). */
+#define ABX_POLAR_COLS 14
+#define ABX_POLAR_DONOR 1
+#define ABX_POLAR_ACCEPTOR 2
+#define ABX_POLAR_CATION 4
+#define ABX_POLAR_ANION 8
+#define ABX_POLAR_ELEMENT 16
+typedef struct AbxPolarArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const unsigned char* region;                    /* optional (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs */
+    const int* table;                               /* [21][14] roles | antecedent slot << 8 */
+    const int* points; int P; double probe;         /* optional (B,L,14,2) of abx_interface_scores, its P and probe */
+    double hb_min, hb_max;                          /* donor-acceptor distance range (2.0, 3.5), Angstrom */
+    double hb_angle, hb_cos2;                       /* smallest antecedent-atom-partner angle (90.0 degrees) and its squared cosine */
+    double salt;                                    /* cation-anion distance (4.0), Angstrom */
+    double* out; long long out_stride;
+    int* bonds;                                     /* optional (B,L,14,2) */
+    int* rows;                                      /* optional (B,L,4) */
+    int B, L, Lab;
+} AbxPolarArgs;
+long long abx_polar_scores_workspace_bytes(int B, int L);
+/* LDS bytes a structure of L rows needs (<= 163840 to be accepted) */
+long long abx_polar_scores_lds_bytes(int L);
+int abx_polar_scores(const AbxPolarArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
