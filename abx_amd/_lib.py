@@ -185,15 +185,19 @@ class AbxGuidanceArgs(C.Structure):
     ]
 
 
+# The leading fields of the five per-design analyses' descriptors (include/abx_hip.h): the structure that csrc/structure_dev.h reads
+_STRUCTURE_FIELDS = [
+    ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
+    ('pred_seq', c_f), ('pred_seq_sb', LL),
+    ('pred_mask', c_f), ('res_mask', c_f),
+    ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+]
+
 SCORE_COLS = 19           # ABX_SCORE_COLS
 
 
 class AbxDesignScoreArgs(C.Structure):
-    _fields_ = [
-        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
-        ('pred_seq', c_f), ('pred_seq_sb', LL),
-        ('pred_mask', c_f), ('res_mask', c_f),
-        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+    _fields_ = _STRUCTURE_FIELDS + [
         ('cdr_def', c_f), ('chain_id', c_f), ('residx', c_f),
         ('complex_batched', I),
         ('radius', c_f),
@@ -207,11 +211,7 @@ RELAX_COLS = 11           # ABX_RELAX_COLS
 
 
 class AbxRelaxArgs(C.Structure):
-    _fields_ = [
-        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
-        ('pred_seq', c_f), ('pred_seq_sb', LL),
-        ('pred_mask', c_f), ('res_mask', c_f),
-        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+    _fields_ = _STRUCTURE_FIELDS + [
         ('chain_id', c_f), ('residx', c_f), ('movable', c_f),
         ('radius', c_f), ('chi_axis', c_f), ('rigid_group', c_f),
         ('overlap_tolerance', F), ('between_chain_factor', F), ('bond_tolerance_factor', F), ('w_clash', F), ('w_bond', F), ('w_angle', F),
@@ -228,11 +228,7 @@ IFACE_COLS = 12           # ABX_IFACE_COLS
 
 
 class AbxInterfaceArgs(C.Structure):
-    _fields_ = [
-        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
-        ('pred_seq', c_f), ('pred_seq_sb', LL),
-        ('pred_mask', c_f), ('res_mask', c_f),
-        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+    _fields_ = _STRUCTURE_FIELDS + [
         ('region', c_f),
         ('radius', c_f),
         ('sphere', c_f), ('P', I),
@@ -294,11 +290,7 @@ ACC_COLS = 21             # ABX_ACC_COLS
 
 
 class AbxAccuracyArgs(C.Structure):
-    _fields_ = [
-        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
-        ('pred_seq', c_f), ('pred_seq_sb', LL),
-        ('pred_mask', c_f), ('res_mask', c_f),
-        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+    _fields_ = _STRUCTURE_FIELDS + [
         ('region', c_f),
         ('radius', c_f),
         ('plddt', c_f), ('plddt_sb', LL),
@@ -314,11 +306,7 @@ POLAR_DONOR, POLAR_ACCEPTOR, POLAR_CATION, POLAR_ANION, POLAR_ELEMENT = 1, 2, 4,
 
 
 class AbxPolarArgs(C.Structure):
-    _fields_ = [
-        ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
-        ('pred_seq', c_f), ('pred_seq_sb', LL),
-        ('pred_mask', c_f), ('res_mask', c_f),
-        ('gt_atom14', c_f), ('gt_exists', c_f), ('gt_seq', c_f),
+    _fields_ = _STRUCTURE_FIELDS + [
         ('region', c_f),
         ('radius', c_f),
         ('table', c_f),

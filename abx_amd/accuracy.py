@@ -17,7 +17,11 @@ ring counts as a deviation.  The definitions, operation by operation: include/ab
 Every decision is taken in float64 from the float32 coordinates in a fixed IEEE operation order, so the counts of the device
 (`AccuracyScorer`, abx_accuracy_scores, csrc/accuracy.hip) and of the host twin (`accuracy_host`, numpy) are equal integers unless a
 pair sits on a threshold, which the twin counts (`n_borderline`, `n_borderline_gdt`)."""
+import functools
+
 import numpy as np
+
+from . import complex_view
 
 # The row of abx_accuracy_scores (include/abx_hip.h, ABX_ACC_COLS)
 ACCURACY_COLUMNS = ('lddt_all', 'lddt_antibody', 'lddt_region', 'lddt_bb_region', 'lddt_ca_all', 'lddt_ca_region', 'plddt_region',
@@ -30,49 +34,27 @@ DELTA_COLUMNS = ('lddt_region', 'lddt_bb_region', 'rmsd_ca', 'n_kept')
 ROW_COLUMNS = ('lddt_all', 'lddt_bb', 'lddt_ca', 'n_pairs')
 THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
 GDT_CUTOFFS = (0.5, 1.0, 2.0, 4.0, 8.0)
-_PLACES = {'plddt_region': 2, 'plddt_err_region': 2, 'rmsd_ca': 3}
+_PLACES = {'plddt_region': 2, 'plddt_err_region': 2, 'rmsd_ca': 3, None: 4}
 
 
-def format_accuracy(row):
-    """One row as TSV fields: integers for the counts, %.2f for the pLDDT columns, %.3f for the RMSD (Angstrom), %.4f for the scores."""
-    return [str(int(v)) if c in COUNT_COLUMNS else f'{float(v):.{_PLACES.get(c, 4)}f}' for c, v in zip(ACCURACY_COLUMNS, row)]
+# format_accuracy(row): integers for the counts, %.2f for the pLDDT columns, %.3f for the RMSD (Angstrom), %.4f for the scores;
+# format_delta(row, base): row minus base for DELTA_COLUMNS, signed, at the same precision
+format_accuracy = functools.partial(complex_view.format_row, ACCURACY_COLUMNS, COUNT_COLUMNS, _PLACES)
+format_delta = functools.partial(complex_view.format_delta, ACCURACY_COLUMNS, COUNT_COLUMNS, DELTA_COLUMNS, _PLACES)
 
 
-def format_delta(row, base):
-    """row minus base for DELTA_COLUMNS, signed, at the precision of format_accuracy."""
-    out = []
-    for c in DELTA_COLUMNS:
-        k = ACCURACY_COLUMNS.index(c)
-        d = float(row[k]) - float(base[k])
-        out.append(f'{int(round(d)):+d}' if c in COUNT_COLUMNS else f'{d:+.{_PLACES.get(c, 4)}f}')
-    return out
-
-
-class AccuracyScorer:
+class AccuracyScorer(complex_view.ComplexView):
     """Accuracy rows of batches of designs of ONE complex on the device.  Built once per complex from its featurised batch (or the
     un-batched complex) like interface.InterfaceScorer.  region: (L) mask of the designed rows the `*_region` columns describe
     (default: the rows the sampler diffuses, sample 0's (1 - fixed_mask) * backbone mask).  radius: lDDT inclusion radius; contact:
     heavy-atom distance of a residue contact (Angstrom)."""
 
-    def __init__(self, batch, region=None, radius=15.0, contact=5.0):
-        import torch
-        one = (lambda k: batch[k][0]) if batch['seq'].dim() == 2 else (lambda k: batch[k])
-        self.Lab = int(batch['anchor_flag'].shape[-1])
-        self.gt_atom14 = one('atom14_gt_positions').to(torch.float32).contiguous()
-        self.gt_exists = one('atom14_gt_exists').to(torch.uint8).contiguous()
-        self.gt_seq = one('seq').to(torch.int64).contiguous()
-        self.res_mask = one('mask').to(torch.uint8).contiguous() if 'mask' in batch else None
-        dev = self.gt_atom14.device
-        if region is None:
-            region = (1 - one('fixed_mask')) * one('atom14_gt_exists')[..., 0]
-        self.region = (torch.as_tensor(region).to(dev) != 0).to(torch.uint8).contiguous()
-        self.L = int(self.gt_seq.shape[0])
-        self.kw = dict(radius=float(radius), contact=float(contact))
+    COLUMNS = ACCURACY_COLUMNS
 
-    def new_table(self, *lead):
-        """An uninitialised (*lead, len(ACCURACY_COLUMNS)) float64 table on the complex's device for `score(..., out=table[i])`."""
-        import torch
-        return torch.empty(*lead, len(ACCURACY_COLUMNS), dtype=torch.float64, device=self.gt_atom14.device)
+    def __init__(self, batch, region=None, radius=15.0, contact=5.0):
+        super().__init__(batch)
+        self.region = complex_view.region_mask(batch, region, self.gt_atom14.device)
+        self.kw = dict(radius=float(radius), contact=float(contact))
 
     def score(self, atom14, seq, plddt=None, out=None, rows=False, counts=False, contacts=False, mask=None):
         """atom14 (B, Lab or L, 14, 3) f32 predicted coordinates (antibody only: the antigen is the ground truth's), seq (B, Lab) tokens,
@@ -90,10 +72,8 @@ class AccuracyScorer:
                                     res_mask=self.res_mask, plddt=plddt, out=out, rows=r, counts=c, contacts=k, **self.kw)
         return (table, r, c, k) if (rows or counts or contacts) else table
 
-    def wild(self, **kw):
-        """(1, len(ACCURACY_COLUMNS)): the crystal structure against itself with its own atoms - every lDDT 1, fnat 1, rmsd_ca 0, the
-        pLDDT columns nan: the first line of the driver's table and the check that the conventions line up."""
-        return self.score(self.gt_atom14[None, :self.Lab], self.gt_seq[None, :self.Lab], mask=self.gt_exists[None], **kw)
+    # wild(**kw): the crystal structure against itself - every lDDT 1, fnat 1, rmsd_ca 0, the pLDDT columns nan: the first line of the
+    # driver's table and the check that the conventions line up
 
 
 # -------------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,11 @@ Upstream trains the head with every checkpoint (`impl.distogram.proj`, abx/model
 sum softmax(logits)[..., :t+1], t = #{breaks <= cutoff}).  At the headline shape the logits are 3.2 GB that exist only to be reduced
 again, so `DistogramScorer` never forms them: abx_distogram_scores (csrc/distogram.hip, include/abx_hip.h AbxDistogramArgs) projects,
 symmetrises, takes the softmax and reduces in one kernel.  `distogram_host` is its float64 twin on the host (numpy; no GPU)."""
+import functools
+
 import numpy as np
+
+from . import complex_view
 
 # The row of abx_distogram_scores (include/abx_hip.h, ABX_DISTO_COLS).  region = the designed rows; pairs are ordered, i != j, both valid.
 CONFIDENCE_COLUMNS = ('nll_all', 'nll_antibody_antigen', 'nll_region', 'nll_region_antigen', 'dist_err_region', 'entropy_region',
@@ -27,14 +31,8 @@ def format_confidence(row):
     return [str(int(round(float(v)))) if c in COUNT_COLUMNS else f'{float(v):.4f}' for c, v in zip(CONFIDENCE_COLUMNS, row)]
 
 
-def format_delta(row, wild):
-    """design minus wild type for DELTA_COLUMNS, signed."""
-    out = []
-    for c in DELTA_COLUMNS:
-        k = CONFIDENCE_COLUMNS.index(c)
-        d = float(row[k]) - float(wild[k])
-        out.append(f'{int(round(d)):+d}' if c in COUNT_COLUMNS else f'{d:+.4f}')
-    return out
+# format_delta(row, wild): design minus wild type for DELTA_COLUMNS, signed
+format_delta = functools.partial(complex_view.format_delta, CONFIDENCE_COLUMNS, COUNT_COLUMNS, DELTA_COLUMNS, 4)
 
 
 def distogram_breaks(conf=None):
@@ -59,30 +57,27 @@ def pseudo_beta(atom14, seq):
     return torch.where((seq == GLY)[..., None], atom14[..., 1, :], atom14[..., 4, :])
 
 
-class DistogramScorer:
+class DistogramScorer(complex_view.ComplexView):
     """Confidence rows of batches of designs of ONE complex on the device.  Built once per complex from its featurised batch (or the
     un-batched complex) like interface.InterfaceScorer: the antigen rows (>= Lab) come from the ground-truth atom14, the antibody rows
     from the design; the pseudo-beta atom is CB, or CA for a Gly of the design's own `seq`.  params_or_model: a state dict or a module
     holding `impl.distogram.proj.{weight,bias}`.  region: (L) mask of the designed rows (default: the rows the sampler diffuses, sample
     0's (1 - fixed_mask) * backbone mask); cutoff: contact distance of the pseudo-beta atoms (Angstrom)."""
 
+    COLUMNS = CONFIDENCE_COLUMNS
+
     def __init__(self, batch, params_or_model, region=None, cutoff=8.0, conf=None):
         import torch
         from abx_amd import ops
-        one = (lambda k: batch[k][0]) if batch['seq'].dim() == 2 else (lambda k: batch[k])
-        self.Lab = int(batch['anchor_flag'].shape[-1])
-        self.gt_atom14 = one('atom14_gt_positions').to(torch.float32).contiguous()
-        self.gt_exists = one('atom14_gt_exists').ne(0)
-        self.gt_seq = one('seq').to(torch.int64).contiguous()
-        L = self.L = int(self.gt_seq.shape[0])
-        dev = self.device = self.gt_atom14.device
-        self.res_mask = one('mask').ne(0) if 'mask' in batch else torch.ones(L, dtype=torch.bool, device=dev)
-        if region is None:
-            region = (1 - one('fixed_mask')) * one('atom14_gt_exists')[..., 0]
-        region = torch.as_tensor(region).to(dev) != 0
+        super().__init__(batch)
+        L, dev = self.L, self.gt_atom14.device
+        self.device = dev
+        self.gt_exists = self.gt_exists.ne(0)               # (this scorer's masks are bool: they are combined on the host side of the call)
+        self.res_mask = self.res_mask.ne(0) if self.res_mask is not None else torch.ones(L, dtype=torch.bool, device=dev)
+        region = complex_view.region_mask(batch, region, dev)
         cls = torch.full((L,), ANTIGEN, dtype=torch.uint8, device=dev)
         cls[:self.Lab] = ANTIBODY
-        self.classes = (cls | (region.to(torch.uint8) * DESIGNED)).contiguous()
+        self.classes = (cls | (region * DESIGNED)).contiguous()
         sd = params_or_model.state_dict() if hasattr(params_or_model, 'state_dict') else params_or_model
         self.weight = sd['impl.distogram.proj.weight'].detach().to(dev, torch.float32).contiguous()
         self.bias = sd['impl.distogram.proj.bias'].detach().to(dev, torch.float32).contiguous()

@@ -13,6 +13,8 @@
 //                    superposition (Horn's quaternion, cyclic Jacobi in LDS, as metrics.hip), the TM block, the row.
 #include "common.h"
 #include "abx_hip.h"
+#include "reduce_dev.h"
+#include "structure_dev.h"
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -24,37 +26,11 @@ constexpr int AT = RT * 14;            // atoms per tile (224)
 constexpr int WS = 20;                 // ints per residue in the workspace: counts [3][5], n_native, n_kept, n_new, scored atoms, pad
 constexpr int F_SCORED = 1, F_WILD = 2, F_DESIGN = 4;
 
-// One design of the batch and the wild type: rows < Lpred of the design from the prediction, the rest from the ground truth
-struct Structure {
-    const float* pred; const float* gt;
-    const long long* pseq; const long long* gseq;
-    const unsigned char* pmask; const unsigned char* gexists; const unsigned char* rmask;
-    const float* radius;
-    int Lab, Lpred;
-    __device__ __forceinline__ Structure(const AbxAccuracyArgs& a, int b) {
-        pred = a.pred_atom14 + (long long)b * a.pred_sb;
-        gt = a.gt_atom14;
-        pseq = a.pred_seq + (long long)b * a.pred_seq_sb;
-        gseq = a.gt_seq;
-        pmask = a.pred_mask ? a.pred_mask + (long long)b * a.L * 14 : nullptr;
-        gexists = a.gt_exists;
-        rmask = a.res_mask;
-        radius = a.radius;
-        Lab = a.Lab; Lpred = a.Lpred;
-    }
-    static __device__ __forceinline__ int clamp_aa(long long aa) { return aa < 0 ? 20 : (aa > 20 ? 20 : (int)aa); }
-    __device__ __forceinline__ int aatype(int res) const { return clamp_aa(res < Lab ? pseq[res] : gseq[res]); }
+// One design of the batch (structure_dev.h) and the wild type: the ground truth in every row
+struct Structure : StructureView<AbxAccuracyArgs> {
+    using StructureView<AbxAccuracyArgs>::StructureView;
     __device__ __forceinline__ int wild_aatype(int res) const { return clamp_aa(gseq[res]); }
-    __device__ __forceinline__ bool kept(int res) const { return !rmask || rmask[res] != 0; }
-    __device__ __forceinline__ const float* xyz(int res, int slot) const {
-        return (res < Lpred ? pred : gt) + ((long long)res * 14 + slot) * 3;
-    }
     __device__ __forceinline__ const float* wild_xyz(int res, int slot) const { return gt + ((long long)res * 14 + slot) * 3; }
-    __device__ __forceinline__ bool exists(int res, int slot, int aa) const {
-        if (!kept(res)) return false;
-        if (pmask) return pmask[(long long)res * 14 + slot] != 0;
-        return res < Lpred ? radius[aa * 14 + slot] > 0.f : gexists[(long long)res * 14 + slot] != 0;
-    }
     __device__ __forceinline__ bool wild_exists(int res, int slot) const { return kept(res) && gexists[(long long)res * 14 + slot] != 0; }
 };
 
@@ -157,63 +133,6 @@ __global__ __launch_bounds__(256) void acc_pair_kernel(const AbxAccuracyArgs a, 
     for (int k = tid; k < RT * WS; k += 256) {
         const int res = it * RT + k / WS;
         if (res < L) ws[((long long)b * L + res) * WS + (k % WS)] = (&rcnt[0][0])[k];
-    }
-}
-
-// Sum of N doubles per thread over the block, in a fixed order; every thread returns with the totals in v.  `sh`: [4][N] doubles.
-template <int N>
-__device__ __forceinline__ void block_sum_d(double (&v)[N], double* sh) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = wave_sum_d(v[k]);
-    __syncthreads();                                   // the previous use of sh is over
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) sh[(tid >> 6) * N + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = (sh[k] + sh[N + k]) + (sh[2 * N + k] + sh[3 * N + k]);
-}
-
-// Eigenvectors of the symmetric 4x4 matrix A (LDS) by cyclic Jacobi rotations, accumulated in V (LDS).  One thread.  The copy of
-// metrics.hip::jacobi4 (ensemble.hip keeps its own too): a rotation zeroes A[p][q] exactly; the sweeps stop when the off-diagonal
-// mass is below 1e-36 of the matrix.
-__device__ void jacobi4(double (*A)[4], double (*V)[4]) {
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 24; ++sweep) {
-        double off = 0.0, all = 0.0;
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) {
-                all += A[i][j] * A[i][j];
-                if (i < j) off += A[i][j] * A[i][j];
-            }
-        if (off <= 1e-36 * all) break;
-        for (int p = 0; p < 3; ++p)
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-                for (int k = 0; k < 4; ++k) {
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - sn * akq;
-                    A[k][q] = sn * akp + c * akq;
-                }
-                for (int k = 0; k < 4; ++k) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - sn * aqk;
-                    A[q][k] = sn * apk + c * aqk;
-                }
-                A[p][q] = A[q][p] = 0.0;
-                for (int k = 0; k < 4; ++k) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - sn * vkq;
-                    V[k][q] = sn * vkp + c * vkq;
-                }
-            }
     }
 }
 
@@ -322,26 +241,7 @@ __global__ __launch_bounds__(256) void acc_row_kernel(const AbxAccuracyArgs a, c
         S[6] += gz * qx; S[7] += gz * qy; S[8] += gz * qz;
     }
     block_sum_d<9>(S, red);
-    if (tid == 0 && nca > 0.0) {
-        // Horn 1987: the unit quaternion of the optimal proper rotation is the eigenvector of the largest eigenvalue of N
-        const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
-        Nm[0][0] = Sxx + Syy + Szz; Nm[0][1] = Syz - Szy;       Nm[0][2] = Szx - Sxz;        Nm[0][3] = Sxy - Syx;
-        Nm[1][1] = Sxx - Syy - Szz; Nm[1][2] = Sxy + Syx;       Nm[1][3] = Szx + Sxz;
-        Nm[2][2] = -Sxx + Syy - Szz; Nm[2][3] = Syz + Szy;
-        Nm[3][3] = -Sxx - Syy + Szz;
-        for (int i = 1; i < 4; ++i)
-            for (int j = 0; j < i; ++j) Nm[i][j] = Nm[j][i];
-        jacobi4(Nm, Vm);
-        int im = 0;
-        for (int i = 1; i < 4; ++i)
-            if (Nm[i][i] > Nm[im][im]) im = i;
-        double qw = Vm[0][im], qx = Vm[1][im], qy = Vm[2][im], qz = Vm[3][im];
-        const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-        qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-        Rs[0] = 1.0 - 2.0 * (qy * qy + qz * qz); Rs[1] = 2.0 * (qx * qy - qw * qz);       Rs[2] = 2.0 * (qx * qz + qw * qy);
-        Rs[3] = 2.0 * (qx * qy + qw * qz);       Rs[4] = 1.0 - 2.0 * (qx * qx + qz * qz); Rs[5] = 2.0 * (qy * qz - qw * qx);
-        Rs[6] = 2.0 * (qx * qz - qw * qy);       Rs[7] = 2.0 * (qy * qz + qw * qx);       Rs[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
-    }
+    if (tid == 0 && nca > 0.0) horn_rotation_lds(S, Nm, Vm, Rs);
     __syncthreads();
     double R[9];
 #pragma unroll
@@ -384,10 +284,8 @@ extern "C" long long abx_accuracy_scores_workspace_bytes(int B, int L) {
 extern "C" int abx_accuracy_scores(const AbxAccuracyArgs* ap, void* workspace, hipStream_t st) {
     ABX_REQUIRE(ap != nullptr, "abx_accuracy_scores: null");
     const AbxAccuracyArgs a = *ap;
-    ABX_REQUIRE(a.B > 0 && a.L > 0 && a.B <= 65535 && a.L < (1 << 22), "abx_accuracy_scores: bad sizes");
-    ABX_REQUIRE(a.Lab > 0 && a.Lab <= a.L, "abx_accuracy_scores: Lab must be in 1..L");
-    ABX_REQUIRE(a.Lpred == a.Lab || a.Lpred == a.L, "abx_accuracy_scores: Lpred must be Lab or L");
-    ABX_REQUIRE(a.pred_atom14 && a.pred_seq && a.gt_atom14 && a.gt_exists && a.gt_seq && a.radius && a.out, "abx_accuracy_scores: null operand");
+    if (int rc = abx_check_structure_args(a, "abx_accuracy_scores", 1, true)) return rc;
+    ABX_REQUIRE(a.out, "abx_accuracy_scores: null operand");
     ABX_REQUIRE(a.out_stride >= ABX_ACC_COLS, "abx_accuracy_scores: out_stride below ABX_ACC_COLS");
     ABX_REQUIRE(std::isfinite(a.lddt_radius) && a.lddt_radius > 0.0, "abx_accuracy_scores: lddt_radius must be > 0");
     ABX_REQUIRE(std::isfinite(a.contact) && a.contact > 0.0, "abx_accuracy_scores: contact must be > 0");

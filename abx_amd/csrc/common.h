@@ -5,6 +5,8 @@
 
 #define ABX_OK 0
 #define ABX_ERR_ARG (-1)
+// LDS bytes of a CU that one workgroup may take (gfx950: 160 KB)
+#define ABX_LDS_LIMIT 163840
 
 // thread-local last error text (abx_last_error_string)
 void abx_set_error(const char* msg);

@@ -7,7 +7,7 @@
 //                       the raw f32 points of its 8 i- and 8 j-structures are staged in LDS (12 P bytes each), one lane per pair.
 //                       Centroids per structure (fp64, index order), the 3x3 covariance per pair (fp64, index order), Horn's quaternion
 //                       matrix solved PER LANE by cyclic Jacobi rotations on statically indexed registers - the arithmetic of
-//                       metrics.hip::jacobi4, which survives a degenerate largest eigenvalue (collinear or planar points: any vector of
+//                       reduce_dev.h::jacobi4, which survives a degenerate largest eigenvalue (collinear or planar points: any vector of
 //                       the eigenspace is optimal), where the adjugate of the characteristic-polynomial route vanishes - and the squared
 //                       deviation in a second pass over the points with the rotation found.  i < j is computed, both entries are written.
 //                       A pair reads nothing but its two structures: its value does not depend on N or on its tile.
@@ -24,12 +24,11 @@ namespace {
 
 constexpr int T = 8;                                   // structures per tile side
 constexpr int MAXP = ABX_ENS_MAX_POINTS;
-constexpr long long LDS_LIMIT = 160 * 1024;
 
 __host__ __device__ inline int point_stride(int P) { return (3 * P) | 1; }     // floats per staged structure, odd
 inline long long pairs_lds_bytes(int P) { return 2ll * T * point_stride(P) * (long long)sizeof(float); }
 
-// One Jacobi rotation of the symmetric 4x4 matrix A in the (P_, Q_) plane, accumulated in V: metrics.hip::jacobi4 with every index a
+// One Jacobi rotation of the symmetric 4x4 matrix A in the (P_, Q_) plane, accumulated in V: reduce_dev.h::jacobi4 with every index a
 // compile-time constant, so that both matrices live in registers.
 template <int P_, int Q_>
 __device__ __forceinline__ void jacobi_rotate(double (&A)[4][4], double (&V)[4][4]) {
@@ -338,7 +337,7 @@ extern "C" int abx_ensemble_pairs(const AbxEnsemblePairsArgs* ap, void* workspac
     ABX_REQUIRE(a.plane_stride >= (long long)a.N * a.N, "abx_ensemble_pairs: plane_stride below N * N");
     const int P = a.M * a.atoms;
     const long long bytes = pairs_lds_bytes(P);
-    ABX_REQUIRE(bytes <= LDS_LIMIT, "abx_ensemble_pairs: the tile does not fit the LDS of a CU");
+    ABX_REQUIRE(bytes <= ABX_LDS_LIMIT, "abx_ensemble_pairs: the tile does not fit the LDS of a CU");
     if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(ens_pairs_kernel), (int)pairs_lds_bytes(MAXP), "abx_ensemble_pairs")) return rc;
     const int nt = (a.N + T - 1) / T;
     hipLaunchKernelGGL(ens_pairs_kernel, dim3(nt, nt), dim3(64), (int)bytes, st, a);

@@ -20,6 +20,8 @@
 // d <= R_a + R_b + 1e-12, six orders inside the slack.
 #include "common.h"
 #include "abx_hip.h"
+#include "reduce_dev.h"
+#include "structure_dev.h"
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -30,7 +32,6 @@ constexpr int NTB = 1024;              // threads of the point kernel
 constexpr int NWB = NTB / 64;          // its waves
 constexpr int CAP = 192;               // neighbour list entries per wave (worked off when fewer than 64 are free)
 constexpr int TILE = 128;              // atoms per workgroup of the point kernel (8 per wave), by which the grid is sized
-constexpr long long LDS_LIMIT = 160 * 1024;
 constexpr double SLACK = 1e-3;         // Angstrom added to R_a + R_b in the neighbour prefilter
 constexpr double FOUR_PI = 12.566370614359172;
 
@@ -38,37 +39,7 @@ __host__ __device__ constexpr long long points_lds_bytes(int L) { return 14ll * 
 // bytes of one structure's workspace: header (16), float4 table, int4 per slot, int tag - a multiple of 16
 __host__ __device__ constexpr long long ws_stride(int L) { return (16 + 14ll * L * 36 + 15) / 16 * 16; }
 
-// One structure of the batch: rows < Lpred from the prediction, the rest from the ground truth (the conventions of AbxDesignScoreArgs)
-struct Structure {
-    const float* pred; const float* gt;
-    const long long* pseq; const long long* gseq;
-    const unsigned char* pmask; const unsigned char* gexists; const unsigned char* rmask;
-    const float* radius;
-    int Lab, Lpred;
-    __device__ __forceinline__ Structure(const AbxInterfaceArgs& a, int b) {
-        pred = a.pred_atom14 + (long long)b * a.pred_sb;
-        gt = a.gt_atom14;
-        pseq = a.pred_seq + (long long)b * a.pred_seq_sb;
-        gseq = a.gt_seq;
-        pmask = a.pred_mask ? a.pred_mask + (long long)b * a.L * 14 : nullptr;
-        gexists = a.gt_exists;
-        rmask = a.res_mask;
-        radius = a.radius;
-        Lab = a.Lab; Lpred = a.Lpred;
-    }
-    __device__ __forceinline__ int aatype(int res) const {
-        const long long aa = res < Lab ? pseq[res] : gseq[res];
-        return aa < 0 ? 20 : (aa > 20 ? 20 : (int)aa);
-    }
-    __device__ __forceinline__ const float* xyz(int res, int slot) const {
-        return (res < Lpred ? pred : gt) + ((long long)res * 14 + slot) * 3;
-    }
-    __device__ __forceinline__ bool exists(int res, int slot, int aa) const {
-        if (rmask && !rmask[res]) return false;
-        if (pmask) return pmask[(long long)res * 14 + slot] != 0;
-        return res < Lpred ? radius[aa * 14 + slot] > 0.f : gexists[(long long)res * 14 + slot] != 0;
-    }
-};
+using Structure = StructureView<AbxInterfaceArgs>;
 
 struct Workspace {
     int* hdr; float4* tab; int4* slot; int* tag;
@@ -80,10 +51,6 @@ struct Workspace {
         tag = reinterpret_cast<int*>(p + 16 + 14ll * L * 32);
     }
 };
-
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 __global__ __launch_bounds__(256) void iface_table_kernel(const AbxInterfaceArgs a, unsigned char* __restrict__ ws) {
     __shared__ int wcnt[4];
@@ -216,20 +183,6 @@ __global__ __launch_bounds__(NTB) void iface_points_kernel(const AbxInterfaceArg
 }
 
 constexpr int NSUM = 12;
-// Sum of NSUM doubles per thread over the 256 threads of the block, in a fixed order; every thread returns with the totals
-__device__ __forceinline__ void block_sum(double (&v)[NSUM], double* sh) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < NSUM; ++k) v[k] = wave_sum_d(v[k]);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < NSUM; ++k) sh[(tid >> 6) * NSUM + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NSUM; ++k) v[k] = (sh[k] + sh[NSUM + k]) + (sh[2 * NSUM + k] + sh[3 * NSUM + k]);
-}
-
 __global__ __launch_bounds__(256) void iface_row_kernel(const AbxInterfaceArgs a, const unsigned char* __restrict__ ws) {
     __shared__ double red[4 * NSUM];
     const int b = blockIdx.x, tid = threadIdx.x, L = a.L;
@@ -270,7 +223,7 @@ __global__ __launch_bounds__(256) void iface_row_kernel(const AbxInterfaceArgs a
             if (reg) v[8] += 1.0;
         }
     }
-    block_sum(v, red);
+    block_sum_d<NSUM>(v, red);
     if (tid < NSUM) {
         double r = v[0];
 #pragma unroll
@@ -289,22 +242,19 @@ extern "C" long long abx_interface_scores_workspace_bytes(int B, int L, int P) {
 extern "C" int abx_interface_scores(const AbxInterfaceArgs* ap, void* workspace, hipStream_t st) {
     ABX_REQUIRE(ap != nullptr, "abx_interface_scores: null");
     const AbxInterfaceArgs a = *ap;
-    ABX_REQUIRE(a.B > 0 && a.L > 0 && a.B <= 65535, "abx_interface_scores: bad sizes");
-    ABX_REQUIRE(a.Lab > 0 && a.Lab <= a.L, "abx_interface_scores: Lab must be in 1..L");
-    ABX_REQUIRE(a.Lpred >= a.Lab && a.Lpred <= a.L, "abx_interface_scores: Lpred must be in Lab..L");
-    ABX_REQUIRE(a.pred_atom14 && a.pred_seq && a.gt_atom14 && a.gt_exists && a.gt_seq && a.radius && a.sphere && a.out,
-                "abx_interface_scores: null operand");
+    if (int rc = abx_check_structure_args(a, "abx_interface_scores", 1)) return rc;
+    ABX_REQUIRE(a.sphere && a.out, "abx_interface_scores: null operand");
     ABX_REQUIRE(a.P >= 1 && a.P <= 1024, "abx_interface_scores: P must be in 1..1024");
     ABX_REQUIRE(a.out_stride >= ABX_IFACE_COLS, "abx_interface_scores: out_stride below ABX_IFACE_COLS");
     ABX_REQUIRE(std::isfinite(a.probe) && a.probe >= 0.0, "abx_interface_scores: probe must be >= 0");
     ABX_REQUIRE(std::isfinite(a.cutoff) && a.cutoff > 0.0, "abx_interface_scores: cutoff must be > 0");
-    ABX_REQUIRE(points_lds_bytes(a.L) <= LDS_LIMIT, "abx_interface_scores: the atom table does not fit the LDS of a CU (L <= 541)");
+    ABX_REQUIRE(points_lds_bytes(a.L) <= ABX_LDS_LIMIT, "abx_interface_scores: the atom table does not fit the LDS of a CU (L <= 541)");
     ABX_REQUIRE(workspace != nullptr, "abx_interface_scores: null workspace");
     unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
     hipLaunchKernelGGL(iface_table_kernel, dim3(a.B), dim3(256), 0, st, a, ws);
     int rc = abx_check_launch("abx_interface_scores(atom table)");
     if (rc) return rc;
-    rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(iface_points_kernel), (int)LDS_LIMIT, "abx_interface_scores");
+    rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(iface_points_kernel), ABX_LDS_LIMIT, "abx_interface_scores");
     if (rc) return rc;
     const int tiles = (a.L * 14 + TILE - 1) / TILE;
     hipLaunchKernelGGL(iface_points_kernel, dim3(tiles, a.B), dim3(NTB), (int)points_lds_bytes(a.L), st, a, ws);

@@ -16,56 +16,28 @@
 #include "common.h"
 #include "abx_hip.h"
 #include "peptide_dev.h"
+#include "reduce_dev.h"
+#include "structure_dev.h"
 
 namespace {
 
 constexpr int RT = 16;                 // residues per tile
 constexpr int AT = RT * 14;            // atoms per tile (224)
 
-// One structure of the batch as the kernels read it: rows < Lpred from the prediction, the rest from the ground truth
-struct Structure {
-    const float* pred; const float* gt;
-    const long long* pseq; const long long* gseq;
-    const unsigned char* pmask; const unsigned char* gexists; const unsigned char* rmask;
+// The structure view (structure_dev.h) with what the peptide links need; the complex is shared by the batch or one per structure
+struct Structure : StructureView<AbxDesignScoreArgs> {
     const int* chain; const int* residx;
-    const float* radius;
-    int L, Lab, Lpred;
-    __device__ __forceinline__ Structure(const AbxDesignScoreArgs& a, int b) {
-        const long long g = a.complex_batched ? (long long)b * a.L : 0;
-        pred = a.pred_atom14 + (long long)b * a.pred_sb;
-        gt = a.gt_atom14 + g * 42;
-        pseq = a.pred_seq + (long long)b * a.pred_seq_sb;
-        gseq = a.gt_seq + g;
-        pmask = a.pred_mask ? a.pred_mask + (long long)b * a.L * 14 : nullptr;
-        gexists = a.gt_exists + g * 14;
-        rmask = a.res_mask;
+    int L;
+    __device__ __forceinline__ Structure(const AbxDesignScoreArgs& a, int b) : Structure(a, b, a.complex_batched ? (long long)b * a.L : 0) {}
+    __device__ __forceinline__ Structure(const AbxDesignScoreArgs& a, int b, long long g) : StructureView<AbxDesignScoreArgs>(a, b, g) {
         chain = a.chain_id + g;
         residx = a.residx ? a.residx + g : nullptr;
-        radius = a.radius;
-        L = a.L; Lab = a.Lab; Lpred = a.Lpred;
-    }
-    __device__ __forceinline__ int aatype(int res) const {
-        const long long aa = res < Lab ? pseq[res] : gseq[res];
-        return aa < 0 ? 20 : (aa > 20 ? 20 : (int)aa);
-    }
-    __device__ __forceinline__ const float* xyz(int res, int slot) const {
-        return (res < Lpred ? pred : gt) + ((long long)res * 14 + slot) * 3;
-    }
-    __device__ __forceinline__ bool exists(int res, int slot, int aa) const {
-        if (rmask && !rmask[res]) return false;
-        if (pmask) return pmask[(long long)res * 14 + slot] != 0;
-        return res < Lpred ? radius[aa * 14 + slot] > 0.f : gexists[(long long)res * 14 + slot] != 0;
+        L = a.L;
     }
     __device__ __forceinline__ bool linked_to_prev(int res) const {
         return res > 0 && res < L && linked_rows(chain, residx, res);
     }
 };
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void clash_count_kernel(const AbxDesignScoreArgs a, unsigned long long* __restrict__ part) {
     __shared__ float4 tile[AT];        // x, y, z, radius (radius < 0: atom absent)
@@ -142,62 +114,6 @@ __global__ __launch_bounds__(256) void clash_count_kernel(const AbxDesignScoreAr
     }
 }
 
-// Sum of N doubles per thread over the block, in a fixed order; every thread returns with the totals in v.  `sh`: [4][N] doubles.
-template <int N>
-__device__ __forceinline__ void block_sum_d(double (&v)[N], double* sh) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = wave_sum_d(v[k]);
-    __syncthreads();                                   // the previous use of sh is over
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) sh[(tid >> 6) * N + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = (sh[k] + sh[N + k]) + (sh[2 * N + k] + sh[3 * N + k]);
-}
-
-// Eigenvectors of the symmetric 4x4 matrix A (LDS) by cyclic Jacobi rotations, accumulated in V (LDS).  One thread.  A rotation
-// zeroes A[p][q] exactly; the sweeps stop when the off-diagonal mass is below 1e-36 of the matrix (quadratic convergence: 5-7 sweeps).
-__device__ void jacobi4(double (*A)[4], double (*V)[4]) {
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 24; ++sweep) {
-        double off = 0.0, all = 0.0;
-        for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) {
-                all += A[i][j] * A[i][j];
-                if (i < j) off += A[i][j] * A[i][j];
-            }
-        if (off <= 1e-36 * all) break;
-        for (int p = 0; p < 3; ++p)
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-                for (int k = 0; k < 4; ++k) {
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - sn * akq;
-                    A[k][q] = sn * akp + c * akq;
-                }
-                for (int k = 0; k < 4; ++k) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - sn * aqk;
-                    A[q][k] = sn * apk + c * aqk;
-                }
-                A[p][q] = A[q][p] = 0.0;
-                for (int k = 0; k < 4; ++k) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - sn * vkq;
-                    V[k][q] = sn * vkp + c * vkq;
-                }
-            }
-    }
-}
-
 constexpr int NREG = 7;                // heavy cdr1 / cdr2 / cdr3, light cdr1 / cdr2 / cdr3, heavy cdr3 Loop
 __global__ __launch_bounds__(256) void score_row_kernel(const AbxDesignScoreArgs a, const unsigned long long* __restrict__ part, int nparts) {
     __shared__ double red[4 * 21];
@@ -235,26 +151,7 @@ __global__ __launch_bounds__(256) void score_row_kernel(const AbxDesignScoreArgs
         S[6] += gz * px; S[7] += gz * py; S[8] += gz * pz;
     }
     block_sum_d<9>(S, red);
-    if (tid == 0) {
-        // Horn 1987: the unit quaternion of the optimal proper rotation is the eigenvector of the largest eigenvalue of N
-        const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
-        Nm[0][0] = Sxx + Syy + Szz; Nm[0][1] = Syz - Szy;       Nm[0][2] = Szx - Sxz;        Nm[0][3] = Sxy - Syx;
-        Nm[1][1] = Sxx - Syy - Szz; Nm[1][2] = Sxy + Syx;       Nm[1][3] = Szx + Sxz;
-        Nm[2][2] = -Sxx + Syy - Szz; Nm[2][3] = Syz + Szy;
-        Nm[3][3] = -Sxx - Syy + Szz;
-        for (int i = 1; i < 4; ++i)
-            for (int j = 0; j < i; ++j) Nm[i][j] = Nm[j][i];
-        jacobi4(Nm, Vm);
-        int im = 0;
-        for (int i = 1; i < 4; ++i)
-            if (Nm[i][i] > Nm[im][im]) im = i;
-        double qw = Vm[0][im], qx = Vm[1][im], qy = Vm[2][im], qz = Vm[3][im];
-        const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-        qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-        Rs[0] = 1.0 - 2.0 * (qy * qy + qz * qz); Rs[1] = 2.0 * (qx * qy - qw * qz);       Rs[2] = 2.0 * (qx * qz + qw * qy);
-        Rs[3] = 2.0 * (qx * qy + qw * qz);       Rs[4] = 1.0 - 2.0 * (qx * qx + qz * qz); Rs[5] = 2.0 * (qy * qz - qw * qx);
-        Rs[6] = 2.0 * (qx * qz - qw * qy);       Rs[7] = 2.0 * (qy * qz + qw * qx);       Rs[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
-    }
+    if (tid == 0) horn_rotation_lds(S, Nm, Vm, Rs);
     __syncthreads();
     double R[9];
 #pragma unroll
@@ -348,11 +245,8 @@ extern "C" long long abx_design_scores_workspace_bytes(int B, int L) {
 extern "C" int abx_design_scores(const AbxDesignScoreArgs* ap, void* workspace, hipStream_t st) {
     ABX_REQUIRE(ap != nullptr, "abx_design_scores: null");
     const AbxDesignScoreArgs a = *ap;
-    ABX_REQUIRE(a.B > 0 && a.L > 1 && a.B <= 65535 && a.L < (1 << 22), "abx_design_scores: bad sizes");
-    ABX_REQUIRE(a.Lab > 0 && a.Lab <= a.L, "abx_design_scores: Lab must be in 1..L");
-    ABX_REQUIRE(a.Lpred >= a.Lab && a.Lpred <= a.L, "abx_design_scores: Lpred must be in Lab..L");
-    ABX_REQUIRE(a.pred_atom14 && a.pred_seq && a.gt_atom14 && a.gt_exists && a.gt_seq && a.cdr_def && a.chain_id && a.radius && a.out,
-                "abx_design_scores: null operand");
+    if (int rc = abx_check_structure_args(a, "abx_design_scores", 2)) return rc;
+    ABX_REQUIRE(a.cdr_def && a.chain_id && a.out, "abx_design_scores: null operand");
     ABX_REQUIRE(a.out_stride >= ABX_SCORE_COLS, "abx_design_scores: out_stride below ABX_SCORE_COLS");
     ABX_REQUIRE(workspace != nullptr, "abx_design_scores: null workspace");
     const int nparts = (a.L + RT - 1) / RT;

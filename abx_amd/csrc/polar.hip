@@ -14,6 +14,8 @@
 //      loop: per thread in slot order, wave shuffles, then the 16 partials in wave order.
 #include "common.h"
 #include "abx_hip.h"
+#include "reduce_dev.h"
+#include "structure_dev.h"
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -23,7 +25,6 @@ namespace {
 constexpr int NT = 1024;               // threads of the workgroup
 constexpr int NW = NT / 64;            // its waves
 constexpr int PER_RES = 5;             // table entries per residue row the LDS is sized for
-constexpr long long LDS_LIMIT = 160 * 1024;
 constexpr double FOUR_PI = 12.566370614359172;
 constexpr int NCNT = 16;               // integer counters (the columns 0-9 and 12)
 
@@ -33,41 +34,7 @@ constexpr int F_BB = 1 << 4, F_REGION = 1 << 5, F_SIDEB = 1 << 6;      // bits 8
 // two float4 and two counters per entry, four counters per row, the counters and the area partials
 __host__ __device__ constexpr long long polar_lds_bytes(int L) { return (40ll * PER_RES + 16) * L + 512; }
 
-// One structure of the batch: rows < Lpred from the prediction, the rest from the ground truth (the conventions of AbxInterfaceArgs)
-struct Structure {
-    const float* pred; const float* gt;
-    const long long* pseq; const long long* gseq;
-    const unsigned char* pmask; const unsigned char* gexists; const unsigned char* rmask;
-    const float* radius;
-    int Lab, Lpred;
-    __device__ __forceinline__ Structure(const AbxPolarArgs& a, int b) {
-        pred = a.pred_atom14 + (long long)b * a.pred_sb;
-        gt = a.gt_atom14;
-        pseq = a.pred_seq + (long long)b * a.pred_seq_sb;
-        gseq = a.gt_seq;
-        pmask = a.pred_mask ? a.pred_mask + (long long)b * a.L * 14 : nullptr;
-        gexists = a.gt_exists;
-        rmask = a.res_mask;
-        radius = a.radius;
-        Lab = a.Lab; Lpred = a.Lpred;
-    }
-    __device__ __forceinline__ int aatype(int res) const {
-        const long long aa = res < Lab ? pseq[res] : gseq[res];
-        return aa < 0 ? 20 : (aa > 20 ? 20 : (int)aa);
-    }
-    __device__ __forceinline__ const float* xyz(int res, int slot) const {
-        return (res < Lpred ? pred : gt) + ((long long)res * 14 + slot) * 3;
-    }
-    __device__ __forceinline__ bool exists(int res, int slot, int aa) const {
-        if (rmask && !rmask[res]) return false;
-        if (pmask) return pmask[(long long)res * 14 + slot] != 0;
-        return res < Lpred ? radius[aa * 14 + slot] > 0.f : gexists[(long long)res * 14 + slot] != 0;
-    }
-};
-
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
+using Structure = StructureView<AbxPolarArgs>;
 
 __device__ __forceinline__ bool salt_roles(int fa, int fb) {
     return ((fa & ABX_POLAR_CATION) && (fb & ABX_POLAR_ANION)) || ((fa & ABX_POLAR_ANION) && (fb & ABX_POLAR_CATION));
@@ -292,11 +259,8 @@ extern "C" int abx_polar_scores(const AbxPolarArgs* ap, void* workspace, hipStre
     (void)workspace;
     ABX_REQUIRE(ap != nullptr, "abx_polar_scores: null");
     const AbxPolarArgs a = *ap;
-    ABX_REQUIRE(a.B > 0 && a.L > 0 && a.B <= 65535, "abx_polar_scores: bad sizes");
-    ABX_REQUIRE(a.Lab > 0 && a.Lab <= a.L, "abx_polar_scores: Lab must be in 1..L");
-    ABX_REQUIRE(a.Lpred >= a.Lab && a.Lpred <= a.L, "abx_polar_scores: Lpred must be in Lab..L");
-    ABX_REQUIRE(a.pred_atom14 && a.pred_seq && a.gt_atom14 && a.gt_exists && a.gt_seq && a.radius && a.table && a.out,
-                "abx_polar_scores: null operand");
+    if (int rc = abx_check_structure_args(a, "abx_polar_scores", 1)) return rc;
+    ABX_REQUIRE(a.table && a.out, "abx_polar_scores: null operand");
     ABX_REQUIRE(a.out_stride >= ABX_POLAR_COLS, "abx_polar_scores: out_stride below ABX_POLAR_COLS");
     ABX_REQUIRE(std::isfinite(a.hb_min) && std::isfinite(a.hb_max) && a.hb_min >= 0.0 && a.hb_min <= a.hb_max,
                 "abx_polar_scores: needs 0 <= hb_min <= hb_max");
@@ -310,8 +274,8 @@ extern "C" int abx_polar_scores(const AbxPolarArgs* ap, void* workspace, hipStre
         ABX_REQUIRE(a.P >= 1 && a.P <= 1024, "abx_polar_scores: P must be in 1..1024");
         ABX_REQUIRE(std::isfinite(a.probe) && a.probe >= 0.0, "abx_polar_scores: probe must be >= 0");
     }
-    ABX_REQUIRE(polar_lds_bytes(a.L) <= LDS_LIMIT, "abx_polar_scores: the polar-atom table does not fit the LDS of a CU (L <= 756)");
-    int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(polar_kernel), (int)LDS_LIMIT, "abx_polar_scores");
+    ABX_REQUIRE(polar_lds_bytes(a.L) <= ABX_LDS_LIMIT, "abx_polar_scores: the polar-atom table does not fit the LDS of a CU (L <= 756)");
+    int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(polar_kernel), ABX_LDS_LIMIT, "abx_polar_scores");
     if (rc) return rc;
     hipLaunchKernelGGL(polar_kernel, dim3(a.B), dim3(NT), (int)polar_lds_bytes(a.L), st, a, cos2);
     return abx_check_launch("abx_polar_scores");

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "abx_hip.h"
 #include "peptide_dev.h"
+#include "structure_dev.h"
 
 namespace {
 
@@ -29,42 +30,10 @@ constexpr int NT = 1024;               // threads per workgroup
 constexpr int GS = 16;                 // lanes that share one movable atom
 constexpr int NG = NT / GS;            // movable atoms per pass
 constexpr int NW = NT / 64;            // waves
-constexpr long long LDS_LIMIT = 160 * 1024;
 
 __host__ __device__ constexpr long long lds_bytes(int L, int M) { return 232ll * L + 340ll * M + 1024; }
 
-// One structure of the batch as the kernel reads it: rows < Lpred from the prediction, the rest from the ground truth (the
-// conventions of AbxDesignScoreArgs, complex shared by the batch)
-struct Structure {
-    const float* pred; const float* gt;
-    const long long* pseq; const long long* gseq;
-    const unsigned char* pmask; const unsigned char* gexists; const unsigned char* rmask;
-    const float* radius;
-    int Lab, Lpred;
-    __device__ __forceinline__ Structure(const AbxRelaxArgs& a, int b) {
-        pred = a.pred_atom14 + (long long)b * a.pred_sb;
-        gt = a.gt_atom14;
-        pseq = a.pred_seq + (long long)b * a.pred_seq_sb;
-        gseq = a.gt_seq;
-        pmask = a.pred_mask ? a.pred_mask + (long long)b * a.L * 14 : nullptr;
-        gexists = a.gt_exists;
-        rmask = a.res_mask;
-        radius = a.radius;
-        Lab = a.Lab; Lpred = a.Lpred;
-    }
-    __device__ __forceinline__ int aatype(int res) const {
-        const long long aa = res < Lab ? pseq[res] : gseq[res];
-        return aa < 0 ? 20 : (aa > 20 ? 20 : (int)aa);
-    }
-    __device__ __forceinline__ const float* xyz(int res, int slot) const {
-        return (res < Lpred ? pred : gt) + ((long long)res * 14 + slot) * 3;
-    }
-    __device__ __forceinline__ bool exists(int res, int slot, int aa) const {
-        if (rmask && !rmask[res]) return false;
-        if (pmask) return pmask[(long long)res * 14 + slot] != 0;
-        return res < Lpred ? radius[aa * 14 + slot] > 0.f : gexists[(long long)res * 14 + slot] != 0;
-    }
-};
+using Structure = StructureView<AbxRelaxArgs>;      // (the complex is shared by the batch)
 
 // rinfo bits of a row
 constexpr int R_LINK = 1, R_MOV = 2, R_CYS = 4, R_AA_SHIFT = 8;
@@ -411,18 +380,15 @@ extern "C" int abx_relax(const AbxRelaxArgs* ap, void* workspace, hipStream_t st
     (void)workspace;
     ABX_REQUIRE(ap != nullptr, "abx_relax: null");
     const AbxRelaxArgs a = *ap;
-    ABX_REQUIRE(a.B > 0 && a.L > 1 && a.B <= 65535 && a.L < (1 << 22), "abx_relax: bad sizes (B > 0, L > 1)");
-    ABX_REQUIRE(a.Lab > 0 && a.Lab <= a.L, "abx_relax: Lab must be in 1..L");
-    ABX_REQUIRE(a.Lpred >= a.Lab && a.Lpred <= a.L, "abx_relax: Lpred must be in Lab..L");
+    if (int rc = abx_check_structure_args(a, "abx_relax", 2)) return rc;
     ABX_REQUIRE(a.M > 0 && a.M <= a.Lpred, "abx_relax: M (movable residues) must be in 1..Lpred");
-    ABX_REQUIRE(lds_bytes(a.L, a.M) <= LDS_LIMIT, "abx_relax: the structure does not fit the LDS-resident atom table (232 L + 340 M + 1024 bytes > 160 KB)");
-    ABX_REQUIRE(a.pred_atom14 && a.pred_seq && a.gt_atom14 && a.gt_exists && a.gt_seq && a.chain_id && a.movable && a.radius && a.chi_axis &&
-                    a.rigid_group && a.out_atom14 && a.report, "abx_relax: null operand");
+    ABX_REQUIRE(lds_bytes(a.L, a.M) <= ABX_LDS_LIMIT, "abx_relax: the structure does not fit the LDS-resident atom table (232 L + 340 M + 1024 bytes > 160 KB)");
+    ABX_REQUIRE(a.chain_id && a.movable && a.chi_axis && a.rigid_group && a.out_atom14 && a.report, "abx_relax: null operand");
     ABX_REQUIRE(a.out_sb >= (long long)a.Lpred * 42 && a.report_stride >= ABX_RELAX_COLS, "abx_relax: out_sb below Lpred * 42 or report_stride below ABX_RELAX_COLS");
     ABX_REQUIRE(a.max_iter >= 0 && a.eta0 > 0.f && a.rho > 0.f && a.grow >= 1.f && a.shrink > 0.f && a.shrink < 1.f && a.k_restraint >= 0.f,
                 "abx_relax: bad parameters (max_iter >= 0, eta0 > 0, rho > 0, grow >= 1, 0 < shrink < 1, k_restraint >= 0)");
     const int bytes = (int)lds_bytes(a.L, a.M);
-    if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(relax_kernel), (int)LDS_LIMIT, "abx_relax")) return rc;
+    if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(relax_kernel), ABX_LDS_LIMIT, "abx_relax")) return rc;
     hipLaunchKernelGGL(relax_kernel, dim3(a.B), dim3(NT), bytes, st, a);
     return abx_check_launch("abx_relax");
 }

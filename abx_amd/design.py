@@ -165,36 +165,30 @@ def _write_relax(out_dir, cname, rows, scored):
     return tsv
 
 
-def _write_interface(out_dir, cname, wild, rows, relaxed):
-    """<out_dir>/<complex>_interface.tsv: the `wild` line, then (sample id, values) per sample; values = the interface.INTERFACE_COLUMNS row
-    and, when relaxed, the row of the relaxed structure.  After the columns: delta_<column> = row minus wild for interface.DELTA_COLUMNS."""
-    from .interface import DELTA_COLUMNS, INTERFACE_COLUMNS, format_delta, format_interface
-    NI = len(INTERFACE_COLUMNS)
-    tsv = os.path.join(out_dir, f'{cname}_interface.tsv')
+def _write_with_wild_deltas(kind, out_dir, cname, wild, rows, relaxed):
+    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar): the `wild` line, then (sample id, values)
+    per sample; values = the module's <KIND>_COLUMNS row and, when relaxed, the row of the relaxed structure.  After the columns:
+    delta_<column> = row minus wild for the module's DELTA_COLUMNS."""
+    import importlib
+    mod = importlib.import_module(f'.{kind}', __package__)
+    columns, fmt = getattr(mod, f'{kind.upper()}_COLUMNS'), getattr(mod, f'format_{kind}')
+    N = len(columns)
+    tsv = os.path.join(out_dir, f'{cname}_{kind}.tsv')
     with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(INTERFACE_COLUMNS + tuple('delta_' + c for c in DELTA_COLUMNS) +
-                                       (tuple(c + '_relaxed' for c in INTERFACE_COLUMNS) if relaxed else ())) + '\n')
-        f.write('wild\t' + '\t'.join(format_interface(wild) + format_delta(wild, wild) + (['nan'] * NI if relaxed else [])) + '\n')
+        f.write('sample\t' + '\t'.join(columns + tuple('delta_' + c for c in mod.DELTA_COLUMNS) +
+                                       (tuple(c + '_relaxed' for c in columns) if relaxed else ())) + '\n')
+        f.write('wild\t' + '\t'.join(fmt(wild) + mod.format_delta(wild, wild) + (['nan'] * N if relaxed else [])) + '\n')
         for i, v in rows:
-            f.write(f'{i}\t' + '\t'.join(format_interface(v[:NI]) + format_delta(v[:NI], wild) +
-                                          (format_interface(v[NI:2 * NI]) if relaxed else [])) + '\n')
+            f.write(f'{i}\t' + '\t'.join(fmt(v[:N]) + mod.format_delta(v[:N], wild) + (fmt(v[N:2 * N]) if relaxed else [])) + '\n')
     return tsv
+
+
+def _write_interface(out_dir, cname, wild, rows, relaxed):
+    return _write_with_wild_deltas('interface', out_dir, cname, wild, rows, relaxed)
 
 
 def _write_polar(out_dir, cname, wild, rows, relaxed):
-    """<out_dir>/<complex>_polar.tsv: the `wild` line, then (sample id, values) per sample; values = the polar.POLAR_COLUMNS row and, when
-    relaxed, the row of the relaxed structure.  After the columns: delta_<column> = row minus wild for polar.DELTA_COLUMNS."""
-    from .polar import DELTA_COLUMNS, POLAR_COLUMNS, format_delta, format_polar
-    NP = len(POLAR_COLUMNS)
-    tsv = os.path.join(out_dir, f'{cname}_polar.tsv')
-    with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(POLAR_COLUMNS + tuple('delta_' + c for c in DELTA_COLUMNS) +
-                                       (tuple(c + '_relaxed' for c in POLAR_COLUMNS) if relaxed else ())) + '\n')
-        f.write('wild\t' + '\t'.join(format_polar(wild) + format_delta(wild, wild) + (['nan'] * NP if relaxed else [])) + '\n')
-        for i, v in rows:
-            f.write(f'{i}\t' + '\t'.join(format_polar(v[:NP]) + format_delta(v[:NP], wild) +
-                                          (format_polar(v[NP:2 * NP]) if relaxed else [])) + '\n')
-    return tsv
+    return _write_with_wild_deltas('polar', out_dir, cname, wild, rows, relaxed)
 
 
 def _write_accuracy(out_dir, cname, wild, rows, relaxed):

@@ -8,7 +8,11 @@ as the patch holds every antigen atom near the antibody, `sasa_antigen` and `sas
 Shrake-Rupley on a golden-spiral point set, heavy atoms of the atom14 slots with the project's van-der-Waals radii plus a probe, point
 tests in float64 in a fixed IEEE operation order (include/abx_hip.h, AbxInterfaceArgs): the point counts of the device
 (`InterfaceScorer`, abx_interface_scores, csrc/interface.hip) and of the host twin (`interface_host`, numpy) are equal integers."""
+import functools
+
 import numpy as np
+
+from . import complex_view
 
 # The row of abx_interface_scores (include/abx_hip.h, ABX_IFACE_COLS)
 INTERFACE_COLUMNS = ('sasa_complex', 'sasa_antibody', 'sasa_antigen', 'dsasa_int', 'dsasa_antibody', 'dsasa_region',
@@ -19,19 +23,10 @@ DELTA_COLUMNS = ('dsasa_int', 'dsasa_antibody', 'dsasa_region', 'n_contact', 'n_
 FOUR_PI = 12.566370614359172
 
 
-def format_interface(row):
-    """One row as TSV fields: %.2f for the areas (square Angstrom), integers for the counts."""
-    return [str(int(v)) if c in COUNT_COLUMNS else f'{float(v):.2f}' for c, v in zip(INTERFACE_COLUMNS, row)]
-
-
-def format_delta(row, wild):
-    """design minus wild type for DELTA_COLUMNS, signed: %+.2f for the areas, %+d for the counts."""
-    out = []
-    for c in DELTA_COLUMNS:
-        k = INTERFACE_COLUMNS.index(c)
-        d = float(row[k]) - float(wild[k])
-        out.append(f'{int(round(d)):+d}' if c in COUNT_COLUMNS else f'{d:+.2f}')
-    return out
+# format_interface(row): %.2f for the areas (square Angstrom), integers for the counts; format_delta(row, wild): design minus wild type
+# for DELTA_COLUMNS, signed
+format_interface = functools.partial(complex_view.format_row, INTERFACE_COLUMNS, COUNT_COLUMNS, 2)
+format_delta = functools.partial(complex_view.format_delta, INTERFACE_COLUMNS, COUNT_COLUMNS, DELTA_COLUMNS, 2)
 
 
 def golden_spiral(P):
@@ -58,31 +53,20 @@ def sphere_points(P, device='cpu'):
     return _SPHERE[key]
 
 
-class InterfaceScorer:
+class InterfaceScorer(complex_view.ComplexView):
     """Interface rows of batches of designs of ONE complex on the device.  Built once per complex from its featurised batch (or the
     un-batched complex) like metrics.DesignScorer.  region: (L) mask of the rows the `*_region` columns count (default: the rows the
     sampler diffuses, sample 0's (1 - fixed_mask) * backbone mask).  n_points: sphere points per atom (128: two per lane of a wave);
     probe: probe radius; cutoff: contact distance of heavy atoms (Angstrom)."""
 
+    COLUMNS = INTERFACE_COLUMNS
+
     def __init__(self, batch, region=None, n_points=128, probe=1.4, cutoff=4.0):
-        import torch
-        one = (lambda k: batch[k][0]) if batch['seq'].dim() == 2 else (lambda k: batch[k])
-        self.Lab = int(batch['anchor_flag'].shape[-1])
-        self.gt_atom14 = one('atom14_gt_positions').to(torch.float32).contiguous()
-        self.gt_exists = one('atom14_gt_exists').to(torch.uint8).contiguous()
-        self.gt_seq = one('seq').to(torch.int64).contiguous()
-        self.res_mask = one('mask').to(torch.uint8).contiguous() if 'mask' in batch else None
+        super().__init__(batch)
         dev = self.gt_atom14.device
-        if region is None:
-            region = (1 - one('fixed_mask')) * one('atom14_gt_exists')[..., 0]
-        self.region = (torch.as_tensor(region).to(dev) != 0).to(torch.uint8).contiguous()
+        self.region = complex_view.region_mask(batch, region, dev)
         self.sphere = sphere_points(n_points, dev)
         self.kw = dict(probe=float(probe), cutoff=float(cutoff))
-
-    def new_table(self, *lead):
-        """An uninitialised (*lead, len(INTERFACE_COLUMNS)) float64 table on the complex's device for `score(..., out=table[i])`."""
-        import torch
-        return torch.empty(*lead, len(INTERFACE_COLUMNS), dtype=torch.float64, device=self.gt_atom14.device)
 
     def score(self, atom14, seq, out=None, points=None, mask=None):
         """atom14 (B, Lab or L, 14, 3) f32 predicted coordinates (antibody only: the antigen is the ground truth's), seq (B, Lab) tokens
@@ -92,10 +76,7 @@ class InterfaceScorer:
         return ops.interface_scores(atom14, seq, self.gt_atom14, self.gt_seq, self.gt_exists, self.sphere, Lab=self.Lab, region=self.region,
                                     mask=mask, res_mask=self.res_mask, out=out, points=points, **self.kw)
 
-    def wild(self, points=None):
-        """(1, len(INTERFACE_COLUMNS)): the row of the ground-truth complex itself with its own atoms (the counterpart of upstream's
-        dG_wild: a design's row minus this one is the geometric analogue of ddG)."""
-        return self.score(self.gt_atom14[None, :self.Lab], self.gt_seq[None, :self.Lab], points=points, mask=self.gt_exists[None])
+    # wild(points=None): the counterpart of upstream's dG_wild - a design's row minus this one is the geometric analogue of ddG
 
 
 # -------------------------------------------------------------------------------------------------------------------

@@ -4,9 +4,12 @@ abx/utils.py:444-465 `kabsch_numpy`): Kabsch-aligned C-alpha RMSD and amino-acid
 On the device: `DesignScorer` (abx_design_scores, csrc/metrics.hip) scores a whole batch of designs of one complex where the sampler
 left them - the columns of `calc_ab_metrics` plus the violation counts of eval/metric_scripts/cal_vio.py:29-110 and the number of
 clashing atom pairs (`SCORE_COLUMNS`).  `violation_counts` / `clash_counts` are the host twins of the count columns (plain torch)."""
+import functools
 from collections import OrderedDict
 
 import numpy as np
+
+from . import complex_view
 
 _SCHEMA = {'cdr1': 1, 'cdr2': 3, 'cdr3': 5}
 
@@ -58,34 +61,21 @@ SCORE_COLUMNS = ('heavy_cdr1_AAR', 'heavy_cdr1_RMSD', 'heavy_cdr2_AAR', 'heavy_c
 COUNT_COLUMNS = tuple(c for c in SCORE_COLUMNS if c.startswith('n_'))
 
 
-def format_scores(row):
-    """One score row as TSV fields: %.4f for RMSD / AAR (nan for a region without residues), integers for the counts."""
-    return [str(int(v)) if c in COUNT_COLUMNS else f'{float(v):.4f}' for c, v in zip(SCORE_COLUMNS, row)]
+# format_scores(row): %.4f for RMSD / AAR (nan for a region without residues), integers for the counts
+format_scores = functools.partial(complex_view.format_row, SCORE_COLUMNS, COUNT_COLUMNS, 4)
 
 
-class DesignScorer:
+class DesignScorer(complex_view.ComplexView):
     """Scores batches of designs of ONE complex on the device.  Built once per complex from its featurised batch (or the un-batched
     complex): ground-truth atom14 / tokens / masks, cdr_def, chain ids, residue numbers, Lab = the antibody length.
     link_by_residx: array neighbours are peptide-bonded only with consecutive residue numbers (the guidance default; False: the
     chain-only rule of cal_vio.py:50)."""
 
-    def __init__(self, batch, link_by_residx=True, overlap_tolerance=1.5, bond_tolerance_factor=12.0):
-        import torch
-        one = (lambda k: batch[k][0]) if batch['seq'].dim() == 2 else (lambda k: batch[k])
-        self.Lab = int(batch['anchor_flag'].shape[-1])
-        self.gt_atom14 = one('atom14_gt_positions').to(torch.float32).contiguous()
-        self.gt_exists = one('atom14_gt_exists').to(torch.uint8).contiguous()
-        self.gt_seq = one('seq').to(torch.int64).contiguous()
-        self.cdr_def = one('cdr_def').to(torch.int32).contiguous()
-        self.chain_id = one('chain_id').to(torch.int32).contiguous()
-        self.residx = one('residx').to(torch.int32).contiguous() if link_by_residx and 'residx' in batch else None
-        self.res_mask = one('mask').to(torch.uint8).contiguous() if 'mask' in batch else None
-        self.kw = dict(overlap_tolerance=float(overlap_tolerance), bond_tolerance_factor=float(bond_tolerance_factor))
+    COLUMNS = SCORE_COLUMNS
 
-    def new_table(self, *lead):
-        """An uninitialised (*lead, len(SCORE_COLUMNS)) float64 table on the complex's device for `score(..., out=table[i])`."""
-        import torch
-        return torch.empty(*lead, len(SCORE_COLUMNS), dtype=torch.float64, device=self.gt_atom14.device)
+    def __init__(self, batch, link_by_residx=True, overlap_tolerance=1.5, bond_tolerance_factor=12.0):
+        super().__init__(batch, chains=True, link_by_residx=link_by_residx, cdr=True)
+        self.kw = dict(overlap_tolerance=float(overlap_tolerance), bond_tolerance_factor=float(bond_tolerance_factor))
 
     def score(self, atom14, seq, out=None):
         """atom14 (B, Lab or L, 14, 3) f32 predicted coordinates (antibody only: the antigen is the ground truth's), seq (B, Lab) tokens

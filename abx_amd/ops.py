@@ -1048,6 +1048,63 @@ def clash_grad(atom14, atom_mask, aatype, chain_id, frame_trans, overlap_toleran
     return energy, g_atom, g_t, g_r
 
 
+def _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region=None, lead=None, extra=()):
+    """Fill the part of a per-design descriptor that csrc/structure_dev.h reads (pred_*, masks, gt_*, optional region, radius, B, L,
+    Lab, Lpred) - the one place where the wrappers check and normalise the structure operands.  lead: the leading shape of the complex
+    tensors, (L,) shared by the batch (default) or (B, L) per structure; extra: further tensors of that leading shape.
+    -> (B, Lp, Lab, own, keep): own(t, dtype) returns the pointer of a contiguous copy that `keep` holds until the launch."""
+    B, Lp = atom14.shape[0], atom14.shape[1]
+    Lab = int(seq.shape[1] if Lab is None else Lab)
+    lead = (L,) if lead is None else lead
+    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
+    assert tuple(gt_atom14.shape) == lead + (14, 3) and tuple(gt_exists.shape) == lead + (14,) and tuple(gt_seq.shape) == lead and \
+        all(tuple(t.shape) == lead for t in extra), \
+        'complex tensors: (L,...) shared by the batch' if lead == (L,) else 'complex tensors: (L,...) shared or (B,L,...) per structure'
+    x = _f32(atom14)
+    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
+        x = x.contiguous()
+    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
+    keep = [x, sq]
+
+    def own(t, dtype):
+        t = t.to(dtype).contiguous()
+        keep.append(t)
+        return _p(t)
+
+    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
+    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
+    if mask is not None:
+        assert tuple(mask.shape) == (B, L, 14), mask.shape
+        a.pred_mask = own(mask, torch.uint8)
+    if res_mask is not None:
+        assert tuple(res_mask.shape) == (L,), res_mask.shape
+        a.res_mask = own(res_mask, torch.uint8)
+    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
+    if region is not None:
+        assert tuple(region.shape) == (L,), region.shape
+        a.region = own(region.ne(0), torch.uint8)
+    a.radius = _p(vdw_radius_table(atom14.device))
+    a.B, a.L, a.Lab = B, L, Lab
+    return B, Lp, Lab, own, keep
+
+
+def _out_rows(a, out, B, cols, device):
+    """a.out / a.out_stride: the (B, cols) float64 table, allocated here or the caller's rows (unit column stride, any row stride)."""
+    if out is None:
+        out = torch.empty(B, cols, dtype=torch.float64, device=device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (B, cols) and out.stride(1) == 1 and out.is_cuda, f'out: (B, {cols}) float64 rows'
+    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else cols
+    return out
+
+
+def _side_output(a, name, t, dtype, shape):
+    """An optional contiguous output tensor of a descriptor (points, bonds, rows, counts, contacts): checked and bound when given."""
+    if t is not None:
+        what = f"{name}: ({','.join(map(str, shape))}) {str(dtype).replace('torch.', '')}"
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.is_cuda, what
+        setattr(a, name, _p(t))
+
+
 def design_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, cdr_def, chain_id, Lab=None, residx=None, mask=None, res_mask=None,
                   overlap_tolerance=1.5, bond_tolerance_factor=12.0, out=None):
     """Per-structure design scores (abx_design_scores; columns: abx_amd.metrics.SCORE_COLUMNS).
@@ -1060,46 +1117,18 @@ def design_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, cdr_def, chain_id, 
     lib = _lib.load()
     dev = atom14.device
     L = cdr_def.shape[-1]
-    B, Lp = atom14.shape[0], atom14.shape[1]
-    Lab = int(seq.shape[1] if Lab is None else Lab)
     batched = gt_atom14.dim() == 4
-    lead = (B, L) if batched else (L,)
-    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
-    assert tuple(gt_atom14.shape) == lead + (14, 3) and tuple(gt_exists.shape) == lead + (14,) and tuple(gt_seq.shape) == lead and \
-        tuple(chain_id.shape) == lead and tuple(cdr_def.shape) == (L,), 'complex tensors: (L,...) shared or (B,L,...) per structure'
-    x = _f32(atom14)
-    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
-        x = x.contiguous()
-    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
-    keep = [x, sq]
-
-    def own(t, dtype):
-        t = t.to(dtype).contiguous()
-        keep.append(t)
-        return _p(t)
-
+    lead = (atom14.shape[0], L) if batched else (L,)
+    assert tuple(cdr_def.shape) == (L,), 'complex tensors: (L,...) shared or (B,L,...) per structure'
     a = AbxDesignScoreArgs()
-    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
-    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
-    if mask is not None:
-        assert tuple(mask.shape) == (B, L, 14), mask.shape
-        a.pred_mask = own(mask, torch.uint8)
-    if res_mask is not None:
-        assert tuple(res_mask.shape) == (L,), res_mask.shape
-        a.res_mask = own(res_mask, torch.uint8)
-    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
+    B, _, _, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, lead=lead, extra=(chain_id,))
     a.cdr_def, a.chain_id = own(cdr_def, torch.int32), own(chain_id, torch.int32)
     if residx is not None:
         assert tuple(residx.shape) == lead, residx.shape
         a.residx = own(residx, torch.int32)
     a.complex_batched = 1 if batched else 0
-    a.radius = _p(vdw_radius_table(dev))
     a.overlap_tolerance, a.bond_tolerance_factor = float(overlap_tolerance), float(bond_tolerance_factor)
-    if out is None:
-        out = torch.empty(B, _lib.SCORE_COLS, dtype=torch.float64, device=dev)
-    assert out.dtype == torch.float64 and tuple(out.shape) == (B, _lib.SCORE_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (B, 19) float64 rows'
-    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else _lib.SCORE_COLS
-    a.B, a.L, a.Lab = B, L, Lab
+    out = _out_rows(a, out, B, _lib.SCORE_COLS, dev)
     ws = torch.empty(max(int(lib.abx_design_scores_workspace_bytes(B, L)), 8), dtype=torch.uint8, device=dev)
     check(lib.abx_design_scores(C.byref(a), _p(ws), _stream()), 'abx_design_scores')
     return out
@@ -1137,39 +1166,15 @@ def relax(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, movable, Lab=None
     lib = _lib.load()
     dev = atom14.device
     L = chain_id.shape[-1]
-    B, Lp = atom14.shape[0], atom14.shape[1]
-    Lab = int(seq.shape[1] if Lab is None else Lab)
-    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
-    assert tuple(gt_atom14.shape) == (L, 14, 3) and tuple(gt_exists.shape) == (L, 14) and tuple(gt_seq.shape) == (L,) and \
-        tuple(chain_id.shape) == (L,) and tuple(movable.shape) == (L,), 'complex tensors: (L,...) shared by the batch'
-    x = _f32(atom14)
-    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
-        x = x.contiguous()
-    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
-    keep = [x, sq]
-
-    def own(t, dtype):
-        t = t.to(dtype).contiguous()
-        keep.append(t)
-        return _p(t)
-
-    M = int(movable[:Lp].ne(0).sum()) if n_movable is None else int(n_movable)
     a = AbxRelaxArgs()
-    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
-    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
-    if mask is not None:
-        assert tuple(mask.shape) == (B, L, 14), mask.shape
-        a.pred_mask = own(mask, torch.uint8)
-    if res_mask is not None:
-        assert tuple(res_mask.shape) == (L,), res_mask.shape
-        a.res_mask = own(res_mask, torch.uint8)
-    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
+    B, Lp, _, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, extra=(chain_id, movable))
+    M = int(movable[:Lp].ne(0).sum()) if n_movable is None else int(n_movable)
     a.chain_id, a.movable = own(chain_id, torch.int32), own(movable, torch.uint8)
     if residx is not None:
         assert tuple(residx.shape) == (L,), residx.shape
         a.residx = own(residx, torch.int32)
     axis, group = chi_tables(dev)
-    a.radius, a.chi_axis, a.rigid_group = _p(vdw_radius_table(dev)), _p(axis), _p(group)
+    a.chi_axis, a.rigid_group = _p(axis), _p(group)
     a.overlap_tolerance, a.between_chain_factor, a.bond_tolerance_factor = float(overlap_tolerance), float(between_chain_factor), float(bond_tolerance_factor)
     a.w_clash, a.w_bond, a.w_angle = float(w_clash), float(w_bond), float(w_angle)
     a.k_restraint, a.eta0, a.rho, a.grow, a.shrink, a.max_iter = float(k_restraint), float(eta0), float(rho), float(grow), float(shrink), int(max_iter)
@@ -1181,7 +1186,7 @@ def relax(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, movable, Lab=None
     if return_grad:
         grad = torch.empty(B, max(M, 1), 10, device=dev)
         a.gen_grad = _p(grad)
-    a.B, a.L, a.Lab, a.M = B, L, Lab, M
+    a.M = M
     ws = torch.empty(max(int(lib.abx_relax_workspace_bytes(B, L, M)), 8), dtype=torch.uint8, device=dev)
     check(lib.abx_relax(C.byref(a), _p(ws), _stream()), 'abx_relax')
     return (out, report, grad) if return_grad else (out, report)
@@ -1200,48 +1205,14 @@ def interface_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, Lab=None
     lib = _lib.load()
     dev = atom14.device
     L = gt_seq.shape[-1]
-    B, Lp = atom14.shape[0], atom14.shape[1]
-    Lab = int(seq.shape[1] if Lab is None else Lab)
-    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
-    assert tuple(gt_atom14.shape) == (L, 14, 3) and tuple(gt_exists.shape) == (L, 14) and tuple(gt_seq.shape) == (L,), \
-        'complex tensors: (L,...) shared by the batch'
     assert sphere.dtype == torch.float64 and sphere.dim() == 2 and sphere.shape[1] == 3 and sphere.is_contiguous() and sphere.device == dev, \
         'sphere: (P,3) float64 on the device of atom14'
-    x = _f32(atom14)
-    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
-        x = x.contiguous()
-    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
-    keep = [x, sq]
-
-    def own(t, dtype):
-        t = t.to(dtype).contiguous()
-        keep.append(t)
-        return _p(t)
-
     a = AbxInterfaceArgs()
-    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
-    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
-    if mask is not None:
-        assert tuple(mask.shape) == (B, L, 14), mask.shape
-        a.pred_mask = own(mask, torch.uint8)
-    if res_mask is not None:
-        assert tuple(res_mask.shape) == (L,), res_mask.shape
-        a.res_mask = own(res_mask, torch.uint8)
-    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
-    if region is not None:
-        assert tuple(region.shape) == (L,), region.shape
-        a.region = own(region.ne(0), torch.uint8)
-    a.radius = _p(vdw_radius_table(dev))
+    B, _, _, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region)
     a.sphere, a.P = _p(sphere), int(sphere.shape[0])
     a.probe, a.cutoff = float(probe), float(cutoff)
-    if out is None:
-        out = torch.empty(B, _lib.IFACE_COLS, dtype=torch.float64, device=dev)
-    assert out.dtype == torch.float64 and tuple(out.shape) == (B, _lib.IFACE_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (B, 12) float64 rows'
-    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else _lib.IFACE_COLS
-    if points is not None:
-        assert points.dtype == torch.int32 and tuple(points.shape) == (B, L, 14, 2) and points.is_contiguous() and points.is_cuda, 'points: (B,L,14,2) int32'
-        a.points = _p(points)
-    a.B, a.L, a.Lab = B, L, Lab
+    out = _out_rows(a, out, B, _lib.IFACE_COLS, dev)
+    _side_output(a, 'points', points, torch.int32, (B, L, 14, 2))
     ws = torch.empty(max(int(lib.abx_interface_scores_workspace_bytes(B, L, a.P)), 16), dtype=torch.uint8, device=dev)
     check(lib.abx_interface_scores(C.byref(a), _p(ws), _stream()), 'abx_interface_scores')
     return out
@@ -1260,53 +1231,18 @@ def polar_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, table, Lab=None, reg
     lib = _lib.load()
     dev = atom14.device
     L = gt_seq.shape[-1]
-    B, Lp = atom14.shape[0], atom14.shape[1]
-    Lab = int(seq.shape[1] if Lab is None else Lab)
-    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
-    assert tuple(gt_atom14.shape) == (L, 14, 3) and tuple(gt_exists.shape) == (L, 14) and tuple(gt_seq.shape) == (L,), \
-        'complex tensors: (L,...) shared by the batch'
     assert table.dtype == torch.int32 and tuple(table.shape) == (21, 14) and table.is_contiguous() and table.device == dev, \
         'table: (21,14) int32 on the device of atom14'
-    x = _f32(atom14)
-    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
-        x = x.contiguous()
-    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
-    keep = [x, sq]
-
-    def own(t, dtype):
-        t = t.to(dtype).contiguous()
-        keep.append(t)
-        return _p(t)
-
     a = AbxPolarArgs()
-    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
-    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
-    if mask is not None:
-        assert tuple(mask.shape) == (B, L, 14), mask.shape
-        a.pred_mask = own(mask, torch.uint8)
-    if res_mask is not None:
-        assert tuple(res_mask.shape) == (L,), res_mask.shape
-        a.res_mask = own(res_mask, torch.uint8)
-    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
-    if region is not None:
-        assert tuple(region.shape) == (L,), region.shape
-        a.region = own(region.ne(0), torch.uint8)
-    a.radius, a.table = _p(vdw_radius_table(dev)), _p(table)
+    B, _, _, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region)
+    a.table = _p(table)
+    _side_output(a, 'points', points, torch.int32, (B, L, 14, 2))
     if points is not None:
-        assert points.dtype == torch.int32 and tuple(points.shape) == (B, L, 14, 2) and points.is_contiguous() and points.device == dev, 'points: (B,L,14,2) int32'
-        a.points, a.P, a.probe = _p(points), int(n_points), float(probe)
+        a.P, a.probe = int(n_points), float(probe)
     a.hb_min, a.hb_max, a.hb_angle, a.hb_cos2, a.salt = float(hb_min), float(hb_max), float(hb_angle), cos2_of(hb_angle), float(salt)
-    if out is None:
-        out = torch.empty(B, _lib.POLAR_COLS, dtype=torch.float64, device=dev)
-    assert out.dtype == torch.float64 and tuple(out.shape) == (B, _lib.POLAR_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (B, 14) float64 rows'
-    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else _lib.POLAR_COLS
-    if bonds is not None:
-        assert bonds.dtype == torch.int32 and tuple(bonds.shape) == (B, L, 14, 2) and bonds.is_contiguous() and bonds.is_cuda, 'bonds: (B,L,14,2) int32'
-        a.bonds = _p(bonds)
-    if rows is not None:
-        assert rows.dtype == torch.int32 and tuple(rows.shape) == (B, L, 4) and rows.is_contiguous() and rows.is_cuda, 'rows: (B,L,4) int32'
-        a.rows = _p(rows)
-    a.B, a.L, a.Lab = B, L, Lab
+    out = _out_rows(a, out, B, _lib.POLAR_COLS, dev)
+    _side_output(a, 'bonds', bonds, torch.int32, (B, L, 14, 2))
+    _side_output(a, 'rows', rows, torch.int32, (B, L, 4))
     check(lib.abx_polar_scores(C.byref(a), None, _stream()), 'abx_polar_scores')
     return out
 
@@ -1325,50 +1261,16 @@ def accuracy_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, Lab=None, region=
     lib = _lib.load()
     dev = atom14.device
     L = gt_seq.shape[-1]
-    B, Lp = atom14.shape[0], atom14.shape[1]
-    Lab = int(seq.shape[1] if Lab is None else Lab)
-    assert tuple(atom14.shape[2:]) == (14, 3) and seq.shape[0] == B and seq.shape[1] >= Lab, (atom14.shape, seq.shape)
-    assert tuple(gt_atom14.shape) == (L, 14, 3) and tuple(gt_exists.shape) == (L, 14) and tuple(gt_seq.shape) == (L,), \
-        'complex tensors: (L,...) shared by the batch'
-    x = _f32(atom14)
-    if not x[0].is_contiguous():                        # (a batch-strided view is read in place)
-        x = x.contiguous()
-    sq = seq if (seq.dtype == torch.int64 and seq.stride(1) == 1) else seq.to(torch.int64).contiguous()
-    keep = [x, sq]
-
-    def own(t, dtype):
-        t = t.to(dtype).contiguous()
-        keep.append(t)
-        return _p(t)
-
     a = AbxAccuracyArgs()
-    a.pred_atom14, a.pred_sb, a.Lpred = _p(x), x.stride(0), Lp
-    a.pred_seq, a.pred_seq_sb = _p(sq), sq.stride(0)
-    if mask is not None:
-        assert tuple(mask.shape) == (B, L, 14), mask.shape
-        a.pred_mask = own(mask, torch.uint8)
-    if res_mask is not None:
-        assert tuple(res_mask.shape) == (L,), res_mask.shape
-        a.res_mask = own(res_mask, torch.uint8)
-    a.gt_atom14, a.gt_exists, a.gt_seq = own(_f32(gt_atom14), torch.float32), own(gt_exists, torch.uint8), own(gt_seq, torch.int64)
-    if region is not None:
-        assert tuple(region.shape) == (L,), region.shape
-        a.region = own(region.ne(0), torch.uint8)
-    a.radius = _p(vdw_radius_table(dev))
+    B, _, Lab, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region)
     if plddt is not None:
         assert tuple(plddt.shape) == (B, L), plddt.shape
         a.plddt, a.plddt_sb = own(plddt, torch.float32), L
     a.lddt_radius, a.contact = float(radius), float(contact)
-    if out is None:
-        out = torch.empty(B, _lib.ACC_COLS, dtype=torch.float64, device=dev)
-    assert out.dtype == torch.float64 and tuple(out.shape) == (B, _lib.ACC_COLS) and out.stride(1) == 1 and out.is_cuda, 'out: (B, 21) float64 rows'
-    a.out, a.out_stride = _p(out), out.stride(0) if B > 1 else _lib.ACC_COLS
-    for name, t, dtype, shape in (('rows', rows, torch.float64, (B, L, 4)), ('counts', counts, torch.int32, (B, L, 3, 5)),
-                                  ('contacts', contacts, torch.uint8, (B, Lab, L - Lab))):
-        if t is not None:
-            assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.is_cuda, f'{name}: {shape} {dtype}'
-            setattr(a, name, _p(t))
-    a.B, a.L, a.Lab = B, L, Lab
+    out = _out_rows(a, out, B, _lib.ACC_COLS, dev)
+    _side_output(a, 'rows', rows, torch.float64, (B, L, 4))
+    _side_output(a, 'counts', counts, torch.int32, (B, L, 3, 5))
+    _side_output(a, 'contacts', contacts, torch.uint8, (B, Lab, L - Lab))
     ws = torch.empty(max(int(lib.abx_accuracy_scores_workspace_bytes(B, L)), 16), dtype=torch.uint8, device=dev)
     check(lib.abx_accuracy_scores(C.byref(a), _p(ws), _stream()), 'abx_accuracy_scores')
     return out

@@ -8,10 +8,12 @@ no His protonation (both ring nitrogens are donor and acceptor, neither a cation
 Every decision in float64 from the float32 coordinates in a fixed IEEE operation order (include/abx_hip.h, AbxPolarArgs): the counts of
 the device (`PolarScorer`, abx_polar_scores, csrc/polar.hip) and of the host twin (`polar_host`, numpy) are equal integers.  Burial comes
 from the point counts of the interface analysis (abx_amd.interface: acc_alone / acc_cplx of every atom14 slot)."""
+import functools
 import math
 
 import numpy as np
 
+from . import complex_view
 from .interface import FOUR_PI
 
 # The row of abx_polar_scores (include/abx_hip.h, ABX_POLAR_COLS)
@@ -77,19 +79,10 @@ def cos2_of(hb_angle):
     return 0.0 if hb_angle == 90.0 else math.cos(math.radians(hb_angle)) ** 2
 
 
-def format_polar(row):
-    """One row as TSV fields: %.2f for the areas (square Angstrom), integers for the counts."""
-    return [str(int(v)) if c in COUNT_COLUMNS else f'{float(v):.2f}' for c, v in zip(POLAR_COLUMNS, row)]
-
-
-def format_delta(row, wild):
-    """design minus wild type for DELTA_COLUMNS, signed: %+.2f for the areas, %+d for the counts."""
-    out = []
-    for c in DELTA_COLUMNS:
-        k = POLAR_COLUMNS.index(c)
-        d = float(row[k]) - float(wild[k])
-        out.append(f'{int(round(d)):+d}' if c in COUNT_COLUMNS else f'{d:+.2f}')
-    return out
+# format_polar(row): %.2f for the areas (square Angstrom), integers for the counts; format_delta(row, wild): design minus wild type for
+# DELTA_COLUMNS, signed
+format_polar = functools.partial(complex_view.format_row, POLAR_COLUMNS, COUNT_COLUMNS, 2)
+format_delta = functools.partial(complex_view.format_delta, POLAR_COLUMNS, COUNT_COLUMNS, DELTA_COLUMNS, 2)
 
 
 class PolarScorer:
@@ -106,11 +99,7 @@ class PolarScorer:
             raise ValueError(f'polar: needs 0 <= hb_min <= hb_max, 90 <= hb_angle < 180, salt >= 0 (got {hb_min}, {hb_max}, {hb_angle}, {salt})')
         self.interface = interface if interface is not None else InterfaceScorer(batch, region=region, n_points=n_points, probe=probe)
         it = self.interface
-        if region is None:
-            self.region = it.region
-        else:
-            import torch
-            self.region = (torch.as_tensor(region).to(it.gt_atom14.device) != 0).to(torch.uint8).contiguous()
+        self.region = it.region if region is None else complex_view.region_mask(batch, region, it.gt_atom14.device)
         self.Lab, self.L = it.Lab, int(it.gt_seq.shape[0])
         self.table = polar_table_on(it.gt_atom14.device)
         self.kw = dict(hb_min=float(hb_min), hb_max=float(hb_max), hb_angle=float(hb_angle), salt=float(salt),
@@ -118,8 +107,7 @@ class PolarScorer:
 
     def new_table(self, *lead):
         """An uninitialised (*lead, len(POLAR_COLUMNS)) float64 table on the complex's device for `score(..., out=table[i])`."""
-        import torch
-        return torch.empty(*lead, len(POLAR_COLUMNS), dtype=torch.float64, device=self.table.device)
+        return complex_view.new_table(POLAR_COLUMNS, self.table.device, *lead)
 
     def new_points(self, B):
         """An uninitialised (B, L, 14, 2) int32 tensor for the point counts of B structures."""

@@ -12,6 +12,7 @@ without a GPU.  k_restraint has no principled default (the energy is in Angstrom
 bounds the motion by k * sum |dCA|^2 <= E_viol(input), because E never increases."""
 import torch
 
+from . import complex_view
 from . import residue_constants as rc
 
 # The report row of abx_relax (include/abx_hip.h, ABX_RELAX_COLS)
@@ -46,25 +47,15 @@ def expand_movable(movable, chain_id, residx=None, flank=0, limit=None):
     return mov
 
 
-class ViolationRelaxer:
+class ViolationRelaxer(complex_view.ComplexView):
     """Relaxes batches of designs of ONE complex on the device.  Built once per complex from its featurised batch like
     metrics.DesignScorer.  movable: (L) mask of the rows that may move (default: the rows the sampler diffuses, sample 0's
     (1 - fixed_mask) * backbone mask); flank: that many peptide-linked neighbours on each side are added.  Only antibody rows
     (< Lab) can move.  params: DEFAULTS."""
 
     def __init__(self, batch, movable=None, flank=0, link_by_residx=True, **params):
-        batched = batch['seq'].dim() == 2
-        one = (lambda k: batch[k][0]) if batched else (lambda k: batch[k])
-        self.Lab = int(batch['anchor_flag'].shape[-1])
-        self.gt_atom14 = one('atom14_gt_positions').to(torch.float32).contiguous()
-        self.gt_exists = one('atom14_gt_exists').to(torch.uint8).contiguous()
-        self.gt_seq = one('seq').to(torch.int64).contiguous()
-        self.chain_id = one('chain_id').to(torch.int32).contiguous()
-        self.residx = one('residx').to(torch.int32).contiguous() if link_by_residx and 'residx' in batch else None
-        self.res_mask = one('mask').to(torch.uint8).contiguous() if 'mask' in batch else None
-        if movable is None:
-            movable = (1 - one('fixed_mask')) * one('atom14_gt_exists')[..., 0]
-        movable = torch.as_tensor(movable).to(self.chain_id.device) != 0
+        super().__init__(batch, chains=True, link_by_residx=link_by_residx)
+        movable = complex_view.region_mask(batch, movable, self.chain_id.device)
         movable = expand_movable(movable, self.chain_id, self.residx, flank, limit=self.Lab)
         self.movable = movable.to(torch.uint8).contiguous()
         self.M = int(self.movable.sum())                     # (the one host synchronisation: at construction)

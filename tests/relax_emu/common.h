@@ -4,6 +4,7 @@
 #include <stdint.h>
 #define ABX_OK 0
 #define ABX_ERR_ARG (-1)
+#define ABX_LDS_LIMIT 163840
 inline void abx_set_error(const char* m) { fprintf(stderr, "abx_relax (host emulation): %s\n", m); }
 inline int abx_check_launch(const char*) { return 0; }
 inline int abx_ensure_dynamic_lds(const void*, int, const char*) { return 0; }

@@ -3,19 +3,16 @@ reference's lddt / lddt_ca_torch / TMscoreHead loop, hand-checkable cases, the b
 for equal integers, the C layout of the descriptor, argument checks without a GPU, and the formats of the design driver."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import host_cases as HC
 import accuracy_cases as AC
 import relax_cases as RC
 from conftest import load_npz
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-HEADER = os.path.join(ROOT, 'include', 'abx_hip.h')
 
 
 def col(name):
@@ -25,11 +22,7 @@ def col(name):
 
 @pytest.fixture(scope='module')
 def lib():
-    import __graft_entry__ as ge
-    from abx_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    return HC.load_lib()
 
 
 def test_host_twin_against_the_reference_vectors():
@@ -226,20 +219,8 @@ def test_accuracy_args_match_c_layout():
     """sizeof / offsetof of AbxAccuracyArgs as gcc lays it out, and ABX_ACC_COLS against the Python side."""
     from abx_amd import _lib, accuracy
     st = _lib.AbxAccuracyArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(){',
-             'printf("cols %d\\n", ABX_ACC_COLS);', 'printf("size %zu\\n", sizeof(AbxAccuracyArgs));']
-    for f, _ in st._fields_:
-        lines.append(f'printf("{f} %zu\\n", offsetof(AbxAccuracyArgs, {f}));')
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'l.c'), os.path.join(d, 'l')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', src, '-o', exe])
-        c_layout = dict(l.split() for l in subprocess.check_output([exe]).decode().split('\n') if l)
-    assert int(c_layout['size']) == ctypes.sizeof(st)
-    for f, _ in st._fields_:
-        assert int(c_layout[f]) == getattr(st, f).offset, f
-    assert int(c_layout['cols']) == _lib.ACC_COLS == len(accuracy.ACCURACY_COLUMNS) == 21
+    c_layout = HC.assert_c_layout({'AbxAccuracyArgs': st}, ['ABX_ACC_COLS'])
+    assert c_layout['ABX_ACC_COLS'] == _lib.ACC_COLS == len(accuracy.ACCURACY_COLUMNS) == 21
     assert accuracy.ACCURACY_COLUMNS[:6] == ('lddt_all', 'lddt_antibody', 'lddt_region', 'lddt_bb_region', 'lddt_ca_all', 'lddt_ca_region')
     assert accuracy.ACCURACY_COLUMNS[6:12] == ('plddt_region', 'plddt_err_region', 'tm_score', 'gdt_ts', 'gdt_ha', 'rmsd_ca')
     assert accuracy.ACCURACY_COLUMNS[12:] == ('n_native', 'n_kept', 'fnat', 'n_new', 'n_native_region', 'n_kept_region', 'fnat_region',

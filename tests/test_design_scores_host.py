@@ -3,26 +3,19 @@ without a GPU, the column names, the TSV formats of the design driver, and the h
 reference's masks (tests/golden/vio_pdb.npz)."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import host_cases as HC
 from conftest import load_npz, tt
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-HEADER = os.path.join(ROOT, 'include', 'abx_hip.h')
 
 
 @pytest.fixture(scope='module')
 def lib():
-    import __graft_entry__ as ge
-    from abx_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    return HC.load_lib()
 
 
 def test_design_score_args_match_c_layout():
@@ -30,20 +23,8 @@ def test_design_score_args_match_c_layout():
     whose struct list is fixed) and ABX_SCORE_COLS against the Python side."""
     from abx_amd import _lib, metrics
     st = _lib.AbxDesignScoreArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(){',
-             'printf("cols %d\\n", ABX_SCORE_COLS);', 'printf("size %zu\\n", sizeof(AbxDesignScoreArgs));']
-    for f, _ in st._fields_:
-        lines.append(f'printf("{f} %zu\\n", offsetof(AbxDesignScoreArgs, {f}));')
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'l.c'), os.path.join(d, 'l')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', src, '-o', exe])
-        c_layout = dict(l.split() for l in subprocess.check_output([exe]).decode().split('\n') if l)
-    assert int(c_layout['size']) == ctypes.sizeof(st)
-    for f, _ in st._fields_:
-        assert int(c_layout[f]) == getattr(st, f).offset, f
-    assert int(c_layout['cols']) == _lib.SCORE_COLS == len(metrics.SCORE_COLUMNS)
+    c_layout = HC.assert_c_layout({'AbxDesignScoreArgs': st}, ['ABX_SCORE_COLS'])
+    assert c_layout['ABX_SCORE_COLS'] == _lib.SCORE_COLS == len(metrics.SCORE_COLUMNS)
 
 
 def test_design_scores_argument_checks_without_gpu(lib):

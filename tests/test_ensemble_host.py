@@ -3,51 +3,29 @@ descriptors, argument checks without a GPU, the float64 host twin against the pi
 Daura rule on hand-made graphs, the synthetic ensemble the GPU tests use, and the formats of the design driver."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import host_cases as HC
 import ensemble_cases as EC
 from conftest import load_npz
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-HEADER = os.path.join(ROOT, 'include', 'abx_hip.h')
 
 
 @pytest.fixture(scope='module')
 def lib():
-    import __graft_entry__ as ge
-    from abx_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    return HC.load_lib()
 
 
 def test_ensemble_args_match_c_layout():
     """sizeof / offsetof of both descriptors as gcc lays them out, and the three constants against the Python side."""
     from abx_amd import _lib, ensemble
     structs = {'AbxEnsemblePairsArgs': _lib.AbxEnsemblePairsArgs, 'AbxEnsembleClusterArgs': _lib.AbxEnsembleClusterArgs}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(){',
-             'printf("cols %d\\n", ABX_ENS_COLS);', 'printf("maxp %d\\n", ABX_ENS_MAX_POINTS);', 'printf("maxn %d\\n", ABX_ENS_MAX_N);']
-    for name, st in structs.items():
-        lines.append(f'printf("{name}.size %zu\\n", sizeof({name}));')
-        for f, _ in st._fields_:
-            lines.append(f'printf("{name}.{f} %zu\\n", offsetof({name}, {f}));')
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'l.c'), os.path.join(d, 'l')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', src, '-o', exe])
-        c_layout = dict(l.split() for l in subprocess.check_output([exe]).decode().split('\n') if l)
-    for name, st in structs.items():
-        assert int(c_layout[name + '.size']) == ctypes.sizeof(st), name
-        for f, _ in st._fields_:
-            assert int(c_layout[f'{name}.{f}']) == getattr(st, f).offset, (name, f)
-    assert int(c_layout['cols']) == _lib.ENS_COLS == len(ensemble.ENSEMBLE_COLUMNS) == 10
-    assert int(c_layout['maxp']) == _lib.ENS_MAX_POINTS == ensemble.MAX_POINTS == 512
-    assert int(c_layout['maxn']) == _lib.ENS_MAX_N == ensemble.MAX_N == 1024
+    c_layout = HC.assert_c_layout(structs, ['ABX_ENS_COLS', 'ABX_ENS_MAX_POINTS', 'ABX_ENS_MAX_N'])
+    assert c_layout['ABX_ENS_COLS'] == _lib.ENS_COLS == len(ensemble.ENSEMBLE_COLUMNS) == 10
+    assert c_layout['ABX_ENS_MAX_POINTS'] == _lib.ENS_MAX_POINTS == ensemble.MAX_POINTS == 512
+    assert c_layout['ABX_ENS_MAX_N'] == _lib.ENS_MAX_N == ensemble.MAX_N == 1024
     assert set(ensemble.COUNT_COLUMNS) <= set(ensemble.ENSEMBLE_COLUMNS)
 
 

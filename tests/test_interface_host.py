@@ -3,46 +3,27 @@ without a GPU, exact cases of the float64 host twin, its discretisation error ag
 complexes, and the formats of the design driver."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import host_cases as HC
 import relax_cases as RC
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-HEADER = os.path.join(ROOT, 'include', 'abx_hip.h')
 R_C, R_N = float(np.float32(1.7)) + 1.4, float(np.float32(1.55)) + 1.4      # inflated radii of a carbon (slot 1) and a nitrogen (slot 0)
 
 
 @pytest.fixture(scope='module')
 def lib():
-    import __graft_entry__ as ge
-    from abx_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    return HC.load_lib()
 
 
 def test_interface_args_match_c_layout():
     """sizeof / offsetof of AbxInterfaceArgs as gcc lays it out, and ABX_IFACE_COLS against the Python side."""
     from abx_amd import _lib, interface
     st = _lib.AbxInterfaceArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(){',
-             'printf("cols %d\\n", ABX_IFACE_COLS);', 'printf("size %zu\\n", sizeof(AbxInterfaceArgs));']
-    for f, _ in st._fields_:
-        lines.append(f'printf("{f} %zu\\n", offsetof(AbxInterfaceArgs, {f}));')
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'l.c'), os.path.join(d, 'l')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', src, '-o', exe])
-        c_layout = dict(l.split() for l in subprocess.check_output([exe]).decode().split('\n') if l)
-    assert int(c_layout['size']) == ctypes.sizeof(st)
-    for f, _ in st._fields_:
-        assert int(c_layout[f]) == getattr(st, f).offset, f
-    assert int(c_layout['cols']) == _lib.IFACE_COLS == len(interface.INTERFACE_COLUMNS) == 12
+    c_layout = HC.assert_c_layout({'AbxInterfaceArgs': st}, ['ABX_IFACE_COLS'])
+    assert c_layout['ABX_IFACE_COLS'] == _lib.IFACE_COLS == len(interface.INTERFACE_COLUMNS) == 12
     assert interface.COUNT_COLUMNS == interface.INTERFACE_COLUMNS[6:]
     assert [interface.INTERFACE_COLUMNS.index(c) for c in interface.DELTA_COLUMNS] == [3, 4, 5, 9, 10]
 

@@ -3,48 +3,29 @@ GPU, the polar table against a literal expectation, exact hand-built cases of th
 recorded numbers and against an independent restatement of the rule, and the formats of the design driver."""
 import ctypes
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import host_cases as HC
 import polar_cases as PC
 import relax_cases as RC
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-HEADER = os.path.join(ROOT, 'include', 'abx_hip.h')
 
 
 @pytest.fixture(scope='module')
 def lib():
-    import __graft_entry__ as ge
-    from abx_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    return HC.load_lib()
 
 
 def test_polar_args_match_c_layout():
     """sizeof / offsetof of AbxPolarArgs as gcc lays it out, and the ABX_POLAR_* constants against the Python side."""
     from abx_amd import _lib, polar
     st = _lib.AbxPolarArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(){',
-             'printf("cols %d\\n", ABX_POLAR_COLS);', 'printf("size %zu\\n", sizeof(AbxPolarArgs));',
-             'printf("bits %d %d %d %d %d\\n", ABX_POLAR_DONOR, ABX_POLAR_ACCEPTOR, ABX_POLAR_CATION, ABX_POLAR_ANION, ABX_POLAR_ELEMENT);']
-    for f, _ in st._fields_:
-        lines.append(f'printf("{f} %zu\\n", offsetof(AbxPolarArgs, {f}));')
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'l.c'), os.path.join(d, 'l')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', src, '-o', exe])
-        c_layout = dict(l.split(None, 1) for l in subprocess.check_output([exe]).decode().split('\n') if l)
-    assert int(c_layout['size']) == ctypes.sizeof(st)
-    for f, _ in st._fields_:
-        assert int(c_layout[f]) == getattr(st, f).offset, f
-    assert int(c_layout['cols']) == _lib.POLAR_COLS == len(polar.POLAR_COLUMNS) == 14
-    bits = [int(v) for v in c_layout['bits'].split()]
+    BITS = ['ABX_POLAR_DONOR', 'ABX_POLAR_ACCEPTOR', 'ABX_POLAR_CATION', 'ABX_POLAR_ANION', 'ABX_POLAR_ELEMENT']
+    c_layout = HC.assert_c_layout({'AbxPolarArgs': st}, ['ABX_POLAR_COLS'] + BITS)
+    assert c_layout['ABX_POLAR_COLS'] == _lib.POLAR_COLS == len(polar.POLAR_COLUMNS) == 14
+    bits = [c_layout[m] for m in BITS]
     assert bits == [_lib.POLAR_DONOR, _lib.POLAR_ACCEPTOR, _lib.POLAR_CATION, _lib.POLAR_ANION, _lib.POLAR_ELEMENT] == \
         [polar.DONOR, polar.ACCEPTOR, polar.CATION, polar.ANION, polar.ELEMENT] == [1, 2, 4, 8, 16]
     assert polar.COUNT_COLUMNS == polar.POLAR_COLUMNS[:10] + polar.POLAR_COLUMNS[12:]

@@ -11,10 +11,10 @@ import tempfile
 import pytest
 import torch
 
+import host_cases as HC
 import relax_cases as RC
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-HEADER = os.path.join(ROOT, 'include', 'abx_hip.h')
 
 # Evaluations relax_host needs to reach E == 0 on the nine perturbed cases (measured; the prototype of the algorithm needed the same).
 # The GPU test relies on the default budget of 200 evaluations with a factor 4 of margin for float32 taking another accept / reject path.
@@ -23,11 +23,7 @@ N_HOST = {('6qd7', 'h3'): (22, 27, 22), ('6ct7', 'h3'): (15, 14, 26), ('6qd7', '
 
 @pytest.fixture(scope='module')
 def lib():
-    import __graft_entry__ as ge
-    from abx_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    return HC.load_lib()
 
 
 def _relax(c, x, **kw):
@@ -106,20 +102,8 @@ def test_relax_args_match_c_layout():
     """sizeof / offsetof of AbxRelaxArgs as gcc lays it out, ABX_RELAX_COLS against the Python side."""
     from abx_amd import _lib, relax
     st = _lib.AbxRelaxArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(){',
-             'printf("cols %d\\n", ABX_RELAX_COLS);', 'printf("size %zu\\n", sizeof(AbxRelaxArgs));']
-    for f, _ in st._fields_:
-        lines.append(f'printf("{f} %zu\\n", offsetof(AbxRelaxArgs, {f}));')
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'l.c'), os.path.join(d, 'l')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', src, '-o', exe])
-        c_layout = dict(l.split() for l in subprocess.check_output([exe]).decode().split('\n') if l)
-    assert int(c_layout['size']) == ctypes.sizeof(st)
-    for f, _ in st._fields_:
-        assert int(c_layout[f]) == getattr(st, f).offset, f
-    assert int(c_layout['cols']) == _lib.RELAX_COLS == len(relax.RELAX_COLUMNS)
+    c_layout = HC.assert_c_layout({'AbxRelaxArgs': st}, ['ABX_RELAX_COLS'])
+    assert c_layout['ABX_RELAX_COLS'] == _lib.RELAX_COLS == len(relax.RELAX_COLUMNS)
 
 
 def test_relax_exports_and_argument_checks_without_gpu(lib):
@@ -223,6 +207,7 @@ def emulated_kernel(tmp_path_factory):
     assert src.count(decl) == 1
     open(os.path.join(d, 'relax_emu.hip'), 'w').write(src.replace(decl, 'unsigned char* lds = emu_lds;'))
     shutil.copy(os.path.join(ROOT, 'abx_amd', 'csrc', 'peptide_dev.h'), d)
+    shutil.copy(os.path.join(ROOT, 'abx_amd', 'csrc', 'structure_dev.h'), d)
     shutil.copy(os.path.join(emu, 'common.h'), d)
     shutil.copy(os.path.join(emu, 'emu.cpp'), d)
     so = os.path.join(d, 'librelax_emu.so')
