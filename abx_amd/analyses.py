@@ -1,0 +1,344 @@
+"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES beside the writers of its tables, and
+RowLayout, the columns of the row table that a set-level run gathers.  design.main walks ANALYSES in their order for the option checks,
+the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and zero-row blocks come from the same declarations), the
+set-level rows and the files of rank 0: the next analysis is one more entry here and nothing in main."""
+import functools
+import math
+import os
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import accuracy, confidence, ensemble, interface, metrics, polar, relax
+from .io import index_to_str_seq
+
+F64 = torch.float64
+# One gathered per-sample field (n, *shape).  shape: 'L' / 'Lab' stand for the lengths of the complex / of its antibody; rows: the field
+# travels in the rows of a set-level run too (the others exist in sample-sharded runs only: 8 L^2 or 32 L bytes a sample).
+Field = namedtuple('Field', 'name dtype shape rows')
+# One analysis.  flag: the option that switches it on; kw: the keyword its scorer is passed to sampler.sample_fn under (None: the
+# analysis runs after the gather, on the rank that writes, with one scorer per complex); build(batch, a, model, cfg, scorers) -> the
+# scorer (scorers: those of the analyses before it, by flag); fields(a) -> [Field]; collect(a, traj, scorers) -> {field: tensor} of a
+# sampled batch; write(a, out_dir, cname, ids, F, scorer) -> the files of one complex from the gathered fields F, rows in the order of
+# the sample ids; checks: (bad(a), the SystemExit text) pairs; extra: its --<flag>_rows / _planes option, whose field is not one of rows.
+Analysis = namedtuple('Analysis', 'flag kw build fields collect write checks extra', defaults=((), None))
+HEAD = (Field('seq', torch.int64, ('Lab',), True), Field('pLDDT', torch.float32, ('Lab',), False))
+
+
+def block_shape(field, L, Lab):
+    return tuple({'L': L, 'Lab': Lab}.get(s, s) for s in field.shape)
+
+
+def _save(out_dir, cname, end, array):
+    np.save(os.path.join(out_dir, f'{cname}_{end}.npy'), array)
+    return os.path.join(out_dir, f'{cname}_{end}.npy')
+
+
+# --score: metrics.SCORE_COLUMNS of every record as it is made (metrics.DesignScorer): further columns of <complex>_designs.tsv and, in
+# trajectory mode, <complex>_trajectory_scores.tsv with one line per sample and record.
+def _score_fields(a):
+    NS, n_rec = len(metrics.SCORE_COLUMNS), a.num_t if a.mode == 'trajectory' else 0
+    return [Field('scores', F64, (NS,), True)] + ([Field('traj_scores', F64, (n_rec, 1 + NS), True)] if n_rec else [])
+
+
+def _score_collect(a, traj, scorers):
+    s = traj[-1]['scores']
+    if a.mode != 'trajectory' or not a.num_t:
+        return {'scores': s}                                    # traj_scores (samples, records, 1 + columns): t, then the scores of the record
+    return {'scores': s, 'traj_scores': torch.stack([torch.cat([s.new_full((s.shape[0], 1), r['time']), r['scores']], 1) for r in traj], 1)}
+
+
+def _write_designs(out_dir, cname, rows):
+    """<out_dir>/<complex>_designs.tsv: (sample id, mean pLDDT, designed antibody sequence) per sample; with --score a row carries
+    a fourth entry, its metrics.SCORE_COLUMNS values, written as further columns."""
+    tsv = os.path.join(out_dir, f'{cname}_designs.tsv')
+    scored = bool(rows) and len(rows[0]) > 3
+    with open(tsv, 'w') as f:
+        f.write('sample\tmean_pLDDT\tantibody_sequence' + ('\t' + '\t'.join(metrics.SCORE_COLUMNS) if scored else '') + '\n')
+        for i, pl, toks, *sc in rows:
+            f.write(f'{i}\t{pl:.3f}\t{index_to_str_seq(toks)}' + ('\t' + '\t'.join(metrics.format_scores(sc[0])) if scored else '') + '\n')
+    return tsv
+
+
+def _write_trajectory_scores(out_dir, cname, table):
+    """<out_dir>/<complex>_trajectory_scores.tsv: one line per (sample, record of the trajectory).  table (samples, records, 1 + columns):
+    t of the record, then its metrics.SCORE_COLUMNS values."""
+    tsv = os.path.join(out_dir, f'{cname}_trajectory_scores.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\tstep\tt\t' + '\t'.join(metrics.SCORE_COLUMNS) + '\n')
+        for i, recs in enumerate(table.tolist()):
+            for k, r in enumerate(recs):
+                f.write(f'{i}\t{k}\t{r[0]:.4f}\t' + '\t'.join(metrics.format_scores(r[1:])) + '\n')
+    return tsv
+
+
+SCORE = Analysis('score', 'scorer', lambda batch, *_: metrics.DesignScorer(batch), _score_fields, _score_collect,
+                 lambda a, out_dir, cname, ids, F, scorer: [_write_trajectory_scores(out_dir, cname, F['traj_scores'].cpu())] if 'traj_scores' in F else [])
+
+
+# --relax: every design is relaxed after the last step (relax.ViolationRelaxer): <name>_relaxed.pdb beside every design (upstream's
+# naming, which its eval_metric.py skips), <complex>_relax.tsv with relax.RELAX_COLUMNS and, with --score, the scores of the relaxed
+# structure, and in the wild tables below the columns of the relaxed structure, suffixed _relaxed (nan on the wild line).
+def _write_relax(out_dir, cname, rows, scored):
+    """<out_dir>/<complex>_relax.tsv: (sample id, values) per sample; values = the relax.RELAX_COLUMNS report and, when scored, the
+    metrics.SCORE_COLUMNS of the relaxed structure."""
+    NR = len(relax.RELAX_COLUMNS)
+    tsv = os.path.join(out_dir, f'{cname}_relax.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(relax.RELAX_COLUMNS + (metrics.SCORE_COLUMNS if scored else ())) + '\n')
+        for i, v in rows:
+            f.write(f'{i}\t' + '\t'.join(relax.format_report(v[:NR]) + (metrics.format_scores(v[NR:]) if scored else [])) + '\n')
+    return tsv
+
+
+RELAX = Analysis('relax', 'relaxer', lambda batch, a, *_: relax.ViolationRelaxer(batch, flank=a.relax_flank, max_iter=a.relax_iters, k_restraint=a.relax_restraint),
+                 lambda a: [Field('relax', F64, (len(relax.RELAX_COLUMNS) + (len(metrics.SCORE_COLUMNS) if a.score else 0),), True)],
+                 lambda a, traj, scorers: {'relax': torch.cat([traj[-1]['relax']] + ([traj[-1]['scores_relaxed']] if a.score else []), 1)},
+                 lambda a, out_dir, cname, ids, F, scorer: [_write_relax(out_dir, cname, list(zip(ids, F['relax'].tolist())), a.score)])
+
+
+def _write_with_wild_deltas(kind, out_dir, cname, wild, rows, relaxed):
+    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence): the `wild` line, then (sample
+    id, values) per sample; values = the module's <KIND>_COLUMNS row and, when relaxed, the row of the relaxed structure.  After the
+    columns: delta_<column> = row minus wild for the module's DELTA_COLUMNS.  wild None: every sample has a wild row of its own, the
+    last columns of its values, and the `wild` line is their mean."""
+    mod = {'interface': interface, 'polar': polar, 'confidence': confidence}[kind]
+    columns, fmt = getattr(mod, f'{kind.upper()}_COLUMNS'), getattr(mod, f'format_{kind}')
+    N = len(columns)
+    wilds = [wild if wild is not None else v[len(v) - N:] for _, v in rows]
+    if wild is None:
+        wild = [sum(w[k] for w in wilds) / max(len(wilds), 1) for k in range(N)]
+    tsv = os.path.join(out_dir, f'{cname}_{kind}.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(columns + tuple('delta_' + c for c in mod.DELTA_COLUMNS) +
+                                       (tuple(c + '_relaxed' for c in columns) if relaxed else ())) + '\n')
+        f.write('wild\t' + '\t'.join(fmt(wild) + mod.format_delta(wild, wild) + (['nan'] * N if relaxed else [])) + '\n')
+        for (i, v), w in zip(rows, wilds):
+            f.write(f'{i}\t' + '\t'.join(fmt(v[:N]) + mod.format_delta(v[:N], w) + (fmt(v[N:2 * N]) if relaxed else [])) + '\n')
+    return tsv
+
+
+# What --<flag>_rows / _planes adds to a wild table.  of_record: last record -> the field; to_array: gathered field -> <complex>_<field>.npy
+Extra = namedtuple('Extra', 'option field of_record to_array')
+
+
+def _wild_table(flag, columns, writer, build, wild, checks, extra=None):
+    """An analysis whose <complex>_<flag>.tsv compares every design with a wild row.  Its field is the design's row, with --relax the
+    relaxed structure's, then the wild row, so that any rank can write the table: (n, 2 or 3 x columns).  wild(last, scorers) -> the
+    wild row(s): (1, columns) of the complex, or (n, columns), one per sample; writer(out_dir, cname, wild of row 0, rows, relaxed)."""
+    def fields(a):
+        return [Field(flag, F64, (len(columns) * (3 if a.relax else 2),), True)] + ([extra.field] if extra and getattr(a, extra.option) else [])
+
+    def collect(a, traj, scorers):
+        last = traj[-1]
+        out = {flag: torch.cat([last[flag]] + ([last[flag + '_relaxed']] if a.relax else []) + [wild(last, scorers).expand(last['seq'].shape[0], -1)], 1)}
+        if extra and getattr(a, extra.option):
+            out[extra.field.name] = extra.of_record(last)
+        return out
+
+    def write(a, out_dir, cname, ids, F, scorer):
+        t = F[flag].tolist()
+        files = [writer(out_dir, cname, t[0][-len(columns):], list(zip(ids, t)), a.relax)]
+        if extra and getattr(a, extra.option):
+            files.append(_save(out_dir, cname, extra.field.name, extra.to_array(F[extra.field.name])))
+        return files
+    return Analysis(flag, flag, build, fields, collect, write, checks, extra and extra.option)
+
+
+_write_interface = functools.partial(_write_with_wild_deltas, 'interface')
+INTERFACE = _wild_table('interface', interface.INTERFACE_COLUMNS, _write_interface,
+                        lambda batch, a, *_: interface.InterfaceScorer(batch, n_points=a.interface_points, probe=a.interface_probe, cutoff=a.interface_cutoff),
+                        lambda last, scorers: scorers['interface'].wild(points=_shared_wild_points(scorers)),
+                        [(lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0 or a.interface_cutoff <= 0,
+                          '--interface_points must be in 1..1024, --interface_probe >= 0, --interface_cutoff > 0')])
+
+
+# --confidence: every sample carries a wild row of its own, the input complex's coordinates under the SAME design's prediction; the
+# `wild` line of the table is their mean.
+def _confidence_build(batch, a, model, cfg, scorers):
+    conf = confidence.DistogramScorer(batch, model, cutoff=a.confidence_cutoff, conf=cfg.model.heads.distogram)
+    conf.want_planes = a.confidence_planes
+    return conf
+
+
+def _write_confidence(out_dir, cname, rows, relaxed):
+    return _write_with_wild_deltas('confidence', out_dir, cname, None, rows, relaxed)
+
+
+CONFIDENCE = _wild_table('confidence', confidence.CONFIDENCE_COLUMNS, lambda out_dir, cname, wild, *rest: _write_confidence(out_dir, cname, *rest), _confidence_build,
+                         lambda last, scorers: last['confidence_wild'], [(lambda a: not a.confidence_cutoff > 0, '--confidence_cutoff must be > 0')],
+                         Extra('confidence_planes', Field('confidence_contacts', torch.float32, ('L', 'L'), False),
+                               lambda last: last['confidence_planes'][0], lambda t: t.double().mean(0).float().cpu().numpy()))
+
+
+def _write_accuracy(out_dir, cname, wild, rows, relaxed):
+    """<out_dir>/<complex>_accuracy.tsv: the `wild` line, then (sample id, values) per sample; values = the accuracy.ACCURACY_COLUMNS row
+    and, when relaxed, the row of the relaxed structure followed by delta_<column> = relaxed minus design for accuracy.DELTA_COLUMNS."""
+    from .accuracy import ACCURACY_COLUMNS, DELTA_COLUMNS, format_accuracy, format_delta
+    NA = len(ACCURACY_COLUMNS)
+    tsv = os.path.join(out_dir, f'{cname}_accuracy.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(ACCURACY_COLUMNS + ((tuple(c + '_relaxed' for c in ACCURACY_COLUMNS) +
+                                                             tuple('delta_' + c for c in DELTA_COLUMNS)) if relaxed else ())) + '\n')
+        f.write('wild\t' + '\t'.join(format_accuracy(wild) + (['nan'] * (NA + len(DELTA_COLUMNS)) if relaxed else [])) + '\n')
+        for i, v in rows:
+            f.write(f'{i}\t' + '\t'.join(format_accuracy(v[:NA]) +
+                                          ((format_accuracy(v[NA:2 * NA]) + format_delta(v[NA:2 * NA], v[:NA])) if relaxed else [])) + '\n')
+    return tsv
+
+
+ACCURACY = _wild_table('accuracy', accuracy.ACCURACY_COLUMNS, _write_accuracy,
+                       lambda batch, a, *_: accuracy.AccuracyScorer(batch, radius=a.accuracy_radius, contact=a.accuracy_contact),
+                       lambda last, scorers: scorers['accuracy'].wild(),
+                       [(lambda a: not a.accuracy_radius > 0 or not a.accuracy_contact > 0, '--accuracy_radius and --accuracy_contact must be > 0')],
+                       Extra('accuracy_rows', Field('accuracy_rows', F64, ('L', 4), False), lambda last: last['accuracy_rows'], lambda t: t.cpu().numpy()))
+
+
+# --polar: the unsatisfied atoms come from the point counts of the interface analysis, so polar is coupled to --interface in three
+# places: with --interface the scorer is built on THAT InterfaceScorer and the surface kernel runs once per structure set for both tables
+# (sampler.sample_fn hands the counts over); one buffer of counts serves both wild rows (_shared_wild_points); and without --interface
+# polar validates the options of the surface, --interface_points and --interface_probe, itself.
+POLAR_CHECKS = [(lambda a: not a.polar_hb_max >= 2.0 or not 90.0 <= a.polar_hb_angle < 180.0 or not a.polar_salt >= 0,
+                 '--polar_hb_max must be >= 2.0 (the smallest donor-acceptor distance), --polar_hb_angle in [90, 180), --polar_salt >= 0'),
+                (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')]
+
+
+def _polar_build(batch, a, model, cfg, scorers):
+    pol = polar.PolarScorer(batch, hb_max=a.polar_hb_max, hb_angle=a.polar_hb_angle, salt=a.polar_salt, n_points=a.interface_points,
+                            probe=a.interface_probe, interface=scorers.get('interface'))
+    pol.want_rows = a.polar_rows
+    return pol
+
+
+def _shared_wild_points(scorers):
+    """--polar with --interface: the (1, L, 14, 2) point counts of the wild type that interface.wild() fills and polar.wild() reads
+    instead of running the surface kernel again, kept with the scorers of the batch; None without both."""
+    if 'polar' in scorers and 'interface' in scorers and 'wild_points' not in scorers:
+        scorers['wild_points'] = scorers['polar'].new_points(1)
+    return scorers.get('wild_points')
+
+
+_write_polar = functools.partial(_write_with_wild_deltas, 'polar')
+POLAR = _wild_table('polar', polar.POLAR_COLUMNS, _write_polar, _polar_build, lambda last, scorers: scorers['polar'].wild(points=_shared_wild_points(scorers)),
+                    POLAR_CHECKS, Extra('polar_rows', Field('polar_rows', torch.int32, ('L', 4), False), lambda last: last['polar_rows'],
+                                        lambda t: t.cpu().numpy().astype('int16')))
+
+
+# --ensemble: the designs of a complex compared with each other (ensemble.EnsembleAnalyzer) by the rank that writes, after the gather: the
+# backbone of the antibody travels with the other fields.  <complex>_ensemble.tsv; --ensemble_matrix: <complex>_ensemble_rmsd.npy, the
+# (3, N, N) planes rmsd_fit, rmsd_frame, seq_diff.  With --relax the analysis still describes the designs as written.
+def _write_ensemble(out_dir, cname, summ, rows, centres):
+    """<out_dir>/<complex>_ensemble.tsv: the `all` line, then (sample id, ensemble.ENSEMBLE_COLUMNS values) per sample in row order.
+    summ: ensemble.summary of the table; centres: the rows' positions of the cluster centres in order of discovery.  Columns: the row,
+    `representative` (sample id of the centre of the row's cluster), then the summary's own columns prefixed all_ (nan on sample
+    lines); the three means of the summary stand in their ENSEMBLE_COLUMNS on the `all` line."""
+    from .ensemble import ENSEMBLE_COLUMNS, format_ensemble, format_summary
+    own = [c for c in summ if c not in ENSEMBLE_COLUMNS]
+    fs = dict(zip(summ, format_summary(summ)))
+    tsv = os.path.join(out_dir, f'{cname}_ensemble.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(ENSEMBLE_COLUMNS + ('representative',) + tuple('all_' + c for c in own)) + '\n')
+        f.write('all\t' + '\t'.join([fs.get(c, 'nan') for c in ENSEMBLE_COLUMNS] + ['nan'] + [fs[c] for c in own]) + '\n')
+        for i, v in rows:
+            f.write(f'{i}\t' + '\t'.join(format_ensemble(v) + [str(rows[centres[int(v[0])]][0])] + ['nan'] * len(own)) + '\n')
+    return tsv
+
+
+def _ensemble_write(a, out_dir, cname, ids, F, an):
+    """The ensemble tables from the gathered tokens (N, Lab) and backbone (N, Lab, 4, 3); an: the EnsembleAnalyzer of the complex."""
+    dev = an.region.device
+    x = torch.zeros(F['seq'].shape[0], an.Lab, 14, 3, dtype=torch.float32, device=dev)
+    x[:, :, :4] = F['backbone'].to(dev)
+    res = an.analyze(x, F['seq'].to(dev).long())
+    table = res['table'].cpu().numpy()
+    centres = res['centres'].cpu().tolist()[:int(res['n_clusters'])]
+    files = [_write_ensemble(out_dir, cname, ensemble.summary(table, an.n_region), list(zip(ids, table.tolist())), centres)]
+    return files + ([_save(out_dir, cname, 'ensemble_rmsd', res['planes'].cpu().numpy())] if a.ensemble_matrix else [])
+
+
+ENSEMBLE = Analysis('ensemble', None, lambda batch, a, *_: ensemble.EnsembleAnalyzer(batch, atoms=a.ensemble_atoms, metric=a.ensemble_metric, cutoff=a.ensemble_cutoff),
+                    lambda a: [Field('backbone', torch.float32, ('Lab', 4, 3), True)],      # N, CA, C, O of the antibody rows: what the comparison reads
+                    lambda a, traj, scorers: {'backbone': traj[-1]['atom14_results'][:, :, :4].float().contiguous()}, _ensemble_write,
+                    [(lambda a: not 1 <= a.num_samples <= ensemble.MAX_N or not a.ensemble_cutoff >= 0,
+                      f'--ensemble compares 1..{ensemble.MAX_N} samples of a complex, --ensemble_cutoff must be >= 0')])
+
+ANALYSES = (SCORE, RELAX, INTERFACE, CONFIDENCE, ACCURACY, POLAR, ENSEMBLE)
+
+
+def check_options(a, set_level):
+    """The analyses that the parsed options `a` switch on, in order, after their option checks.  set_level: the run gathers rows."""
+    active = []
+    for an in ANALYSES:
+        if getattr(a, an.flag):
+            for bad, text in an.checks:
+                if bad(a):
+                    raise SystemExit(text)
+            if an.extra and getattr(a, an.extra) and set_level:
+                raise SystemExit(f'--{an.extra} needs the sample-sharded schedule (--shard_samples): a set-level run gathers one table only')
+            active.append(an)
+        elif an.extra and getattr(a, an.extra):
+            raise SystemExit(f'--{an.extra} needs --{an.flag}')
+    return active
+
+
+def fields_of(active, a):
+    return list(HEAD) + [f for an in active for f in an.fields(a)]
+
+
+def collect(active, a, traj, scorers):
+    """The fields of a sampled batch, keyed and ordered as declared (one gather per field, in this order on every rank)."""
+    got = {'seq': traj[-1]['seq'], 'pLDDT': traj[-1]['pLDDT']}
+    for an in active:
+        got.update(an.collect(a, traj, scorers))
+    assert list(got) == [f.name for f in fields_of(active, a)], list(got)
+    return got
+
+
+def zero_rows(active, a, L, Lab, device):
+    """The block of a rank without samples of a complex: it still joins the gather."""
+    return {f.name: torch.zeros(0, *block_shape(f, L, Lab), dtype=f.dtype, device=device) for f in fields_of(active, a)}
+
+
+class RowLayout:
+    """Columns of the (n, WIDTH) float64 row table of a set-level run: job, sample id, mean pLDDT, Lab, then one span per field that
+    travels in rows, wide enough for the longest antibody of the set (maxLab) and filled up to the job's own Lab.  Every value is exact
+    in float64: tokens, float32 coordinates, and the float32 mean of pLDDT that the sample-sharded path prints too."""
+    def __init__(self, fields, maxLab):
+        self.fields, self.spans, c = [f for f in fields if f.rows], {}, 4
+        for f in self.fields:
+            self.spans[f.name] = (c, c + math.prod(block_shape(f, 0, maxLab)))
+            c = self.spans[f.name][1]
+        self.WIDTH = c
+
+    def pack(self, ji, ids, local):
+        """The rows of the samples `ids` of job ji from their fields (on any device) -> (n, WIDTH) on the host."""
+        n, Lab = local['seq'].shape
+        rows = torch.zeros(n, self.WIDTH, dtype=F64)
+        rows[:, 0], rows[:, 1], rows[:, 3] = ji, torch.tensor(ids, dtype=F64), Lab
+        rows[:, 2] = local['pLDDT'].float().mean(1).double().cpu()
+        for f in self.fields:
+            v = local[f.name].reshape(n, -1).double().cpu()
+            rows[:, self.spans[f.name][0]:self.spans[f.name][0] + v.shape[1]] = v
+        return rows
+
+    def unpack(self, rows):
+        """The rows of ONE job in any order -> (sample ids, {field: (n, ...)}) in the order of the sample ids, 'mean_pLDDT' for 'pLDDT'."""
+        rows = rows[torch.argsort(rows[:, 1])]
+        n, Lab = rows.shape[0], int(rows[0, 3])
+        F = {'mean_pLDDT': rows[:, 2]}
+        for f in self.fields:
+            shape, c = block_shape(f, 0, Lab), self.spans[f.name][0]
+            F[f.name] = rows[:, c:c + math.prod(shape)].to(f.dtype).reshape(n, *shape)
+        return [int(i) for i in rows[:, 1]], F
+
+
+def write_job(active, a, out_dir, cname, ids, F, kept_scorer):
+    """The tables of one complex from the form both schedules end in: the sample ids and the gathered fields F = {name: (n, ...)} in their
+    order, 'mean_pLDDT' (n) among them.  kept_scorer(an): the per-complex scorer of an analysis that runs after the gather."""
+    sc = F['scores'].tolist() if 'scores' in F else None
+    files = [_write_designs(out_dir, cname, [(i, float(pl), toks) + ((sc[k],) if sc else ()) for k, (i, pl, toks) in
+                                             enumerate(zip(ids, F['mean_pLDDT'], F['seq'].tolist()))])]
+    for an in active:
+        files += an.write(a, out_dir, cname, ids, F, kept_scorer(an) if an.kw is None else None)
+    return files

@@ -65,6 +65,7 @@ class DistogramScorer(complex_view.ComplexView):
     0's (1 - fixed_mask) * backbone mask); cutoff: contact distance of the pseudo-beta atoms (Angstrom)."""
 
     COLUMNS = CONFIDENCE_COLUMNS
+    want_planes = False                 # set on an instance: sampler.sample_fn also records 'confidence_planes'
 
     def __init__(self, batch, params_or_model, region=None, cutoff=8.0, conf=None):
         import torch

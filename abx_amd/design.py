@@ -28,49 +28,18 @@ Multi-GPU (one process per GPU under torch.distributed.run): the SAMPLES of ever
 (sampler.shard_sample_ids: contiguous blocks; per-sample noise keys, so a sample's trajectory does not depend on where it runs),
 every rank writes the PDB files of its own samples, and the designed sequences / pLDDT are gathered with one RCCL all_gather per
 field (sampler.gather_results) for `<output_dir>/<complex>_designs.tsv`, written by rank 0.
---score: every design is scored on the GPU as its record is made (abx_amd.metrics.DesignScorer, one launch pair per record, no host
-synchronisation); the scores travel as one more field of the same gathers and become the columns metrics.SCORE_COLUMNS of the TSV.
---relax: every design is relaxed on the GPU after the last step (abx_amd.relax.ViolationRelaxer, abx_relax: one launch per batch): the
-violation energy of the designed residues (+ --relax_flank linked neighbours on each side) is minimised over rigid-body motions and chi
-angles of those residues; <name>_relaxed.pdb is written beside every design (upstream's naming, which its eval_metric.py skips) and
-<output_dir>/<complex>_relax.tsv holds one line per sample: relax.RELAX_COLUMNS and, with --score, the scores of the relaxed structure.
-The design files and <complex>_designs.tsv are what they are without --relax.
---interface: every design gets its interface row on the GPU after the last step (abx_amd.interface.InterfaceScorer, abx_interface_scores):
-solvent-accessible surface buried between the antibody and the featurised antigen (a cropped patch when the complex was cropped),
-interface residues and heavy-atom contacts, with the designed residues as the region.  <output_dir>/<complex>_interface.tsv holds a
-`wild` line (the input complex itself) and one line per sample: interface.INTERFACE_COLUMNS, then delta_<column> = design minus wild
-type for interface.DELTA_COLUMNS (the geometric analogue of upstream's ddG) and, with --relax, the columns of the relaxed structure
-suffixed _relaxed (nan on the wild line).  No other output file changes.
---ensemble: the N designs of a complex are compared with each other on the GPU (abx_amd.ensemble.EnsembleAnalyzer, abx_ensemble_pairs +
-abx_ensemble_cluster) by the rank that writes the tables, after the gather: the backbone of the designed antibody travels with the other
-fields.  <output_dir>/<complex>_ensemble.tsv holds an `all` line (clusters, unique sequences, mean pairwise RMSD and sequence identity)
-and one line per sample: ensemble.ENSEMBLE_COLUMNS and `representative`, the sample id of the centre of the sample's cluster - the few
-files worth the expensive evaluation.  --ensemble_matrix also writes <complex>_ensemble_rmsd.npy, the (3, N, N) planes rmsd_fit,
-rmsd_frame, seq_diff.  With --relax the analysis still describes the designs as written.  No other output file changes.
---confidence: every design gets its confidence row on the GPU right after the last network call (abx_amd.confidence.DistogramScorer,
-abx_distogram_scores): the checkpoint's distogram head on the pair representation of that call - the network's own distribution over
-every pseudo-beta distance - against the structure it emitted.  <output_dir>/<complex>_confidence.tsv holds a `wild` line (the input
-complex's own coordinates against the same predictions, the mean over the designs), one line per sample: confidence.CONFIDENCE_COLUMNS,
-then delta_<column> = design minus the wild type under the SAME design's prediction for confidence.DELTA_COLUMNS and, with --relax, the
-columns of the relaxed structure suffixed _relaxed (nan on the wild line).  --confidence_planes also writes
-<complex>_confidence_contacts.npy, the mean predicted contact probability over the designs, (L, L) (sample-sharded runs only: the planes
-of a set-level schedule would travel as 8 L^2 bytes per sample).  No other output file changes.
---accuracy: every design is compared with the input crystal structure on the GPU after the last step (abx_amd.accuracy.AccuracyScorer,
-abx_accuracy_scores): all-atom / backbone / C-alpha lDDT (the quantity pLDDT predicts) with the designed residues as the region, the
-calibration of the per-residue pLDDT of the last network call, TM-score / GDT-TS / GDT-HA / RMSD of the C-alpha (upstream's TMscoreHead)
-and the native antibody-antigen residue contacts that survive (DockQ's Fnat).  <output_dir>/<complex>_accuracy.tsv holds a `wild` line
-(the input complex against itself: every lDDT and fnat 1, rmsd_ca 0) and one line per sample: accuracy.ACCURACY_COLUMNS and, with
---relax, the columns of the relaxed structure suffixed _relaxed (nan on the wild line), then delta_<column> = relaxed minus design for
-accuracy.DELTA_COLUMNS.  --accuracy_rows also writes <complex>_accuracy_rows.npy, the per-residue lDDT (N, L, 4: accuracy.ROW_COLUMNS;
-sample-sharded runs only).  No other output file changes.
---polar: every design gets its polar row on the GPU after the last step (abx_amd.polar.PolarScorer, abx_polar_scores): heavy-atom hydrogen
-bonds and salt bridges between the antibody and the featurised antigen, the hydrogen bonds that hold the designed loop, and the polar
-atoms that binding buries without a partner (from the point counts of the interface analysis; with --interface the surface kernel runs
-once for both tables).  <output_dir>/<complex>_polar.tsv holds a `wild` line (the input complex itself) and one line per sample:
-polar.POLAR_COLUMNS, then delta_<column> = design minus wild type for polar.DELTA_COLUMNS and, with --relax, the columns of the relaxed
-structure suffixed _relaxed (nan on the wild line).  --polar_rows also writes <complex>_polar_rows.npy, (N, L, 4) int16 per residue:
-cross-side and same-side hydrogen bonds, salt bridges, unsatisfied atoms (polar.ROW_COLUMNS; sample-sharded runs only).  No other output
-file changes.
+The per-design analyses run on the GPU without a host synchronisation in the sampling loop; abx_amd.analyses states each of them once.
+--score: per-CDR RMSD / AAR, violation and clash counts as further columns of <complex>_designs.tsv; in trajectory mode also
+<complex>_trajectory_scores.tsv.  --relax: rigid-body + chi minimisation of the violation energy of the designed residues;
+<name>_relaxed.pdb beside every design, <complex>_relax.tsv, and _relaxed columns in the four tables that follow, each with a `wild`
+line for the input complex and one line per sample.  --interface: buried surface, interface residues and contacts,
+<complex>_interface.tsv.  --confidence: the distogram head of the last network call against the emitted structure,
+<complex>_confidence.tsv (--confidence_planes: also <complex>_confidence_contacts.npy).  --accuracy: lDDT, TM-score / GDT / RMSD and
+Fnat against the input structure, <complex>_accuracy.tsv (--accuracy_rows: also <complex>_accuracy_rows.npy).  --polar: hydrogen bonds,
+salt bridges and unsatisfied polar atoms across the interface, <complex>_polar.tsv (--polar_rows: also <complex>_polar_rows.npy).
+--ensemble: the designs of a complex compared with each other, Daura clusters and their centres, <complex>_ensemble.tsv
+(--ensemble_matrix: also <complex>_ensemble_rmsd.npy).  No flag changes a file that another one writes; the _rows / _planes tables need
+the sample-sharded schedule (--shard_samples).
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -78,7 +47,9 @@ from collections import OrderedDict
 
 import torch
 
-from . import features, sampler, synthetic
+from . import analyses, features, sampler, synthetic
+from .analyses import (_write_accuracy, _write_confidence, _write_designs, _write_ensemble, _write_interface, _write_polar,      # noqa: F401
+                       _write_relax, _write_trajectory_scores)                 # (the table writers, under the names the host tests call)
 from .config import default_config, load_config
 from .diffuser.full_diffuser import FullDiffuser
 from .io import TrajectoryWriter, index_to_str_seq
@@ -118,129 +89,6 @@ def read_model_features(path):
         if 'diffuse' in name:
             return opts.get('generate_area', 'H3'), list(opts.get('optimize_steps', []))
     return 'H3', []
-
-
-def _write_designs(out_dir, cname, rows):
-    """<out_dir>/<complex>_designs.tsv: (sample id, mean pLDDT, designed antibody sequence) per sample; with --score a row carries
-    a fourth entry, its metrics.SCORE_COLUMNS values, written as further columns."""
-    tsv = os.path.join(out_dir, f'{cname}_designs.tsv')
-    scored = bool(rows) and len(rows[0]) > 3
-    with open(tsv, 'w') as f:
-        if scored:
-            from .metrics import SCORE_COLUMNS, format_scores
-            f.write('sample\tmean_pLDDT\tantibody_sequence\t' + '\t'.join(SCORE_COLUMNS) + '\n')
-            for i, pl, toks, sc in rows:
-                f.write(f'{i}\t{pl:.3f}\t{index_to_str_seq(toks)}\t' + '\t'.join(format_scores(sc)) + '\n')
-        else:
-            f.write('sample\tmean_pLDDT\tantibody_sequence\n')
-            for i, pl, toks in rows:
-                f.write(f'{i}\t{pl:.3f}\t{index_to_str_seq(toks)}\n')
-    return tsv
-
-
-def _write_trajectory_scores(out_dir, cname, table):
-    """<out_dir>/<complex>_trajectory_scores.tsv: one line per (sample, record of the trajectory).  table (samples, records, 1 + columns):
-    t of the record, then its metrics.SCORE_COLUMNS values."""
-    from .metrics import SCORE_COLUMNS, format_scores
-    tsv = os.path.join(out_dir, f'{cname}_trajectory_scores.tsv')
-    with open(tsv, 'w') as f:
-        f.write('sample\tstep\tt\t' + '\t'.join(SCORE_COLUMNS) + '\n')
-        for i, recs in enumerate(table.tolist()):
-            for k, r in enumerate(recs):
-                f.write(f'{i}\t{k}\t{r[0]:.4f}\t' + '\t'.join(format_scores(r[1:])) + '\n')
-    return tsv
-
-
-def _write_relax(out_dir, cname, rows, scored):
-    """<out_dir>/<complex>_relax.tsv: (sample id, values) per sample; values = the relax.RELAX_COLUMNS report and, when scored, the
-    metrics.SCORE_COLUMNS of the relaxed structure."""
-    from .relax import RELAX_COLUMNS, format_report
-    from .metrics import SCORE_COLUMNS, format_scores
-    NR = len(RELAX_COLUMNS)
-    tsv = os.path.join(out_dir, f'{cname}_relax.tsv')
-    with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(RELAX_COLUMNS + (SCORE_COLUMNS if scored else ())) + '\n')
-        for i, v in rows:
-            f.write(f'{i}\t' + '\t'.join(format_report(v[:NR]) + (format_scores(v[NR:]) if scored else [])) + '\n')
-    return tsv
-
-
-def _write_with_wild_deltas(kind, out_dir, cname, wild, rows, relaxed):
-    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar): the `wild` line, then (sample id, values)
-    per sample; values = the module's <KIND>_COLUMNS row and, when relaxed, the row of the relaxed structure.  After the columns:
-    delta_<column> = row minus wild for the module's DELTA_COLUMNS."""
-    import importlib
-    mod = importlib.import_module(f'.{kind}', __package__)
-    columns, fmt = getattr(mod, f'{kind.upper()}_COLUMNS'), getattr(mod, f'format_{kind}')
-    N = len(columns)
-    tsv = os.path.join(out_dir, f'{cname}_{kind}.tsv')
-    with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(columns + tuple('delta_' + c for c in mod.DELTA_COLUMNS) +
-                                       (tuple(c + '_relaxed' for c in columns) if relaxed else ())) + '\n')
-        f.write('wild\t' + '\t'.join(fmt(wild) + mod.format_delta(wild, wild) + (['nan'] * N if relaxed else [])) + '\n')
-        for i, v in rows:
-            f.write(f'{i}\t' + '\t'.join(fmt(v[:N]) + mod.format_delta(v[:N], wild) + (fmt(v[N:2 * N]) if relaxed else [])) + '\n')
-    return tsv
-
-
-def _write_interface(out_dir, cname, wild, rows, relaxed):
-    return _write_with_wild_deltas('interface', out_dir, cname, wild, rows, relaxed)
-
-
-def _write_polar(out_dir, cname, wild, rows, relaxed):
-    return _write_with_wild_deltas('polar', out_dir, cname, wild, rows, relaxed)
-
-
-def _write_accuracy(out_dir, cname, wild, rows, relaxed):
-    """<out_dir>/<complex>_accuracy.tsv: the `wild` line, then (sample id, values) per sample; values = the accuracy.ACCURACY_COLUMNS row
-    and, when relaxed, the row of the relaxed structure followed by delta_<column> = relaxed minus design for accuracy.DELTA_COLUMNS."""
-    from .accuracy import ACCURACY_COLUMNS, DELTA_COLUMNS, format_accuracy, format_delta
-    NA = len(ACCURACY_COLUMNS)
-    tsv = os.path.join(out_dir, f'{cname}_accuracy.tsv')
-    with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(ACCURACY_COLUMNS + ((tuple(c + '_relaxed' for c in ACCURACY_COLUMNS) +
-                                                             tuple('delta_' + c for c in DELTA_COLUMNS)) if relaxed else ())) + '\n')
-        f.write('wild\t' + '\t'.join(format_accuracy(wild) + (['nan'] * (NA + len(DELTA_COLUMNS)) if relaxed else [])) + '\n')
-        for i, v in rows:
-            f.write(f'{i}\t' + '\t'.join(format_accuracy(v[:NA]) +
-                                          ((format_accuracy(v[NA:2 * NA]) + format_delta(v[NA:2 * NA], v[:NA])) if relaxed else [])) + '\n')
-    return tsv
-
-
-def _write_confidence(out_dir, cname, rows, relaxed):
-    """<out_dir>/<complex>_confidence.tsv: the `wild` line, then (sample id, values) per sample; values = the confidence.CONFIDENCE_COLUMNS
-    row, when relaxed the row of the relaxed structure, and last the sample's own wild row (the input complex's coordinates against the
-    sample's prediction).  wild line: the mean of the wild rows.  After the columns: delta_<column> = row minus the sample's wild row."""
-    from .confidence import CONFIDENCE_COLUMNS, DELTA_COLUMNS, format_confidence, format_delta
-    NC = len(CONFIDENCE_COLUMNS)
-    tsv = os.path.join(out_dir, f'{cname}_confidence.tsv')
-    wilds = [v[len(v) - NC:] for _, v in rows]
-    wild = [sum(w[k] for w in wilds) / max(len(wilds), 1) for k in range(NC)]
-    with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(CONFIDENCE_COLUMNS + tuple('delta_' + c for c in DELTA_COLUMNS) +
-                                       (tuple(c + '_relaxed' for c in CONFIDENCE_COLUMNS) if relaxed else ())) + '\n')
-        f.write('wild\t' + '\t'.join(format_confidence(wild) + format_delta(wild, wild) + (['nan'] * NC if relaxed else [])) + '\n')
-        for (i, v), w in zip(rows, wilds):
-            f.write(f'{i}\t' + '\t'.join(format_confidence(v[:NC]) + format_delta(v[:NC], w) +
-                                          (format_confidence(v[NC:2 * NC]) if relaxed else [])) + '\n')
-    return tsv
-
-
-def _write_ensemble(out_dir, cname, summ, rows, centres):
-    """<out_dir>/<complex>_ensemble.tsv: the `all` line, then (sample id, ensemble.ENSEMBLE_COLUMNS values) per sample in row order.
-    summ: ensemble.summary of the table; centres: the rows' positions of the cluster centres in order of discovery.  Columns: the row,
-    `representative` (sample id of the centre of the row's cluster), then the summary's own columns prefixed all_ (nan on sample
-    lines); the three means of the summary stand in their ENSEMBLE_COLUMNS on the `all` line."""
-    from .ensemble import ENSEMBLE_COLUMNS, format_ensemble, format_summary
-    own = [c for c in summ if c not in ENSEMBLE_COLUMNS]
-    fs = dict(zip(summ, format_summary(summ)))
-    tsv = os.path.join(out_dir, f'{cname}_ensemble.tsv')
-    with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(ENSEMBLE_COLUMNS + ('representative',) + tuple('all_' + c for c in own)) + '\n')
-        f.write('all\t' + '\t'.join([fs.get(c, 'nan') for c in ENSEMBLE_COLUMNS] + ['nan'] + [fs[c] for c in own]) + '\n')
-        for i, v in rows:
-            f.write(f'{i}\t' + '\t'.join(format_ensemble(v) + [str(rows[centres[int(v[0])]][0])] + ['nan'] * len(own)) + '\n')
-    return tsv
 
 
 def _relaunch_on_gpus(gpu_list, argv):
@@ -457,85 +305,25 @@ def main(argv=None):
         if a.verbose or rank == 0:
             print(f'set-level schedule: {sum(len(p) for p in plan)} units of >= {min(a.min_block, N)} samples over {world} ranks; '
                   f'rank {rank} runs {[(jobs[ji][1], len(ids_)) for ji, ids_ in work]}')
-    set_rows = []                                               # set-level mode: (job, sample id, mean pLDDT, Lab, tokens...) rows of this rank
-    maxLab = max([load_job(ji)['Lab'] for ji in range(len(jobs))]) if plan is not None else 0
-    NS = 0                                                      # --score: score columns per sample (+ (t, scores) of every trajectory record)
-    if a.score:
-        from .metrics import SCORE_COLUMNS, DesignScorer
-        NS = len(SCORE_COLUMNS)
-    n_rec = a.num_t if (a.score and a.mode == 'trajectory') else 0
-    NR = 0                                                      # --relax: report columns per sample (+ the scores of the relaxed structure)
-    if a.relax:
-        from .relax import RELAX_COLUMNS, ViolationRelaxer
-        NR = len(RELAX_COLUMNS) + NS
-    NI = 0                                                      # --interface: the row (+ that of the relaxed structure) + the wild type's row
-    if a.interface:
-        from .interface import INTERFACE_COLUMNS, InterfaceScorer
-        if not 1 <= a.interface_points <= 1024 or a.interface_probe < 0 or a.interface_cutoff <= 0:
-            raise SystemExit('--interface_points must be in 1..1024, --interface_probe >= 0, --interface_cutoff > 0')
-        NI = len(INTERFACE_COLUMNS) * (3 if a.relax else 2)
-    NCF = 0                                                     # --confidence: the row (+ that of the relaxed structure) + the sample's wild row
-    if a.confidence:
-        from .confidence import CONFIDENCE_COLUMNS, DistogramScorer
-        if not a.confidence_cutoff > 0:
-            raise SystemExit('--confidence_cutoff must be > 0')
-        if a.confidence_planes and plan is not None:
-            raise SystemExit('--confidence_planes needs the sample-sharded schedule (--shard_samples): a set-level run gathers one table only')
-        NCF = len(CONFIDENCE_COLUMNS) * (3 if a.relax else 2)
-    elif a.confidence_planes:
-        raise SystemExit('--confidence_planes needs --confidence')
-    NA = 0                                                      # --accuracy: the row (+ that of the relaxed structure) + the wild type's row
-    if a.accuracy:
-        from .accuracy import ACCURACY_COLUMNS, AccuracyScorer
-        if not a.accuracy_radius > 0 or not a.accuracy_contact > 0:
-            raise SystemExit('--accuracy_radius and --accuracy_contact must be > 0')
-        if a.accuracy_rows and plan is not None:
-            raise SystemExit('--accuracy_rows needs the sample-sharded schedule (--shard_samples): a set-level run gathers one table only')
-        NA = len(ACCURACY_COLUMNS) * (3 if a.relax else 2)
-    elif a.accuracy_rows:
-        raise SystemExit('--accuracy_rows needs --accuracy')
-    NP = 0                                                      # --polar: the row (+ that of the relaxed structure) + the wild type's row
-    if a.polar:
-        from .polar import POLAR_COLUMNS, PolarScorer
-        if not a.polar_hb_max >= 2.0 or not 90.0 <= a.polar_hb_angle < 180.0 or not a.polar_salt >= 0:
-            raise SystemExit('--polar_hb_max must be >= 2.0 (the smallest donor-acceptor distance), --polar_hb_angle in [90, 180), --polar_salt >= 0')
-        if not 1 <= a.interface_points <= 1024 or a.interface_probe < 0:
-            raise SystemExit('--interface_points must be in 1..1024, --interface_probe >= 0')
-        if a.polar_rows and plan is not None:
-            raise SystemExit('--polar_rows needs the sample-sharded schedule (--shard_samples): a set-level run gathers one table only')
-        NP = len(POLAR_COLUMNS) * (3 if a.relax else 2)
-    elif a.polar_rows:
-        raise SystemExit('--polar_rows needs --polar')
-    NE = 0                                                      # --ensemble, set-level rows: the antibody backbone (maxLab, 4, 3), f32 values
-    analyzers = {}                                              # --ensemble: job -> EnsembleAnalyzer (the compared rows of the complex)
-    if a.ensemble:
-        from . import ensemble
-        if not 1 <= N <= ensemble.MAX_N or not a.ensemble_cutoff >= 0:
-            raise SystemExit(f'--ensemble compares 1..{ensemble.MAX_N} samples of a complex, --ensemble_cutoff must be >= 0')
-        NE = 12 * maxLab
-    E0 = 4 + maxLab + NS + n_rec * (1 + NS)                     # set-level rows: the backbone columns follow the scores
-    WIDTH = E0 + NE + NCF + NA + NP + NR + NI                   # (the confidence, accuracy and polar columns sit between the backbone and the relax report)
+    set_rows = []                                               # set-level mode: the rows of this rank (analyses.RowLayout)
+    active = analyses.check_options(a, set_level=plan is not None)
+    layout = analyses.RowLayout(analyses.fields_of(active, a), max(load_job(ji)['Lab'] for ji in range(len(jobs)))) if plan is not None else None
 
-    def analyze_ensemble(ji, out_dir, cname, ids, seq, backbone):
-        """The ensemble tables of job ji from the gathered tokens (N, Lab) and backbone (N, Lab, 4, 3) in the order of `ids`."""
-        import numpy as np
-        if ji not in analyzers:                                 # a complex this rank did not sample: its features give the compared rows
-            J = load_job(ji)
-            raw = {k: v.to(dev) for k, v in J['one'].items()}
-            fb = features.build_features(raw, diffuser, generate_area=a.generate_area, opt_step=jobs[ji][3] if a.mode == 'optimize' else None,
-                                         noise=features.per_sample_init_noise([0], J['L'], a.seed, dev))
-            analyzers[ji] = ensemble.EnsembleAnalyzer(fb, atoms=a.ensemble_atoms, metric=a.ensemble_metric, cutoff=a.ensemble_cutoff)
-        an = analyzers[ji]
-        x = torch.zeros(seq.shape[0], an.Lab, 14, 3, dtype=torch.float32, device=dev)
-        x[:, :, :4] = backbone.to(dev)
-        res = an.analyze(x, seq.to(dev).long())
-        table = res['table'].cpu().numpy()
-        centres = res['centres'].cpu().tolist()[:int(res['n_clusters'])]
-        out = [_write_ensemble(out_dir, cname, ensemble.summary(table, an.n_region), list(zip(ids, table.tolist())), centres)]
-        if a.ensemble_matrix:
-            out.append(os.path.join(out_dir, f'{cname}_ensemble_rmsd.npy'))
-            np.save(out[-1], res['planes'].cpu().numpy())
-        return out
+    def featurise(ji, ids):
+        """The featurised batch of the samples `ids` of job ji on the device."""
+        J = load_job(ji)
+        raw = {k: v.to(dev).expand(len(ids), *v.shape[1:]).contiguous() for k, v in J['one'].items()}
+        return features.build_features(raw, diffuser, generate_area=a.generate_area, opt_step=jobs[ji][3] if a.mode == 'optimize' else None,
+                                       noise=features.per_sample_init_noise(ids, J['L'], a.seed, dev))
+
+    kept = {}
+
+    def kept_scorer(an, ji, batch=None):
+        """The scorer of an analysis that runs after the gather: one per complex, from the first batch this rank sampled of it or, for a
+        complex the rank did not sample, from one featurised sample (the scorer reads what all samples share)."""
+        if (an.flag, ji) not in kept:
+            kept[an.flag, ji] = an.build(batch if batch is not None else featurise(ji, [0]), a, model, cfg, {})
+        return kept[an.flag, ji]
 
     ref_written = set()
     for ji, ids in work:
@@ -545,7 +333,6 @@ def main(argv=None):
         os.makedirs(out_dir, exist_ok=True)
         J = load_job(ji)
         cname, L, Lab = J['cname'], J['L'], J['Lab']
-        one = {k: v.to(dev) for k, v in J['one'].items()}
         if kind in ('pdb', 'npz'):
             cb = J['cb']
             meta = {k: list(cb[k]) * n for k in ('str_heavy_seq', 'str_light_seq', 'antigen_origin_str_seq',
@@ -559,6 +346,7 @@ def main(argv=None):
                 ref_written.add((cname, ref_dir))
                 ref_meta = {k: list(cb[k]) for k in meta}
                 ref_meta['name'] = [cname]
+                one = {k: J['one'][k].to(dev) for k in ('seq', 'atom14_gt_positions')}
                 files += postprocess_trajectory(ref_meta, [{'seq': one['seq'][:, :Lab], 'atom14_results': one['atom14_gt_positions'][:, :Lab],
                                                             'pLDDT': torch.full((1, Lab), 100.0), 'time': 0.0}], ref_dir)
         else:
@@ -571,37 +359,18 @@ def main(argv=None):
         else:
             meta['name'] = sample_names(cname, ids, N)
         if n > 0:
-            raw = {k: v.expand(n, *v.shape[1:]).contiguous() for k, v in one.items()}
-            batch = features.build_features(raw, diffuser, generate_area=a.generate_area,
-                                            opt_step=opt_step if a.mode == 'optimize' else None,
-                                            noise=features.per_sample_init_noise(ids, L, a.seed, dev))
+            batch = featurise(ji, ids)
             batch['_shared_context'] = True
             diffuser.seed = a.seed
             writer = TrajectoryWriter(meta, out_dir, multi=a.mode == 'trajectory')
-            iface = InterfaceScorer(batch, n_points=a.interface_points, probe=a.interface_probe, cutoff=a.interface_cutoff) if a.interface else None
-            conf = None
-            if a.confidence:
-                conf = DistogramScorer(batch, model, cutoff=a.confidence_cutoff, conf=cfg.model.heads.distogram)
-                conf.want_planes = a.confidence_planes
-            acc = AccuracyScorer(batch, radius=a.accuracy_radius, contact=a.accuracy_contact) if a.accuracy else None
-            pol = None
-            if a.polar:                                         # (with --interface: one surface call per structure set serves both tables)
-                pol = PolarScorer(batch, hb_max=a.polar_hb_max, hb_angle=a.polar_hb_angle, salt=a.polar_salt, n_points=a.interface_points,
-                                  probe=a.interface_probe, interface=iface)
-                pol.want_rows = a.polar_rows
-            if a.ensemble and ji not in analyzers:
-                analyzers[ji] = ensemble.EnsembleAnalyzer(batch, atoms=a.ensemble_atoms, metric=a.ensemble_metric, cutoff=a.ensemble_cutoff)
+            scorers = {}                                        # by flag, in the order of the analyses: a later one may build on an earlier one
+            for an in active:
+                scorers[an.flag] = an.build(batch, a, model, cfg, scorers) if an.kw else kept_scorer(an, ji, batch)
             torch.cuda.synchronize()
             t_feat = time.perf_counter()
             traj = sampler.sample_fn(batch, cfg, diffuser, model, mode=a.mode, num_t=a.num_t,
                                      sample_ids=torch.tensor(ids, device=dev, dtype=torch.int64), on_record=writer.submit, guidance=guide,
-                                     **({'scorer': DesignScorer(batch)} if a.score else {}),
-                                     **({'relaxer': ViolationRelaxer(batch, flank=a.relax_flank, max_iter=a.relax_iters,
-                                                                     k_restraint=a.relax_restraint)} if a.relax else {}),
-                                     **({'interface': iface} if a.interface else {}),
-                                     **({'confidence': conf} if a.confidence else {}),
-                                     **({'accuracy': acc} if a.accuracy else {}),
-                                     **({'polar': pol} if a.polar else {}))
+                                     **{an.kw: scorers[an.flag] for an in active if an.kw})
             torch.cuda.synchronize()
             t_samp = time.perf_counter()
             new_files = writer.close()
@@ -616,121 +385,21 @@ def main(argv=None):
                                 sampling_s=t_samp - t_feat, writer_tail_s=t_done - t_samp, files=len(new_files),
                                 range_fallbacks=len(traj[-1].get('range_fallbacks', [])),
                                 range_sticky_ops=list(traj[-1].get('range_sticky_ops', []))))
-            local = {'seq': traj[-1]['seq'], 'pLDDT': traj[-1]['pLDDT']}
-            if a.score:
-                local['scores'] = traj[-1]['scores']
-                if n_rec:                                       # (samples, records, 1 + NS): t, then the scores of the record
-                    local['traj_scores'] = torch.stack([torch.cat([torch.full((n, 1), r['time'], dtype=torch.float64, device=dev), r['scores']], 1)
-                                                        for r in traj], 1)
-            if a.relax:
-                local['relax'] = torch.cat([traj[-1]['relax']] + ([traj[-1]['scores_relaxed']] if a.score else []), 1)
-            wild_pts = pol.new_points(1) if (a.polar and a.interface) else None      # the wild type's point counts serve both tables too
-            if a.interface:                                     # the wild type's row rides along in every row: any rank can write the table
-                local['interface'] = torch.cat([traj[-1]['interface']] + ([traj[-1]['interface_relaxed']] if a.relax else []) +
-                                               [iface.wild(points=wild_pts).expand(n, -1)], 1)
-            if a.confidence:                                    # every sample's own wild row rides along: any rank can write the table
-                local['confidence'] = torch.cat([traj[-1]['confidence']] + ([traj[-1]['confidence_relaxed']] if a.relax else []) +
-                                                [traj[-1]['confidence_wild']], 1)
-                if a.confidence_planes:
-                    local['confidence_contacts'] = traj[-1]['confidence_planes'][0]
-            if a.accuracy:                                      # the wild type's row rides along in every row: any rank can write the table
-                local['accuracy'] = torch.cat([traj[-1]['accuracy']] + ([traj[-1]['accuracy_relaxed']] if a.relax else []) +
-                                              [acc.wild().expand(n, -1)], 1)
-                if a.accuracy_rows:
-                    local['accuracy_rows'] = traj[-1]['accuracy_rows']
-            if a.polar:                                         # the wild type's row rides along in every row: any rank can write the table
-                local['polar'] = torch.cat([traj[-1]['polar']] + ([traj[-1]['polar_relaxed']] if a.relax else []) +
-                                           [pol.wild(points=wild_pts).expand(n, -1)], 1)
-                if a.polar_rows:
-                    local['polar_rows'] = traj[-1]['polar_rows']
-            if a.ensemble:                                      # N, CA, C, O of the antibody rows: what the comparison reads
-                local['backbone'] = traj[-1]['atom14_results'][:, :, :4].float().contiguous()
+            local = analyses.collect(active, a, traj, scorers)
         else:                                                   # more ranks than samples: join the gather with zero-row blocks
-            local = {'seq': torch.zeros(0, Lab, dtype=torch.int64, device=dev), 'pLDDT': torch.zeros(0, Lab, device=dev)}
-            if a.score:
-                local['scores'] = torch.zeros(0, NS, dtype=torch.float64, device=dev)
-                if n_rec:
-                    local['traj_scores'] = torch.zeros(0, n_rec, 1 + NS, dtype=torch.float64, device=dev)
-            if a.relax:
-                local['relax'] = torch.zeros(0, NR, dtype=torch.float64, device=dev)
-            if a.interface:
-                local['interface'] = torch.zeros(0, NI, dtype=torch.float64, device=dev)
-            if a.confidence:
-                local['confidence'] = torch.zeros(0, NCF, dtype=torch.float64, device=dev)
-                if a.confidence_planes:
-                    local['confidence_contacts'] = torch.zeros(0, L, L, dtype=torch.float32, device=dev)
-            if a.accuracy:
-                local['accuracy'] = torch.zeros(0, NA, dtype=torch.float64, device=dev)
-                if a.accuracy_rows:
-                    local['accuracy_rows'] = torch.zeros(0, L, 4, dtype=torch.float64, device=dev)
-            if a.polar:
-                local['polar'] = torch.zeros(0, NP, dtype=torch.float64, device=dev)
-                if a.polar_rows:
-                    local['polar_rows'] = torch.zeros(0, L, 4, dtype=torch.int32, device=dev)
-            if a.ensemble:
-                local['backbone'] = torch.zeros(0, Lab, 4, 3, dtype=torch.float32, device=dev)
+            local = analyses.zero_rows(active, a, L, Lab, dev)
         if plan is not None:
-            row = torch.zeros(n, WIDTH, dtype=torch.float64)
-            row[:, 0], row[:, 1], row[:, 3] = ji, torch.tensor(ids, dtype=torch.float64), Lab
-            row[:, 2] = local['pLDDT'].float().mean(1).double().cpu()       # (the float32 mean of the sample-sharded path: same TSV digits)
-            row[:, 4:4 + Lab] = local['seq'].double().cpu()
-            if a.score:
-                row[:, 4 + maxLab:4 + maxLab + NS] = local['scores'].cpu()
-                if n_rec:
-                    row[:, 4 + maxLab + NS:4 + maxLab + NS + n_rec * (1 + NS)] = local['traj_scores'].reshape(n, -1).cpu()
-            if a.ensemble:                                      # f32 values are exact in float64
-                row[:, E0:E0 + 12 * Lab] = local['backbone'].reshape(n, -1).double().cpu()
-            if a.confidence:
-                row[:, E0 + NE:E0 + NE + NCF] = local['confidence'].cpu()
-            if a.accuracy:
-                row[:, E0 + NE + NCF:E0 + NE + NCF + NA] = local['accuracy'].cpu()
-            if a.polar:
-                row[:, E0 + NE + NCF + NA:E0 + NE + NCF + NA + NP] = local['polar'].cpu()
-            if a.relax:
-                row[:, row.shape[1] - NI - NR:row.shape[1] - NI] = local['relax'].cpu()
-            if a.interface:
-                row[:, row.shape[1] - NI:] = local['interface'].cpu()
-            set_rows.append(row)
+            set_rows.append(layout.pack(ji, ids, local))
             continue
         if a.debug_one_gpu and world > 1:                       # gloo moves host tensors
             local = {k: v.cpu() for k, v in local.items()}
         res = sampler.gather_results(local, N, rank, world, group, force=a.force_collective)
-        if rank == 0:
-            sc = res['scores'].tolist() if a.score else None
-            files.append(_write_designs(out_dir, cname, [(i, float(res['pLDDT'][i].float().mean()), res['seq'][i].tolist()) + ((sc[i],) if a.score else ())
-                                                         for i in range(N)]))
-            if n_rec:
-                files.append(_write_trajectory_scores(out_dir, cname, res['traj_scores'].cpu()))
-            if a.relax:
-                files.append(_write_relax(out_dir, cname, list(enumerate(res['relax'].tolist())), a.score))
-            if a.interface:
-                it = res['interface'].tolist()
-                files.append(_write_interface(out_dir, cname, it[0][NI - len(INTERFACE_COLUMNS):], list(enumerate(it)), a.relax))
-            if a.confidence:
-                files.append(_write_confidence(out_dir, cname, list(enumerate(res['confidence'].tolist())), a.relax))
-                if a.confidence_planes:
-                    import numpy as np
-                    files.append(os.path.join(out_dir, f'{cname}_confidence_contacts.npy'))
-                    np.save(files[-1], res['confidence_contacts'].double().mean(0).float().cpu().numpy())
-            if a.accuracy:
-                at = res['accuracy'].tolist()
-                files.append(_write_accuracy(out_dir, cname, at[0][NA - len(ACCURACY_COLUMNS):], list(enumerate(at)), a.relax))
-                if a.accuracy_rows:
-                    import numpy as np
-                    files.append(os.path.join(out_dir, f'{cname}_accuracy_rows.npy'))
-                    np.save(files[-1], res['accuracy_rows'].cpu().numpy())
-            if a.polar:
-                pt = res['polar'].tolist()
-                files.append(_write_polar(out_dir, cname, pt[0][NP - len(POLAR_COLUMNS):], list(enumerate(pt)), a.relax))
-                if a.polar_rows:
-                    import numpy as np
-                    files.append(os.path.join(out_dir, f'{cname}_polar_rows.npy'))
-                    np.save(files[-1], res['polar_rows'].cpu().numpy().astype(np.int16))
-            if a.ensemble:
-                files += analyze_ensemble(ji, out_dir, cname, list(range(N)), res['seq'], res['backbone'])
+        if rank == 0:                                           # (the float32 mean of every sample alone: what a set-level row carries)
+            res['mean_pLDDT'] = [float(res['pLDDT'][i].float().mean()) for i in range(N)]
+            files += analyses.write_job(active, a, out_dir, cname, list(range(N)), res, lambda an: kept_scorer(an, ji))
     if plan is not None:
         # ---- the one collective of the set: every rank's rows of the designs table (counts known from the common plan)
-        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, WIDTH, dtype=torch.float64)
+        table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, layout.WIDTH, dtype=torch.float64)
         if not (a.debug_one_gpu and world > 1):
             table = table.to(dev)
         counts = [sum(len(ids_) for _, ids_ in p) for p in plan]
@@ -738,33 +407,8 @@ def main(argv=None):
         if rank == 0:
             for ji in range(len(jobs)):
                 rows = full[full[:, 0] == ji]
-                rows = rows[torch.argsort(rows[:, 1])]
                 assert rows.shape[0] == N, (jobs[ji][1], rows.shape)
-                files.append(_write_designs(jobs[ji][2], load_job(ji)['cname'],
-                                            [(int(r[1]), float(r[2]), r[4:4 + int(r[3])].long().tolist()) +
-                                             ((r[4 + maxLab:4 + maxLab + NS].tolist(),) if a.score else ()) for r in rows]))
-                if n_rec:
-                    files.append(_write_trajectory_scores(jobs[ji][2], load_job(ji)['cname'],
-                                                          rows[:, 4 + maxLab + NS:4 + maxLab + NS + n_rec * (1 + NS)].reshape(N, n_rec, 1 + NS)))
-                if a.relax:
-                    files.append(_write_relax(jobs[ji][2], load_job(ji)['cname'], [(int(r[1]), r[r.shape[0] - NI - NR:r.shape[0] - NI].tolist()) for r in rows], a.score))
-                if a.interface:
-                    files.append(_write_interface(jobs[ji][2], load_job(ji)['cname'], rows[0, rows.shape[1] - len(INTERFACE_COLUMNS):].tolist(),
-                                                  [(int(r[1]), r[r.shape[0] - NI:].tolist()) for r in rows], a.relax))
-                if a.confidence:
-                    files.append(_write_confidence(jobs[ji][2], load_job(ji)['cname'], [(int(r[1]), r[E0 + NE:E0 + NE + NCF].tolist()) for r in rows], a.relax))
-                if a.accuracy:
-                    A0 = E0 + NE + NCF
-                    files.append(_write_accuracy(jobs[ji][2], load_job(ji)['cname'], rows[0, A0 + NA - len(ACCURACY_COLUMNS):A0 + NA].tolist(),
-                                                 [(int(r[1]), r[A0:A0 + NA].tolist()) for r in rows], a.relax))
-                if a.polar:
-                    P0 = E0 + NE + NCF + NA
-                    files.append(_write_polar(jobs[ji][2], load_job(ji)['cname'], rows[0, P0 + NP - len(POLAR_COLUMNS):P0 + NP].tolist(),
-                                              [(int(r[1]), r[P0:P0 + NP].tolist()) for r in rows], a.relax))
-                if a.ensemble:
-                    lab = int(rows[0, 3])
-                    files += analyze_ensemble(ji, jobs[ji][2], load_job(ji)['cname'], [int(r[1]) for r in rows], rows[:, 4:4 + lab].long(),
-                                              rows[:, E0:E0 + 12 * lab].float().reshape(N, lab, 4, 3))
+                files += analyses.write_job(active, a, jobs[ji][2], load_job(ji)['cname'], *layout.unpack(rows), lambda an: kept_scorer(an, ji))
     if world > 1 or a.force_collective:
         import torch.distributed as dist
         dist.barrier()

@@ -93,6 +93,8 @@ class PolarScorer:
     interface: an existing InterfaceScorer of the same complex - `score(..., points=)` then takes the counts of ITS call for the same
     structures, so that the surface kernel runs once per structure set."""
 
+    want_rows = False                   # set on an instance: sampler.sample_fn also records 'polar_bonds' and 'polar_rows'
+
     def __init__(self, batch, region=None, hb_min=2.0, hb_max=3.5, hb_angle=90.0, salt=4.0, n_points=128, probe=1.4, interface=None):
         from .interface import InterfaceScorer
         if not (0 <= hb_min <= hb_max and 90.0 <= hb_angle < 180.0 and salt >= 0):

@@ -121,40 +121,8 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 traj.append({kk: (v.clone() if torch.is_tensor(v) else v) for kk, v in rec.items()})
                 if scorer is not None:
                     traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
-                if relaxer is not None and k == len(steps) - 1:
-                    traj[-1]['atom14_relaxed'], traj[-1]['relax'] = relaxer.relax(traj[-1]['atom14_results'], traj[-1]['seq'])
-                    if scorer is not None:
-                        traj[-1]['scores_relaxed'] = scorer.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'])
-                pts = pts_relaxed = None                        # point counts of the interface call, when the polar scorer shares it
-                if interface is not None and k == len(steps) - 1:
-                    if polar is not None and polar.interface is interface:
-                        pts = polar.new_points(B)
-                        pts_relaxed = polar.new_points(B) if relaxer is not None else None
-                    traj[-1]['interface'] = interface.score(traj[-1]['atom14_results'], traj[-1]['seq'], points=pts)
-                    if relaxer is not None:
-                        traj[-1]['interface_relaxed'] = interface.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'], points=pts_relaxed)
-                if polar is not None and k == len(steps) - 1:
-                    rows = bool(getattr(polar, 'want_rows', False))
-                    if rows:
-                        traj[-1]['polar_bonds'] = torch.empty(B, polar.L, 14, 2, dtype=torch.int32, device=device)
-                        traj[-1]['polar_rows'] = torch.empty(B, polar.L, 4, dtype=torch.int32, device=device)
-                    traj[-1]['polar'] = polar.score(traj[-1]['atom14_results'], traj[-1]['seq'], points=pts,
-                                                    bonds=traj[-1].get('polar_bonds'), rows=traj[-1].get('polar_rows'))
-                    if relaxer is not None:
-                        traj[-1]['polar_relaxed'] = polar.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'], points=pts_relaxed)
-                if confidence is not None and k == len(steps) - 1:
-                    pair = out['representations']['pair']       # of the call just made: nothing between it and here runs the network
-                    got = confidence.score(pair, traj[-1]['atom14_results'], traj[-1]['seq'], planes=bool(getattr(confidence, 'want_planes', False)))
-                    traj[-1]['confidence'], traj[-1]['confidence_rows'] = got[0], got[1]
-                    if len(got) > 2:
-                        traj[-1]['confidence_planes'] = got[2]
-                    traj[-1]['confidence_wild'] = confidence.wild(pair)[0]
-                    if relaxer is not None:
-                        traj[-1]['confidence_relaxed'] = confidence.score(pair, traj[-1]['atom14_relaxed'], traj[-1]['seq'])[0]
-                if accuracy is not None and k == len(steps) - 1:
-                    traj[-1]['accuracy'], traj[-1]['accuracy_rows'] = accuracy.score(traj[-1]['atom14_results'], traj[-1]['seq'], plddt=pl_res, rows=True)[:2]
-                    if relaxer is not None:
-                        traj[-1]['accuracy_relaxed'] = accuracy.score(traj[-1]['atom14_relaxed'], traj[-1]['seq'], plddt=pl_res)
+                if k == len(steps) - 1:
+                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar)
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)
@@ -174,6 +142,44 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
         # (different batch mates in a flagged call, a different flag history per rank) is explained by these two entries
         traj[-1]['range_sticky_ops'] = list(getattr(model, 'range_sticky_ops', []))
     return traj
+
+
+def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar):
+    """What the analyses of sample_fn add to the LAST record, from the model's output `out` of the call that made it and its per-residue
+    pLDDT, each on the design and, with a relaxer, on the relaxed structure.  Launches only, no host synchronisation."""
+    x, seq, B = rec['atom14_results'], rec['seq'], rec['seq'].shape[0]
+    if relaxer is not None:
+        rec['atom14_relaxed'], rec['relax'] = relaxer.relax(x, seq)
+        if scorer is not None:
+            rec['scores_relaxed'] = scorer.score(rec['atom14_relaxed'], seq)
+    pts = pts_relaxed = None                                    # point counts of the interface call, when the polar scorer shares it
+    if interface is not None:
+        if polar is not None and polar.interface is interface:
+            pts = polar.new_points(B)
+            pts_relaxed = polar.new_points(B) if relaxer is not None else None
+        rec['interface'] = interface.score(x, seq, points=pts)
+        if relaxer is not None:
+            rec['interface_relaxed'] = interface.score(rec['atom14_relaxed'], seq, points=pts_relaxed)
+    if polar is not None:
+        if polar.want_rows:
+            rec['polar_bonds'] = torch.empty(B, polar.L, 14, 2, dtype=torch.int32, device=x.device)
+            rec['polar_rows'] = torch.empty(B, polar.L, 4, dtype=torch.int32, device=x.device)
+        rec['polar'] = polar.score(x, seq, points=pts, bonds=rec.get('polar_bonds'), rows=rec.get('polar_rows'))
+        if relaxer is not None:
+            rec['polar_relaxed'] = polar.score(rec['atom14_relaxed'], seq, points=pts_relaxed)
+    if confidence is not None:
+        pair = out['representations']['pair']                   # of the call just made: nothing between it and here runs the network
+        got = confidence.score(pair, x, seq, planes=bool(confidence.want_planes))
+        rec['confidence'], rec['confidence_rows'] = got[0], got[1]
+        if len(got) > 2:
+            rec['confidence_planes'] = got[2]
+        rec['confidence_wild'] = confidence.wild(pair)[0]
+        if relaxer is not None:
+            rec['confidence_relaxed'] = confidence.score(pair, rec['atom14_relaxed'], seq)[0]
+    if accuracy is not None:
+        rec['accuracy'], rec['accuracy_rows'] = accuracy.score(x, seq, plddt=pl_res, rows=True)[:2]
+        if relaxer is not None:
+            rec['accuracy_relaxed'] = accuracy.score(rec['atom14_relaxed'], seq, plddt=pl_res)
 
 
 def check_finite(*tensors, what='the end of the trajectory'):
