@@ -2,7 +2,6 @@
 counts and the residue-contact bits against the float64 host twin - equal, not close (tests/test_accuracy_host.py shows that no decision
 of these structures is borderline) -, the input conventions shared with abx_design_scores, batch independence at the headline size, and
 the path through the sampler and the design driver."""
-import copy
 import os
 
 import numpy as np
@@ -10,51 +9,28 @@ import pytest
 import torch
 
 import accuracy_cases as AC
+from analysis_gpu_cases import (ALONE, CODES, DEV, IDX13, assert_row as assert_columns, driver_pair, l352_designs, runs_of,
+                                sample_tiny, sampler_pair, structure_inputs, table_lines, tiny_batch, typed_or_gt, ops, gpu_model)  # noqa: F401  (ops, gpu_model: set up once per importing module)
 import relax_cases as RC
-from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
 GDT = [9, 10]
 COUNT = [12, 13, 15, 16, 17, 19, 20]
 FLOAT = [0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 14, 18]
-
-
-@pytest.fixture(scope='module')
-def ops():
-    from abx_amd import ops as _ops, _lib
-    lib = _lib.load()
-    assert lib.abx_init(0) == 0, lib.abx_last_error_string()
-    return _ops
-
-
-@pytest.fixture(scope='module')
-def gpu_model(params, cfg, tmp_path_factory):
-    from abx_amd.model.abx import ScoreNetwork
-    from abx_amd.diffuser.full_diffuser import FullDiffuser
-    dc = copy.deepcopy(cfg.diffuser)
-    dc.so3.cache_dir = str(tmp_path_factory.mktemp('igso3_cache'))
-    D = FullDiffuser(dc).to(DEV)
-    m = ScoreNetwork(cfg.model, D)
-    m.load_state_dict(params, strict=True)
-    return m.to(DEV).eval(), D
 
 
 def gpu_scores(ops, c, xs, aas=None, Lp=None, mask='gt', extras=True, **kw):
     """abx_accuracy_scores on structures xs (B,L,14,3) of complex c (rows >= Lp come from the crystal structure, which xs holds there).
     -> (table, rows, counts, contacts) on the host."""
     B, L, Lab = xs.shape[0], c['aa'].shape[0], c['Lab']
-    Lp = L if Lp is None else Lp
-    d = lambda t: t.to(DEV)
-    m = d(c['mask'][None].repeat(B, 1, 1)) if isinstance(mask, str) else (None if mask is None else d(mask))
-    aas = c['aa'][None].repeat(B, 1) if aas is None else aas
-    kw.setdefault('region', d(c['mov']))
+    x, sq, cplx, m, region = structure_inputs(c, xs, Lp, mask)
+    sq = sq if aas is None else aas[:, :Lab].to(DEV)
+    kw.setdefault('region', region)
     rows = torch.full((B, L, 4), -7.0, dtype=torch.float64, device=DEV) if extras else None
     counts = torch.full((B, L, 3, 5), -7, dtype=torch.int32, device=DEV) if extras else None
     contacts = torch.full((B, Lab, L - Lab), 77, dtype=torch.uint8, device=DEV) if extras else None
-    table = ops.accuracy_scores(d(xs[:, :Lp].float()), d(aas[:, :Lab]), d(c['x'].float()), d(c['aa']), d(c['mask']), Lab=Lab, mask=m,
-                                rows=rows, counts=counts, contacts=contacts, **kw)
+    table = ops.accuracy_scores(x, sq, *cplx, Lab=Lab, mask=m, rows=rows, counts=counts, contacts=contacts, **kw)
     cpu = lambda t: None if t is None else t.cpu()
     return table.cpu(), cpu(rows), cpu(counts), cpu(contacts)
 
@@ -62,9 +38,8 @@ def gpu_scores(ops, c, xs, aas=None, Lp=None, mask='gt', extras=True, **kw):
 def assert_row(got, want, what):
     """count and GDT columns equal; the other columns to 1e-9 relative (the order of the sums and the last bit of the square root are
     the only freedom); nan where the twin says nan."""
+    assert_columns(got, want, COUNT + GDT, [], 0.0, what)
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got[COUNT].tolist() == want[COUNT].tolist(), (what, got[COUNT], want[COUNT])
-    assert got[GDT].tolist() == want[GDT].tolist(), (what, got[GDT], want[GDT])
     assert np.array_equal(np.isnan(got), np.isnan(want)), (what, got, want)
     ok = ~np.isnan(want[FLOAT])
     err = np.abs(got[FLOAT][ok] - want[FLOAT][ok]) / np.maximum(np.abs(want[FLOAT][ok]), 1e-300)
@@ -175,14 +150,9 @@ def test_conventions_shared_with_design_scores(ops):
 def test_a_structure_does_not_depend_on_its_batch():
     """L = 352 synthetic workload, B = 100 perturbed copies: rows 0, 57 and 99 are bit-identical alone, in a chunk of 13 and in the
     batch of 100; a second call repeats the first bit for bit; structure 57 against the host twin."""
-    from abx_amd import accuracy, synthetic
-    cx = synthetic.make_complex(seed=2, **synthetic.WORKLOADS['L352'])
-    B, L, Lab = 100, cx['seq'].shape[0], cx['anchor_flag'].shape[0]
-    assert (L, Lab) == (352, 228)
-    g = torch.Generator().manual_seed(23)
-    xh = (cx['atom14_gt_positions'][None, :Lab] + 0.3 * torch.randn(B, Lab, 1, 3, generator=g) + 0.05 * torch.randn(B, Lab, 14, 3, generator=g)).float()
-    x = xh.to(DEV)
-    sq = cx['seq'][None, :Lab].repeat(B, 1).to(DEV)
+    from abx_amd import accuracy
+    cx, xh, x, sq, g = l352_designs()
+    (B, Lab), L = sq.shape, cx['seq'].shape[0]
     pl = (40.0 + 55.0 * torch.rand(B, L, generator=g)).float()
     sc = accuracy.AccuracyScorer({k: v.to(DEV) for k, v in cx.items()}, region=cx['cdr_def'] == 5)
     full, rows, counts, contacts = sc.score(x, sq, plddt=pl.to(DEV), rows=True, counts=True, contacts=True)
@@ -194,19 +164,15 @@ def test_a_structure_does_not_depend_on_its_batch():
     print('L352 B=100: lddt_all', h[:, 0].min().item(), h[:, 0].max().item(), 'lddt_region', h[:, 2].min().item(), h[:, 2].max().item(),
           'tm', h[:, 8].min().item(), 'native', h[0, 12].item(), 'kept', h[:, 13].min().item(), h[:, 13].max().item(), 'scored atoms', h[0, 20].item())
     assert len({float(v) for v in h[:, 0]}) > 50 and bool((h[:, 20] == h[0, 20]).all()) and bool((h[:, 12] == h[0, 12]).all())
-    idx13 = [1, 57, 2, 3, 99, 4, 5, 0, 6, 7, 8, 9, 10]
-    chunk = sc.score(x[idx13], sq[idx13], plddt=pl[idx13].to(DEV))
-    for j, b in enumerate(idx13):
+    chunk = sc.score(x[IDX13], sq[IDX13], plddt=pl[IDX13].to(DEV))
+    for j, b in enumerate(IDX13):
         assert torch.equal(bits(chunk[j]), bits(full[b])), b
-    for b in (0, 57, 99):
+    for b in ALONE:
         alone = sc.score(x[b:b + 1], sq[b:b + 1], plddt=pl[b:b + 1].to(DEV))
         assert torch.equal(bits(alone[0]), bits(full[b])), b
     xs = torch.cat([xh[57], cx['atom14_gt_positions'][Lab:].float()])
-    keep = cx['mask'].bool()
-    from abx_amd import residue_constants as rc
-    typed_or_gt = torch.cat([torch.as_tensor(rc.restype_atom14_mask)[cx['seq'][:Lab]].bool(), cx['atom14_gt_exists'][Lab:].bool()])
-    hh = accuracy.accuracy_host(xs, typed_or_gt, cx['seq'], cx['atom14_gt_positions'], cx['atom14_gt_exists'], cx['seq'], Lab, region=cx['cdr_def'] == 5,
-                                res_mask=keep, plddt=pl[57])
+    hh = accuracy.accuracy_host(xs, typed_or_gt(cx, Lab, typed=True), cx['seq'], cx['atom14_gt_positions'], cx['atom14_gt_exists'], cx['seq'], Lab,
+                                region=cx['cdr_def'] == 5, res_mask=cx['mask'].bool(), plddt=pl[57])
     assert hh['n_borderline'] == 0 and hh['n_borderline_gdt'] == 0
     assert_structure((h, rows.cpu(), counts.cpu(), contacts.cpu()), 57, hh, 'L352 structure 57')
 
@@ -215,33 +181,16 @@ def test_sampler_scores_the_last_record(gpu_model, cfg, monkeypatch):
     """sample_fn(accuracy=) on the tiny workload: 'accuracy' and 'accuracy_rows' sit on the last record only and equal a direct .score()
     of that record with the per-residue pLDDT of that call; with a relaxer also 'accuracy_relaxed'; with accuracy=None the records have
     exactly today's keys and equal tensors."""
-    from abx_amd import accuracy, features, relax, sampler, synthetic
-    model, D = gpu_model
-    B = 3
-    cx = synthetic.make_complex(seed=3, **synthetic.WORKLOADS['tiny'])
-    raw = {k: v.to(DEV) for k, v in synthetic.replicate(cx, B).items()}
-    torch.manual_seed(11)
-    b = features.build_features(raw, D)
-    b['_shared_context'] = True
-    sid = torch.arange(B, device=DEV) + 5
-    model.max_chunk = None
+    from abx_amd import accuracy, relax
+    b, sid = tiny_batch(gpu_model)
+    B = sid.shape[0]
     sc, relaxer = accuracy.AccuracyScorer(b), relax.ViolationRelaxer(b)
     dm = ((1 - b['fixed_mask'][0]) * b['atom14_gt_exists'][0, :, 0]) != 0
     assert torch.equal(sc.region.bool(), dm) and int(dm.sum()) > 0
-    today = {'seq', 'atom14_results', 'pLDDT', 'time', 'rigids_t', 'seq_t'}
     seen = []
     real = sc.score
     monkeypatch.setattr(sc, 'score', lambda *a, **kw: (seen.append(kw['plddt'].clone()) if kw.get('plddt') is not None else None, real(*a, **kw))[1])
-    D.seed = 21
-    plain = sampler.sample_fn(b, cfg, D, model, mode='trajectory', num_t=5, sample_ids=sid)
-    D.seed = 21
-    scored = sampler.sample_fn(b, cfg, D, model, mode='trajectory', num_t=5, sample_ids=sid, accuracy=sc, relaxer=relaxer)
-    assert len(plain) == len(scored) == 5
-    for k, (p, q) in enumerate(zip(plain, scored)):
-        assert set(p) - {'range_fallbacks', 'range_sticky_ops'} == today, (k, sorted(p))
-        for key in ('rigids_t', 'seq', 'atom14_results', 'pLDDT', 'seq_t'):
-            assert torch.equal(p[key], q[key]), (k, key)
-        assert all((key in q) == (k == 4) for key in ('accuracy', 'accuracy_rows', 'accuracy_relaxed')), k
+    _, scored = sampler_pair(gpu_model, cfg, b, sid, ('accuracy', 'accuracy_rows', 'accuracy_relaxed'), accuracy=sc, relaxer=relaxer)
     last = scored[-1]
     NA, L = len(accuracy.ACCURACY_COLUMNS), b['seq'].shape[1]
     assert last['accuracy'].shape == last['accuracy_relaxed'].shape == (B, NA) and last['accuracy'].dtype == torch.float64
@@ -253,8 +202,7 @@ def test_sampler_scores_the_last_record(gpu_model, cfg, monkeypatch):
     direct = real(last['atom14_results'], last['seq'], plddt=seen[0], rows=True)
     assert torch.equal(bits(direct[0]), bits(last['accuracy'])) and torch.equal(bits(direct[1]), bits(last['accuracy_rows']))
     assert torch.equal(bits(real(last['atom14_relaxed'], last['seq'], plddt=seen[0])), bits(last['accuracy_relaxed']))
-    D.seed = 21
-    design = sampler.sample_fn(b, cfg, D, model, mode='design', num_t=5, sample_ids=sid, accuracy=sc)
+    design = sample_tiny(gpu_model, cfg, b, sid, mode='design', accuracy=sc)
     assert len(design) == 1 and 'accuracy_relaxed' not in design[0]
     assert torch.equal(bits(design[0]['accuracy']), bits(last['accuracy']))
     row, wild = last['accuracy'].cpu(), sc.wild().cpu()
@@ -270,39 +218,16 @@ def test_design_driver_writes_the_accuracy_table(tmp_path, monkeypatch, collecti
     sample whose fields are the sampler's records at print precision; every other file of the run is byte-identical to the run without
     the flag.  collective = False: the shipped 6ct7 complex with --relax (the relaxed columns follow) and --accuracy_rows.
     collective = True: the 1-rank RCCL path on both shipped complexes, the table as further columns of the set-level gather."""
-    from abx_amd import accuracy, design, sampler
-    codes = ['6ct7_H_L_S', '6qd7_X_Z_F|E'] if collective else ['6ct7_H_L_S']
-    N = 2 if collective else 4
-    seen = []
-    real = sampler.sample_fn
-
-    def spy(batch, *a, **kw):
-        traj = real(batch, *a, **kw)
-        if 'accuracy' in kw:
-            seen.append((batch['seq'].shape[1], kw['accuracy'], traj))
-        return traj
-
-    monkeypatch.setattr(sampler, 'sample_fn', spy)
-    monkeypatch.setenv('MASTER_PORT', '29567')
-    common = ['--pdb_file'] + [os.path.join(GOLDEN, 'pdb', c + '.pdb') for c in codes] + ['--num_samples', str(N), '--num_t', '4']
-    common += ['--force_collective', '--min_block', '1'] if collective else ['--relax']
-    files = design.main(common + ['--accuracy', '--output_dir', str(tmp_path / 'acc')] + ([] if collective else ['--accuracy_rows']))
-    plain_files = design.main(common + ['--output_dir', str(tmp_path / 'plain')])
-    names = lambda fs: sorted(os.path.basename(f) for f in fs)
-    extra = [c + '_accuracy.tsv' for c in codes] + ([] if collective else [codes[0] + '_accuracy_rows.npy'])
-    assert names(files) == sorted(names(plain_files) + extra)
-    assert sorted(os.listdir(tmp_path / 'acc')) == names(files) and sorted(os.listdir(tmp_path / 'plain')) == names(plain_files)
-    for f in plain_files:
-        assert open(f, 'rb').read() == open(os.path.join(tmp_path / 'acc', os.path.basename(f)), 'rb').read(), f
+    from abx_amd import accuracy
+    out, codes, N, seen = driver_pair(tmp_path, monkeypatch, 'accuracy', ['--accuracy'] + ([] if collective else ['--accuracy_rows']), collective,
+                                        plain_extra=['--relax'], extra_files=[] if collective else [CODES[0] + '_accuracy_rows.npy'])
     NA, ND = len(accuracy.ACCURACY_COLUMNS), len(accuracy.DELTA_COLUMNS)
     for code in codes:
-        lines = [ln.split('\t') for ln in open(os.path.join(tmp_path / 'acc', code + '_accuracy.tsv')).read().splitlines()]
+        lines = table_lines(out, code, 'accuracy')
         head = ['sample'] + list(accuracy.ACCURACY_COLUMNS)
         assert lines[0] == head + ([] if collective else [c + '_relaxed' for c in accuracy.ACCURACY_COLUMNS] + ['delta_' + c for c in accuracy.DELTA_COLUMNS])
         assert len(lines) == 1 + 1 + N and all(len(r) == len(lines[0]) for r in lines)
-        Lc = 231 if code.startswith('6ct7') else 259
-        runs = [(sc, tr) for L, sc, tr in seen if L == Lc]
-        assert len(runs) == (2 if collective else 1)
+        runs = runs_of(seen, code, collective)
         wild = runs[0][0].wild().cpu()[0].tolist()
         assert lines[1][:1 + NA] == ['wild'] + accuracy.format_accuracy(wild)
         assert lines[1][1:7] == ['1.0000'] * 6 and lines[1][15] == '1.0000' and lines[1][12] == '0.000' and lines[1][7:9] == ['nan', 'nan']
@@ -315,5 +240,5 @@ def test_design_driver_writes_the_accuracy_table(tmp_path, monkeypatch, collecti
             assert lines[1][1 + NA:] == ['nan'] * (NA + ND)
             for i, r in enumerate(lines[2:]):
                 assert r[1 + NA:1 + 2 * NA] == accuracy.format_accuracy(relaxed[i]) and r[1 + 2 * NA:] == accuracy.format_delta(relaxed[i], rows[i]), (code, i)
-            per_res = np.load(os.path.join(tmp_path / 'acc', code + '_accuracy_rows.npy'))
-            assert per_res.shape == (N, Lc, 4) and np.array_equal(per_res, runs[0][1][-1]['accuracy_rows'].cpu().numpy(), equal_nan=True)
+            per_res = np.load(os.path.join(out, code + '_accuracy_rows.npy'))
+            assert per_res.shape == (N, 231, 4) and np.array_equal(per_res, runs[0][1][-1]['accuracy_rows'].cpu().numpy(), equal_nan=True)

@@ -1,7 +1,6 @@
 """GPU checks of the design scores (abx_design_scores, csrc/metrics.hip; abx_amd.metrics.DesignScorer): RMSD / AAR against the
 reference-pinned host calc_ab_metrics, the violation counts against the reference's masks (vio_pdb.npz), the clash counts against the
 fp64 host twin and the clash energy of abx_clash_grad, batch invariance, and the path through the sampler and the design driver."""
-import copy
 import os
 import warnings
 
@@ -9,33 +8,12 @@ import numpy as np
 import pytest
 import torch
 
+from analysis_gpu_cases import ALONE, CODES, DEV, SHARED, pdb_args, set_master_port, spy_on_sampler, ops, gpu_model  # noqa: F401  (ops, gpu_model: set up once per importing module)
 from conftest import GOLDEN, load_npz, tt
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
 VIO_KEYS = ('c_n_violation_mask', 'ca_c_n_violation_mask', 'c_n_ca_violation_mask')
-
-
-@pytest.fixture(scope='module')
-def ops():
-    from abx_amd import ops as _ops, _lib
-    lib = _lib.load()
-    assert lib.abx_init(0) == 0, lib.abx_last_error_string()
-    return _ops
-
-
-@pytest.fixture(scope='module')
-def gpu_model(params, cfg, tmp_path_factory):
-    """Score network with the seeded test weights and the product's own IGSO(3) tables (built by abx_igso3_tables into a fresh cache)."""
-    from abx_amd.model.abx import ScoreNetwork
-    from abx_amd.diffuser.full_diffuser import FullDiffuser
-    dc = copy.deepcopy(cfg.diffuser)
-    dc.so3.cache_dir = str(tmp_path_factory.mktemp('igso3_cache'))
-    D = FullDiffuser(dc).to(DEV)
-    m = ScoreNetwork(cfg.model, D)
-    m.load_state_dict(params, strict=True)
-    return m.to(DEV).eval(), D
 
 
 def col(name):
@@ -286,7 +264,7 @@ def test_rows_do_not_depend_on_the_batch(ops):
     assert np.isfinite(h[:, [col('heavy_cdr3_RMSD'), col('heavy_cdr3_Loop_RMSD'), col('heavy_cdr3_AAR')]]).all() and np.isfinite(h[:, 14:]).all()
     assert np.isnan(h[:, [col('heavy_cdr1_RMSD'), col('light_cdr3_AAR')]]).all()          # make_complex labels CDR-H3 only
     assert (h[:, 17] > 1000).all() and (h[:, 18] <= h[:, 17]).all() and h[:, 18].sum() > 0 and len({float(v) for v in h[:, 17]}) > 50
-    for b in (0, 57, 99):
+    for b in ALONE:
         alone = scorer.score(x[b:b + 1], sq[b:b + 1])
         assert torch.equal(alone[0].view(torch.int64), full[b].view(torch.int64)), b
     table = torch.full((3 * B, len(metrics.SCORE_COLUMNS)), -7.0, dtype=torch.float64, device=DEV)
@@ -365,7 +343,7 @@ def test_sampler_scores_every_record_and_leaves_the_trajectory_alone(gpu_model, 
     assert len(plain) == len(scored) == 4 and all('scores' not in r for r in plain)
     base = scored[0]['scores'].data_ptr()
     for k, (a, b) in enumerate(zip(plain, scored)):
-        for key in ('rigids_t', 'seq', 'atom14_results', 'pLDDT', 'seq_t'):
+        for key in SHARED:
             assert torch.equal(a[key], b[key]), (k, key)
         s = b['scores']
         assert s.shape == (3, len(metrics.SCORE_COLUMNS)) and s.dtype == torch.float64
@@ -383,19 +361,11 @@ def test_design_driver_score_columns(tmp_path, monkeypatch, collective):
     at print precision; without --score exactly three columns; in trajectory mode the second table.  collective = False: the shipped
     6ct7 complex in a plain process.  collective = True: the 1-rank RCCL path (--force_collective) on both shipped complexes, i.e. the
     scores as further columns of the set-level table and its one gather."""
-    from abx_amd import design, metrics, sampler
-    codes = ['6ct7_H_L_S', '6qd7_X_Z_F|E'] if collective else ['6ct7_H_L_S']
-    seen = []
-    real = sampler.sample_fn
-
-    def spy(batch, *a, **kw):
-        traj = real(batch, *a, **kw)
-        seen.append((metrics.DesignScorer(batch), traj))
-        return traj
-
-    monkeypatch.setattr(sampler, 'sample_fn', spy)
-    monkeypatch.setenv('MASTER_PORT', '29561')
-    common = ['--pdb_file'] + [os.path.join(GOLDEN, 'pdb', c + '.pdb') for c in codes] + ['--num_samples', '2', '--num_t', '4']
+    from abx_amd import design, metrics
+    codes = CODES if collective else CODES[:1]
+    seen = spy_on_sampler(monkeypatch, lambda batch, kw, traj: (metrics.DesignScorer(batch), traj))
+    set_master_port(monkeypatch)
+    common = pdb_args(codes) + ['--num_samples', '2', '--num_t', '4']
     if collective:
         common += ['--force_collective', '--min_block', '1']
     NC = len(metrics.SCORE_COLUMNS)

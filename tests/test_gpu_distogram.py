@@ -13,11 +13,11 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_npz, tt, feat_batch_from_golden, GOLDEN
+from analysis_gpu_cases import CODES, DEV, pdb_args, table_lines
+from conftest import load_npz, tt, feat_batch_from_golden
 from distogram_cases import (EPS, LIP_ENT, LIP_NLL, LIP_PC, SHAPES, VARIANTS, logit_bound, shape_case, twin_of, variant_case)
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
 MARGIN = 0.0            # 4 x the measured excess over the logit-implied bound (see the module docstring)
 
 
@@ -168,6 +168,7 @@ def test_a_design_does_not_depend_on_its_batch():
 
 @pytest.fixture(scope='module')
 def gpu_model(params, cfg, oracle_diffuser):
+    """Not analysis_gpu_cases.gpu_model: the IGSO(3) tables are the oracle's (set_tables), not the product's own from a fresh cache."""
     from abx_amd.model.abx import ScoreNetwork
     from abx_amd.diffuser.full_diffuser import FullDiffuser
     so3 = oracle_diffuser.so3
@@ -213,14 +214,13 @@ def test_design_driver_writes_the_confidence_table(tmp_path):
     values; without the flag no such file, and every other output file keeps its bytes."""
     from abx_amd import design
     from abx_amd.confidence import CONFIDENCE_COLUMNS, DELTA_COLUMNS
-    src = os.path.join(GOLDEN, 'pdb', '6ct7_H_L_S.pdb')
-    common = ['--pdb_file', src, '--num_samples', '3', '--mode', 'design', '--num_t', '2']
+    common = pdb_args(CODES[:1]) + ['--num_samples', '3', '--mode', 'design', '--num_t', '2']
     out_a, out_b = str(tmp_path / 'with'), str(tmp_path / 'without')
     files_a = design.main(common + ['--output_dir', out_a, '--confidence', '--confidence_planes'])
     files_b = design.main(common + ['--output_dir', out_b])
     tsv = os.path.join(out_a, '6ct7_H_L_S_confidence.tsv')
     assert tsv in files_a and not [f for f in os.listdir(out_b) if 'confidence' in f]
-    lines = [ln.split('\t') for ln in open(tsv).read().splitlines()]
+    lines = table_lines(out_a, CODES[0], 'confidence')
     assert lines[0] == ['sample'] + list(CONFIDENCE_COLUMNS) + ['delta_' + c for c in DELTA_COLUMNS]
     assert [ln[0] for ln in lines[1:]] == ['wild', '0', '1', '2'] and all(len(ln) == len(lines[0]) for ln in lines)
     vals = np.array([[float(v) for v in ln[1:]] for ln in lines[1:]])

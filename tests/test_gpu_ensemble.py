@@ -8,22 +8,13 @@ import numpy as np
 import pytest
 import torch
 
+from analysis_gpu_cases import CODES, DEV, assert_same_bytes, names, pdb_args, set_master_port, table_lines, ops  # noqa: F401  (ops: set up once per importing module)
 import ensemble_cases as EC
-from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
 COUNTS = [0, 1, 2, 8, 9]            # cluster, is_centre, n_neighbours, n_same_seq, first_same_seq
 STATS = [3, 4, 5, 6, 7]             # rmsd_fit_mean / min, rmsd_frame_mean / min, seq_diff_mean
-
-
-@pytest.fixture(scope='module')
-def ops():
-    from abx_amd import ops as _ops, _lib
-    lib = _lib.load()
-    assert lib.abx_init(0) == 0, lib.abx_last_error_string()
-    return _ops
 
 
 def analyze(x, seq, region, Lab=None, **kw):
@@ -218,20 +209,18 @@ def test_design_driver_writes_the_ensemble_table(tmp_path, monkeypatch):
     collective (the backbone as one more gathered field).  Both write the same table, which equals the twin on the backbone read back
     from the PDB files; a run without the flag writes the other files with the same bytes and no _ensemble file."""
     from abx_amd import design, synthetic
-    monkeypatch.setenv('MASTER_PORT', '29567')
+    set_master_port(monkeypatch)
     common = ['--workload', 'tiny', '--num_samples', '6', '--num_t', '2']
     ens = ['--ensemble', '--ensemble_matrix', '--ensemble_cutoff', '40.0']
     files = design.main(common + ens + ['--output_dir', str(tmp_path / 'ens')])
     files_c = design.main(common + ens + ['--force_collective', '--output_dir', str(tmp_path / 'coll')])
     plain = design.main(common + ['--output_dir', str(tmp_path / 'plain')])
-    names = lambda fs: sorted(os.path.basename(f) for f in fs)
     extra = ['tiny_H_L_A_ensemble.tsv', 'tiny_H_L_A_ensemble_rmsd.npy']
     assert names(files) == names(files_c) == sorted(names(plain) + extra)
     assert not [n for n in names(plain) if 'ensemble' in n] and sorted(os.listdir(tmp_path / 'plain')) == names(plain)
     assert sorted(os.listdir(tmp_path / 'ens')) == names(files)
-    for f in plain:
-        for d in ('ens', 'coll'):
-            assert open(f, 'rb').read() == open(os.path.join(tmp_path / d, os.path.basename(f)), 'rb').read(), (f, d)
+    for d in ('ens', 'coll'):
+        assert_same_bytes(plain, tmp_path / d)
     for n in extra:
         assert open(tmp_path / 'ens' / n, 'rb').read() == open(tmp_path / 'coll' / n, 'rb').read(), n
     first, last = synthetic.WORKLOADS['tiny']['cdr']
@@ -244,23 +233,21 @@ def test_design_driver_set_level_rows_carry_the_backbone(tmp_path, monkeypatch):
     """Two complexes through the set-level schedule (one gather of rows, the backbone as 12 maxLab further columns): the same ensemble
     files as the complex-by-complex run, and every other file unchanged by the flag."""
     from abx_amd import design
-    monkeypatch.setenv('MASTER_PORT', '29568')
-    codes = ['6ct7_H_L_S', '6qd7_X_Z_F|E']
-    common = ['--pdb_file'] + [os.path.join(GOLDEN, 'pdb', c + '.pdb') for c in codes] + ['--num_samples', '3', '--num_t', '2']
+    set_master_port(monkeypatch)
+    codes = CODES
+    common = pdb_args(codes) + ['--num_samples', '3', '--num_t', '2']
     ens = ['--ensemble', '--ensemble_matrix', '--ensemble_atoms', 'ca', '--ensemble_metric', 'frame', '--ensemble_cutoff', '3.0']
     set_level = ['--force_collective', '--min_block', '1']
     a = design.main(common + ens + ['--output_dir', str(tmp_path / 'one')])
     b = design.main(common + ens + set_level + ['--score', '--output_dir', str(tmp_path / 'set')])
     c = design.main(common + set_level + ['--score', '--output_dir', str(tmp_path / 'set_plain')])
-    names = lambda fs: sorted(os.path.basename(f) for f in fs)
     extra = sorted(f'{code}_ensemble{end}' for code in codes for end in ('.tsv', '_rmsd.npy'))
     assert names(a) == names(b) == sorted(names(c) + extra)
     for n in extra:
         assert open(tmp_path / 'one' / n, 'rb').read() == open(tmp_path / 'set' / n, 'rb').read(), n
-    for f in c:
-        assert open(f, 'rb').read() == open(os.path.join(tmp_path / 'set', os.path.basename(f)), 'rb').read(), f
+    assert_same_bytes(c, tmp_path / 'set')
     for code in codes:
-        lines = [ln.split('\t') for ln in open(tmp_path / 'set' / f'{code}_ensemble.tsv').read().splitlines()]
+        lines = table_lines(tmp_path / 'set', code, 'ensemble')
         assert len(lines) == 2 + 3 and lines[1][0] == 'all' and [r[0] for r in lines[2:]] == ['0', '1', '2']
         planes = np.load(tmp_path / 'set' / f'{code}_ensemble_rmsd.npy')
         assert planes.shape == (3, 3, 3) and (planes[0][~np.eye(3, dtype=bool)] > 0).all() and (planes[1] >= planes[0] - 1e-9).all()

@@ -1,40 +1,16 @@
 """GPU checks of the interface analysis (abx_interface_scores, csrc/interface.hip; abx_amd.interface.InterfaceScorer): the point counts
 of every atom14 slot against the float64 host twin - equal, not close -, the input conventions shared with abx_design_scores, batch
 independence at the headline size, and the path through the sampler and the design driver."""
-import copy
-import os
-
-import numpy as np
 import pytest
 import torch
 
+from analysis_gpu_cases import (ALONE, DEV, IDX13, assert_row as assert_columns, driver_pair, l352_designs, runs_of,
+                                sample_tiny, sampler_pair, structure_inputs, table_lines, tiny_batch, typed_or_gt, ops, gpu_model)  # noqa: F401  (ops, gpu_model: set up once per importing module)
 import relax_cases as RC
-from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
 AREA, COUNT = slice(0, 6), slice(6, 12)
-
-
-@pytest.fixture(scope='module')
-def ops():
-    from abx_amd import ops as _ops, _lib
-    lib = _lib.load()
-    assert lib.abx_init(0) == 0, lib.abx_last_error_string()
-    return _ops
-
-
-@pytest.fixture(scope='module')
-def gpu_model(params, cfg, tmp_path_factory):
-    from abx_amd.model.abx import ScoreNetwork
-    from abx_amd.diffuser.full_diffuser import FullDiffuser
-    dc = copy.deepcopy(cfg.diffuser)
-    dc.so3.cache_dir = str(tmp_path_factory.mktemp('igso3_cache'))
-    D = FullDiffuser(dc).to(DEV)
-    m = ScoreNetwork(cfg.model, D)
-    m.load_state_dict(params, strict=True)
-    return m.to(DEV).eval(), D
 
 
 _HOST = {}
@@ -54,23 +30,16 @@ def host(code, which, P, c=None):
 def gpu_scores(ops, c, xs, P, Lp=None, mask='gt', points=True, **kw):
     """abx_interface_scores on structures xs (B,L,14,3) of complex c (rows >= Lp come from the crystal structure, which xs holds there)."""
     from abx_amd import interface
-    B, L = xs.shape[0], c['aa'].shape[0]
-    Lp = L if Lp is None else Lp
-    d = lambda t: t.to(DEV)
-    pts = torch.full((B, L, 14, 2), -7, dtype=torch.int32, device=DEV) if points else None
-    m = d(c['mask'][None].repeat(B, 1, 1)) if isinstance(mask, str) else (None if mask is None else d(mask))
-    kw.setdefault('region', d(c['mov']))
-    row = ops.interface_scores(d(xs[:, :Lp].float()), d(c['aa'][None, :c['Lab']].repeat(B, 1)), d(c['x'].float()), d(c['aa']), d(c['mask']),
-                               interface.sphere_points(P, DEV), Lab=c['Lab'], mask=m, points=pts, **kw)
+    x, sq, cplx, m, region = structure_inputs(c, xs, Lp, mask)
+    pts = torch.full((xs.shape[0], c['aa'].shape[0], 14, 2), -7, dtype=torch.int32, device=DEV) if points else None
+    kw.setdefault('region', region)
+    row = ops.interface_scores(x, sq, *cplx, interface.sphere_points(P, DEV), Lab=c['Lab'], mask=m, points=pts, **kw)
     return row.cpu(), (pts.cpu() if points else None)
 
 
 def assert_row(got, want, what):
     """integer columns equal; areas to 1e-10 relative (the order of the sums is the only freedom)."""
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got[COUNT].tolist() == want[COUNT].tolist(), (what, got[COUNT], want[COUNT])
-    err = np.abs(got[AREA] - want[AREA]) / np.maximum(np.abs(want[AREA]), 1.0)
-    assert float(err.max()) <= 1e-10, (what, got[AREA], want[AREA])
+    assert_columns(got, want, COUNT, AREA, 1e-10, what)
 
 
 @pytest.mark.parametrize('P', [128, 100, 960])
@@ -141,14 +110,9 @@ def test_a_structure_does_not_depend_on_its_batch():
     """L = 352 synthetic workload, B = 100 perturbed copies: rows 0, 57 and 99 are bit-identical alone, in a chunk of 13 and in the
     batch of 100; a second call repeats the first bit for bit; one structure against the host twin (compact random coordinates: far
     more neighbours per atom than a protein has, so the neighbour list is worked off several times per atom)."""
-    from abx_amd import interface, synthetic
-    cx = synthetic.make_complex(seed=2, **synthetic.WORKLOADS['L352'])
-    B, L, Lab = 100, cx['seq'].shape[0], cx['anchor_flag'].shape[0]
-    assert (L, Lab) == (352, 228)
-    g = torch.Generator().manual_seed(23)
-    xh = (cx['atom14_gt_positions'][None, :Lab] + 0.3 * torch.randn(B, Lab, 1, 3, generator=g) + 0.05 * torch.randn(B, Lab, 14, 3, generator=g)).float()
-    x = xh.to(DEV)
-    sq = cx['seq'][None, :Lab].repeat(B, 1).to(DEV)
+    from abx_amd import interface
+    cx, xh, x, sq, _ = l352_designs()
+    (B, Lab), L = sq.shape, cx['seq'].shape[0]
     sc = interface.InterfaceScorer({k: v.to(DEV) for k, v in cx.items()}, region=cx['cdr_def'] == 5)
     pts = torch.zeros(B, L, 14, 2, dtype=torch.int32, device=DEV)
     full = sc.score(x, sq, points=pts)
@@ -158,16 +122,14 @@ def test_a_structure_does_not_depend_on_its_batch():
     h = full.cpu()
     print('L352 B=100: dsasa_int', h[:, 3].min().item(), h[:, 3].max().item(), 'contacts', h[:, 9].min().item(), h[:, 9].max().item(), 'atoms', h[0, 11].item())
     assert len({float(v) for v in h[:, 3]}) > 50 and bool((h[:, 11] == h[0, 11]).all())
-    idx13 = [1, 57, 2, 3, 99, 4, 5, 0, 6, 7, 8, 9, 10]
-    chunk = sc.score(x[idx13], sq[idx13])
-    for j, b in enumerate(idx13):
+    chunk = sc.score(x[IDX13], sq[IDX13])
+    for j, b in enumerate(IDX13):
         assert torch.equal(chunk[j].view(torch.int64), full[b].view(torch.int64)), b
-    for b in (0, 57, 99):
+    for b in ALONE:
         alone = sc.score(x[b:b + 1], sq[b:b + 1])
         assert torch.equal(alone[0].view(torch.int64), full[b].view(torch.int64)), b
     xs = torch.cat([xh[57], cx['atom14_gt_positions'][Lab:].float()])
-    typed_or_gt = torch.cat([torch.ones(Lab, 14, dtype=torch.bool), cx['atom14_gt_exists'][Lab:].bool()]) & cx['mask'].bool()[:, None]
-    hrow, hpts = interface.interface_host(xs, typed_or_gt, cx['seq'], Lab, region=cx['cdr_def'] == 5, n_points=128)
+    hrow, hpts = interface.interface_host(xs, typed_or_gt(cx, Lab), cx['seq'], Lab, region=cx['cdr_def'] == 5, n_points=128)
     assert torch.equal(pts[57].cpu(), torch.from_numpy(hpts))
     assert_row(h[57], hrow, 'L352 structure 57')
 
@@ -175,37 +137,19 @@ def test_a_structure_does_not_depend_on_its_batch():
 def test_sampler_scores_the_last_record(gpu_model, cfg):
     """sample_fn(interface=) on the tiny workload: 'interface' sits on the last record only and equals a direct .score() of that
     record; with a relaxer also 'interface_relaxed'; with interface=None the records have exactly today's keys."""
-    from abx_amd import features, interface, relax, sampler, synthetic
-    model, D = gpu_model
-    B = 3
-    cx = synthetic.make_complex(seed=3, **synthetic.WORKLOADS['tiny'])
-    raw = {k: v.to(DEV) for k, v in synthetic.replicate(cx, B).items()}
-    torch.manual_seed(11)
-    b = features.build_features(raw, D)
-    b['_shared_context'] = True
-    sid = torch.arange(B, device=DEV) + 5
-    model.max_chunk = None
+    from abx_amd import interface, relax
+    b, sid = tiny_batch(gpu_model)
+    B = sid.shape[0]
     sc, relaxer = interface.InterfaceScorer(b), relax.ViolationRelaxer(b)
     dm = ((1 - b['fixed_mask'][0]) * b['atom14_gt_exists'][0, :, 0]) != 0
     assert torch.equal(sc.region.bool(), dm) and int(dm.sum()) > 0
-    today = {'seq', 'atom14_results', 'pLDDT', 'time', 'rigids_t', 'seq_t'}
-    D.seed = 21
-    plain = sampler.sample_fn(b, cfg, D, model, mode='trajectory', num_t=5, sample_ids=sid)
-    D.seed = 21
-    scored = sampler.sample_fn(b, cfg, D, model, mode='trajectory', num_t=5, sample_ids=sid, interface=sc, relaxer=relaxer)
-    assert len(plain) == len(scored) == 5
-    for k, (p, q) in enumerate(zip(plain, scored)):
-        assert set(p) - {'range_fallbacks', 'range_sticky_ops'} == today, (k, sorted(p))
-        for key in ('rigids_t', 'seq', 'atom14_results', 'pLDDT', 'seq_t'):
-            assert torch.equal(p[key], q[key]), (k, key)
-        assert all((key in q) == (k == 4) for key in ('interface', 'interface_relaxed')), k
+    _, scored = sampler_pair(gpu_model, cfg, b, sid, ('interface', 'interface_relaxed'), interface=sc, relaxer=relaxer)
     last = scored[-1]
     NI = len(interface.INTERFACE_COLUMNS)
     assert last['interface'].shape == last['interface_relaxed'].shape == (B, NI) and last['interface'].dtype == torch.float64
     assert torch.equal(sc.score(last['atom14_results'], last['seq']).view(torch.int64), last['interface'].view(torch.int64))
     assert torch.equal(sc.score(last['atom14_relaxed'], last['seq']).view(torch.int64), last['interface_relaxed'].view(torch.int64))
-    D.seed = 21
-    design = sampler.sample_fn(b, cfg, D, model, mode='design', num_t=5, sample_ids=sid, interface=sc)
+    design = sample_tiny(gpu_model, cfg, b, sid, mode='design', interface=sc)
     assert len(design) == 1 and 'interface_relaxed' not in design[0]
     assert torch.equal(design[0]['interface'].view(torch.int64), last['interface'].view(torch.int64))
     row = last['interface'].cpu()
@@ -219,37 +163,15 @@ def test_design_driver_writes_the_interface_table(tmp_path, monkeypatch, collect
     sampler's records at print precision; every other file of the run is byte-identical to the run without the flag.  collective =
     False: the shipped 6ct7 complex with --relax --score (the relaxed columns follow).  collective = True: the 1-rank RCCL path on both
     shipped complexes, the table as further columns of the set-level gather."""
-    from abx_amd import design, interface, sampler
-    codes = ['6ct7_H_L_S', '6qd7_X_Z_F|E'] if collective else ['6ct7_H_L_S']
-    N = 2 if collective else 4
-    seen = []
-    real = sampler.sample_fn
-
-    def spy(batch, *a, **kw):
-        traj = real(batch, *a, **kw)
-        if 'interface' in kw:
-            seen.append((batch['seq'].shape[1], kw['interface'], traj))
-        return traj
-
-    monkeypatch.setattr(sampler, 'sample_fn', spy)
-    monkeypatch.setenv('MASTER_PORT', '29563')
-    common = ['--pdb_file'] + [os.path.join(GOLDEN, 'pdb', c + '.pdb') for c in codes] + ['--num_samples', str(N), '--num_t', '4']
-    common += ['--force_collective', '--min_block', '1'] if collective else ['--relax', '--score']
-    files = design.main(common + ['--interface', '--output_dir', str(tmp_path / 'iface')])
-    plain_files = design.main(common + ['--output_dir', str(tmp_path / 'plain')])
-    names = lambda fs: sorted(os.path.basename(f) for f in fs)
-    assert names(files) == sorted(names(plain_files) + [c + '_interface.tsv' for c in codes])
-    assert sorted(os.listdir(tmp_path / 'iface')) == names(files) and sorted(os.listdir(tmp_path / 'plain')) == names(plain_files)
-    for f in plain_files:
-        assert open(f, 'rb').read() == open(os.path.join(tmp_path / 'iface', os.path.basename(f)), 'rb').read(), f
+    from abx_amd import interface
+    out, codes, N, seen = driver_pair(tmp_path, monkeypatch, 'interface', ['--interface'], collective, plain_extra=['--relax', '--score'])
     NI = len(interface.INTERFACE_COLUMNS)
     for code in codes:
-        lines = [ln.split('\t') for ln in open(os.path.join(tmp_path / 'iface', code + '_interface.tsv')).read().splitlines()]
+        lines = table_lines(out, code, 'interface')
         head = ['sample'] + list(interface.INTERFACE_COLUMNS) + ['delta_' + c for c in interface.DELTA_COLUMNS]
         assert lines[0] == head + ([] if collective else [c + '_relaxed' for c in interface.INTERFACE_COLUMNS])
         assert len(lines) == 1 + 1 + N and all(len(r) == len(lines[0]) for r in lines)
-        runs = [(sc, tr) for L, sc, tr in seen if L == (231 if code.startswith('6ct7') else 259)]
-        assert len(runs) == (2 if collective else 1)
+        runs = runs_of(seen, code, collective)
         wild = runs[0][0].wild().cpu()[0].tolist()
         assert lines[1][:1 + NI] == ['wild'] + interface.format_interface(wild) and lines[1][1 + NI:1 + NI + 5] == ['+0.00', '+0.00', '+0.00', '+0', '+0']
         assert wild[9] == (119 if code.startswith('6ct7') else 1)            # the contacts of the crystal structure (any P)

@@ -1,42 +1,21 @@
 """GPU checks of the polar-contact analysis (abx_polar_scores, csrc/polar.hip; abx_amd.polar.PolarScorer): the bonds of every atom14
 slot and every count column against the float64 host twin - equal, not close -, the input conventions shared with
 abx_interface_scores, batch independence at the headline size, and the path through the sampler and the design driver."""
-import copy
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from analysis_gpu_cases import (ALONE, CODES, DEV, IDX13, assert_row as assert_columns, driver_pair, l352_designs, runs_of,
+                                sample_tiny, sampler_pair, structure_inputs, table_lines, tiny_batch, typed_or_gt, ops, gpu_model)  # noqa: F401  (ops, gpu_model: set up once per importing module)
 import relax_cases as RC
-from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
 COUNT = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13]
 AREA = [10, 11]
 P = 128
-
-
-@pytest.fixture(scope='module')
-def ops():
-    from abx_amd import ops as _ops, _lib
-    lib = _lib.load()
-    assert lib.abx_init(0) == 0, lib.abx_last_error_string()
-    return _ops
-
-
-@pytest.fixture(scope='module')
-def gpu_model(params, cfg, tmp_path_factory):
-    from abx_amd.model.abx import ScoreNetwork
-    from abx_amd.diffuser.full_diffuser import FullDiffuser
-    dc = copy.deepcopy(cfg.diffuser)
-    dc.so3.cache_dir = str(tmp_path_factory.mktemp('igso3_cache'))
-    D = FullDiffuser(dc).to(DEV)
-    m = ScoreNetwork(cfg.model, D)
-    m.load_state_dict(params, strict=True)
-    return m.to(DEV).eval(), D
 
 
 def gpu_scores(ops, c, xs, Lp=None, mask='gt', points=True, want=True, **kw):
@@ -44,28 +23,21 @@ def gpu_scores(ops, c, xs, Lp=None, mask='gt', points=True, want=True, **kw):
     the crystal structure, which xs holds there).  -> (rows, bonds, per-residue rows, points) on the host."""
     from abx_amd import interface, polar
     B, L = xs.shape[0], c['aa'].shape[0]
-    Lp = L if Lp is None else Lp
-    d = lambda t: t.to(DEV)
-    m = d(c['mask'][None].repeat(B, 1, 1)) if isinstance(mask, str) else (None if mask is None else d(mask))
-    x, sq = d(xs[:, :Lp].float()), d(c['aa'][None, :c['Lab']].repeat(B, 1))
-    cx = (d(c['x'].float()), d(c['aa']), d(c['mask']))
+    x, sq, cx, m, region = structure_inputs(c, xs, Lp, mask)
     pts = None
     if points:
         pts = torch.full((B, L, 14, 2), -7, dtype=torch.int32, device=DEV)
         ops.interface_scores(x, sq, *cx, interface.sphere_points(P, DEV), Lab=c['Lab'], mask=m, points=pts, res_mask=kw.get('res_mask'))
     bonds = torch.full((B, L, 14, 2), -7, dtype=torch.int32, device=DEV) if want else None
     rows = torch.full((B, L, 4), -7, dtype=torch.int32, device=DEV) if want else None
-    kw.setdefault('region', d(c['mov']))
+    kw.setdefault('region', region)
     row = ops.polar_scores(x, sq, *cx, polar.polar_table_on(DEV), Lab=c['Lab'], mask=m, points=pts, n_points=P, bonds=bonds, rows=rows, **kw)
     return row.cpu(), (bonds.cpu() if want else None), (rows.cpu() if want else None), (pts.cpu() if points else None)
 
 
 def assert_row(got, want, what):
     """count columns equal; areas to 1e-10 relative (the order of the sums is the only freedom)."""
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got[COUNT].tolist() == want[COUNT].tolist(), (what, got[COUNT], want[COUNT])
-    err = np.abs(got[AREA] - want[AREA]) / np.maximum(np.abs(want[AREA]), 1.0)
-    assert float(err.max()) <= 1e-10, (what, got[AREA], want[AREA])
+    assert_columns(got, want, COUNT, AREA, 1e-10, what)
 
 
 @pytest.mark.parametrize('code,sel', RC.MOVABLE_SETS)
@@ -155,14 +127,9 @@ def test_conventions_shared_with_the_interface_analysis(ops):
 def test_a_structure_does_not_depend_on_its_batch():
     """L = 352 synthetic workload, B = 100 perturbed copies: rows, bonds and per-residue tables are bit-identical alone, in a chunk of 13
     and in the batch of 100; a second call repeats the first bit for bit; one structure against the host twin."""
-    from abx_amd import polar, synthetic
-    cx = synthetic.make_complex(seed=2, **synthetic.WORKLOADS['L352'])
-    B, L, Lab = 100, cx['seq'].shape[0], cx['anchor_flag'].shape[0]
-    assert (L, Lab) == (352, 228)
-    g = torch.Generator().manual_seed(23)
-    xh = (cx['atom14_gt_positions'][None, :Lab] + 0.3 * torch.randn(B, Lab, 1, 3, generator=g) + 0.05 * torch.randn(B, Lab, 14, 3, generator=g)).float()
-    x = xh.to(DEV)
-    sq = cx['seq'][None, :Lab].repeat(B, 1).to(DEV)
+    from abx_amd import polar
+    cx, xh, x, sq, _ = l352_designs()
+    (B, Lab), L = sq.shape, cx['seq'].shape[0]
     sc = polar.PolarScorer({k: v.to(DEV) for k, v in cx.items()}, region=cx['cdr_def'] == 5)
     pts = sc.new_points(B)
     sc.interface.score(x, sq, points=pts)
@@ -176,18 +143,16 @@ def test_a_structure_does_not_depend_on_its_batch():
     print('L352 B=100: hbond_total', h[:, 12].min().item(), h[:, 12].max().item(), 'hbond_int', h[:, 0].min().item(), h[:, 0].max().item(),
           'polar', h[0, 13].item(), 'unsat', h[:, 8].min().item(), h[:, 8].max().item())
     assert bool((h[:, 13] == h[0, 13]).all()) and len({tuple(r) for r in h.tolist()}) > 50
-    idx13 = [1, 57, 2, 3, 99, 4, 5, 0, 6, 7, 8, 9, 10]
     b13, r13 = new(13)
-    chunk = sc.score(x[idx13], sq[idx13], points=pts[idx13].contiguous(), bonds=b13, rows=r13)
-    for j, b in enumerate(idx13):
+    chunk = sc.score(x[IDX13], sq[IDX13], points=pts[IDX13].contiguous(), bonds=b13, rows=r13)
+    for j, b in enumerate(IDX13):
         assert torch.equal(chunk[j].view(torch.int64), full[b].view(torch.int64)) and torch.equal(b13[j], bonds[b]) and torch.equal(r13[j], rows[b]), b
-    for b in (0, 57, 99):
+    for b in ALONE:
         b1, r1 = new(1)
         alone = sc.score(x[b:b + 1], sq[b:b + 1], points=pts[b:b + 1].contiguous(), bonds=b1, rows=r1)
         assert torch.equal(alone[0].view(torch.int64), full[b].view(torch.int64)) and torch.equal(b1[0], bonds[b]) and torch.equal(r1[0], rows[b]), b
     xs = torch.cat([xh[57], cx['atom14_gt_positions'][Lab:].float()])
-    typed_or_gt = torch.cat([torch.ones(Lab, 14, dtype=torch.bool), cx['atom14_gt_exists'][Lab:].bool()]) & cx['mask'].bool()[:, None]
-    hrow, hbonds, hd = polar.polar_host(xs, typed_or_gt, cx['seq'], Lab, region=cx['cdr_def'] == 5, points=pts[57].cpu(), details=True)
+    hrow, hbonds, hd = polar.polar_host(xs, typed_or_gt(cx, Lab), cx['seq'], Lab, region=cx['cdr_def'] == 5, points=pts[57].cpu(), details=True)
     assert torch.equal(bonds[57].cpu(), torch.from_numpy(hbonds)) and torch.equal(rows[57].cpu(), torch.from_numpy(hd['rows']))
     assert_row(h[57], hrow, 'L352 structure 57')
 
@@ -218,32 +183,15 @@ def test_sampler_scores_the_last_record(gpu_model, cfg):
     """sample_fn(polar=) on the tiny workload: 'polar' sits on the last record only and equals a direct .score() of that record; with a
     relaxer also 'polar_relaxed', with want_rows 'polar_bonds' / 'polar_rows'; sharing the interface scorer changes neither table;
     with polar=None the records have exactly today's keys."""
-    from abx_amd import features, interface, polar, relax, sampler, synthetic
-    model, D = gpu_model
-    B = 3
-    cx = synthetic.make_complex(seed=3, **synthetic.WORKLOADS['tiny'])
-    raw = {k: v.to(DEV) for k, v in synthetic.replicate(cx, B).items()}
-    torch.manual_seed(11)
-    b = features.build_features(raw, D)
-    b['_shared_context'] = True
-    sid = torch.arange(B, device=DEV) + 5
-    model.max_chunk = None
+    from abx_amd import interface, polar, relax
+    b, sid = tiny_batch(gpu_model)
+    B = sid.shape[0]
     it = interface.InterfaceScorer(b)
     sc, relaxer = polar.PolarScorer(b, interface=it), relax.ViolationRelaxer(b)
     sc.want_rows = True
     L = b['seq'].shape[1]
-    today = {'seq', 'atom14_results', 'pLDDT', 'time', 'rigids_t', 'seq_t'}
-    D.seed = 21
-    plain = sampler.sample_fn(b, cfg, D, model, mode='trajectory', num_t=5, sample_ids=sid)
-    D.seed = 21
-    scored = sampler.sample_fn(b, cfg, D, model, mode='trajectory', num_t=5, sample_ids=sid, polar=sc, interface=it, relaxer=relaxer)
-    assert len(plain) == len(scored) == 5
     new = ('polar', 'polar_relaxed', 'polar_bonds', 'polar_rows', 'interface', 'interface_relaxed')
-    for k, (p, q) in enumerate(zip(plain, scored)):
-        assert set(p) - {'range_fallbacks', 'range_sticky_ops'} == today, (k, sorted(p))
-        for key in ('rigids_t', 'seq', 'atom14_results', 'pLDDT', 'seq_t'):
-            assert torch.equal(p[key], q[key]), (k, key)
-        assert all((key in q) == (k == 4) for key in new), k
+    _, scored = sampler_pair(gpu_model, cfg, b, sid, new, polar=sc, interface=it, relaxer=relaxer)
     last = scored[-1]
     NP = len(polar.POLAR_COLUMNS)
     assert last['polar'].shape == last['polar_relaxed'].shape == (B, NP) and last['polar'].dtype == torch.float64
@@ -255,9 +203,7 @@ def test_sampler_scores_the_last_record(gpu_model, cfg):
     assert torch.equal(sc.score(last['atom14_relaxed'], last['seq']).view(torch.int64), last['polar_relaxed'].view(torch.int64))
     assert torch.equal(it.score(last['atom14_results'], last['seq']).view(torch.int64), last['interface'].view(torch.int64))
     assert torch.equal(it.score(last['atom14_relaxed'], last['seq']).view(torch.int64), last['interface_relaxed'].view(torch.int64))
-    D.seed = 21
-    sc2 = polar.PolarScorer(b)
-    design = sampler.sample_fn(b, cfg, D, model, mode='design', num_t=5, sample_ids=sid, polar=sc2)
+    design = sample_tiny(gpu_model, cfg, b, sid, mode='design', polar=polar.PolarScorer(b))
     assert len(design) == 1 and not {'polar_relaxed', 'polar_bonds', 'polar_rows', 'interface'} & set(design[0])
     assert torch.equal(design[0]['polar'].view(torch.int64), last['polar'].view(torch.int64))
     row = last['polar'].cpu()
@@ -272,38 +218,16 @@ def test_design_driver_writes_the_polar_table(tmp_path, monkeypatch, collective)
     records at print precision; every other file of the run is byte-identical to the run without the flag.  collective = False: the
     shipped 6ct7 complex with --relax --interface --polar_rows (the relaxed columns follow, the per-residue table is written).
     collective = True: the 1-rank RCCL path on both shipped complexes, the table as further columns of the set-level gather."""
-    from abx_amd import design, polar, sampler
-    codes = ['6ct7_H_L_S', '6qd7_X_Z_F|E'] if collective else ['6ct7_H_L_S']
-    N = 2 if collective else 4
-    seen = []
-    real = sampler.sample_fn
-
-    def spy(batch, *a, **kw):
-        traj = real(batch, *a, **kw)
-        if 'polar' in kw:
-            seen.append((batch['seq'].shape[1], kw['polar'], traj))
-        return traj
-
-    monkeypatch.setattr(sampler, 'sample_fn', spy)
-    monkeypatch.setenv('MASTER_PORT', '29567')
-    common = ['--pdb_file'] + [os.path.join(GOLDEN, 'pdb', c + '.pdb') for c in codes] + ['--num_samples', str(N), '--num_t', '4']
-    common += ['--force_collective', '--min_block', '1'] if collective else ['--relax', '--interface']
-    files = design.main(common + ['--polar', '--output_dir', str(tmp_path / 'polar')] + ([] if collective else ['--polar_rows']))
-    plain_files = design.main(common + ['--output_dir', str(tmp_path / 'plain')])
-    names = lambda fs: sorted(os.path.basename(f) for f in fs)
-    extra = [c + '_polar.tsv' for c in codes] + ([] if collective else [codes[0] + '_polar_rows.npy'])
-    assert names(files) == sorted(names(plain_files) + extra)
-    assert sorted(os.listdir(tmp_path / 'polar')) == names(files) and sorted(os.listdir(tmp_path / 'plain')) == names(plain_files)
-    for f in plain_files:
-        assert open(f, 'rb').read() == open(os.path.join(tmp_path / 'polar', os.path.basename(f)), 'rb').read(), f
+    from abx_amd import polar
+    out, codes, N, seen = driver_pair(tmp_path, monkeypatch, 'polar', ['--polar'] + ([] if collective else ['--polar_rows']), collective,
+                                        plain_extra=['--relax', '--interface'], extra_files=[] if collective else [CODES[0] + '_polar_rows.npy'])
     NP, ND = len(polar.POLAR_COLUMNS), len(polar.DELTA_COLUMNS)
     for code in codes:
-        lines = [ln.split('\t') for ln in open(os.path.join(tmp_path / 'polar', code + '_polar.tsv')).read().splitlines()]
+        lines = table_lines(out, code, 'polar')
         head = ['sample'] + list(polar.POLAR_COLUMNS) + ['delta_' + c for c in polar.DELTA_COLUMNS]
         assert lines[0] == head + ([] if collective else [c + '_relaxed' for c in polar.POLAR_COLUMNS])
         assert len(lines) == 1 + 1 + N and all(len(r) == len(lines[0]) for r in lines)
-        runs = [(sc, tr) for L, sc, tr in seen if L == (231 if code.startswith('6ct7') else 259)]
-        assert len(runs) == (2 if collective else 1)
+        runs = runs_of(seen, code, collective)
         wild = runs[0][0].wild().cpu()[0].tolist()
         assert lines[1][:1 + NP] == ['wild'] + polar.format_polar(wild) and lines[1][1 + NP:1 + NP + ND] == polar.format_delta(wild, wild)
         assert lines[1][1 + NP:1 + NP + ND] == ['+0'] * 6 + ['+0.00'] * 2
@@ -319,7 +243,7 @@ def test_design_driver_writes_the_polar_table(tmp_path, monkeypatch, collective)
             assert lines[1][1 + NP + ND:] == ['nan'] * NP
             for i, r in enumerate(lines[2:]):
                 assert r[1 + NP + ND:] == polar.format_polar(relaxed[i]), (code, i)
-            per_res = np.load(os.path.join(tmp_path / 'polar', code + '_polar_rows.npy'))
+            per_res = np.load(os.path.join(out, code + '_polar_rows.npy'))
             want = runs[0][1][-1]['polar_rows'].cpu().numpy()
             assert per_res.dtype == np.int16 and per_res.shape == (N, 231, 4) and np.array_equal(per_res, want)
             bonds = runs[0][1][-1]['polar_bonds'].cpu().numpy()

@@ -2,40 +2,17 @@
 gradient against float64 autograd of the host twin, the constant offset against abx_clash_grad, convergence on the perturbed loops of
 the two shipped complexes, the invariants of the rigid-body + chi parametrisation, batch invariance at the headline size, and the
 path through the sampler and the design driver."""
-import copy
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from analysis_gpu_cases import (ALONE, CODES, DEV, SHARED, assert_same_bytes, l352_designs, names, pdb_args,
+                                sample_tiny, spy_on_sampler, structure_inputs, table_lines, tiny_batch, ops, gpu_model)  # noqa: F401  (ops, gpu_model: set up once per importing module)
 import relax_cases as RC
-from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
-
-DEV = 'cuda:0'
-
-
-@pytest.fixture(scope='module')
-def ops():
-    from abx_amd import ops as _ops, _lib
-    lib = _lib.load()
-    assert lib.abx_init(0) == 0, lib.abx_last_error_string()
-    return _ops
-
-
-@pytest.fixture(scope='module')
-def gpu_model(params, cfg, tmp_path_factory):
-    """Score network with the seeded test weights and the product's own IGSO(3) tables (built by abx_igso3_tables into a fresh cache)."""
-    from abx_amd.model.abx import ScoreNetwork
-    from abx_amd.diffuser.full_diffuser import FullDiffuser
-    dc = copy.deepcopy(cfg.diffuser)
-    dc.so3.cache_dir = str(tmp_path_factory.mktemp('igso3_cache'))
-    D = FullDiffuser(dc).to(DEV)
-    m = ScoreNetwork(cfg.model, D)
-    m.load_state_dict(params, strict=True)
-    return m.to(DEV).eval(), D
 
 
 def rel_err(a, b):
@@ -53,19 +30,14 @@ def check(a, b, tol, name):
 
 def gpu_relax(ops, c, xs, Lp=None, **kw):
     """abx_relax on structures xs (B,L,14,3) of complex c (rows >= Lp come from the crystal structure, which is what xs holds there)."""
-    B, L = xs.shape[0], c['aa'].shape[0]
-    Lp = L if Lp is None else Lp
-    d = lambda t: t.to(DEV)
-    return ops.relax(d(xs[:, :Lp].float()), d(c['aa'][None, :c['Lab']].repeat(B, 1)), d(c['x'].float()), d(c['aa']), d(c['mask']), d(c['chain'].int()),
-                     d(c['mov']), Lab=c['Lab'], residx=d(c['residx'].int()), mask=d(c['mask'][None].repeat(B, 1, 1)), **kw)
+    x, sq, cplx, m, mov = structure_inputs(c, xs, Lp)
+    return ops.relax(x, sq, *cplx, c['chain'].int().to(DEV), mov, Lab=c['Lab'], residx=c['residx'].int().to(DEV), mask=m, **kw)
 
 
 def gpu_counts(ops, c, xs):
     """The five count columns of abx_design_scores for structures xs (B,L,14,3)."""
-    B = xs.shape[0]
-    d = lambda t: t.to(DEV)
-    s = ops.design_scores(d(xs.float()), d(c['aa'][None, :c['Lab']].repeat(B, 1)), d(c['x'].float()), d(c['aa']), d(c['mask']), d(c['cdr'].int()),
-                          d(c['chain'].int()), Lab=c['Lab'], residx=d(c['residx'].int()), mask=d(c['mask'][None].repeat(B, 1, 1)))
+    x, sq, cplx, m, _ = structure_inputs(c, xs)
+    s = ops.design_scores(x, sq, *cplx, c['cdr'].int().to(DEV), c['chain'].int().to(DEV), Lab=c['Lab'], residx=c['residx'].int().to(DEV), mask=m)
     return s[:, 14:].cpu().long().tolist()
 
 
@@ -248,13 +220,9 @@ def test_invariants_on_a_mixed_batch(ops, k):
 def test_a_structure_does_not_depend_on_its_batch(ops):
     """L = 352 synthetic workload (the LDS-resident atom table at the headline size): a structure relaxed alone, in a batch of 7 and in
     a batch of 100 gives torch.equal coordinates and report rows."""
-    from abx_amd import relax, synthetic
-    cx = synthetic.make_complex(seed=2, **synthetic.WORKLOADS['L352'])
-    B, L, Lab = 100, cx['seq'].shape[0], cx['anchor_flag'].shape[0]
-    assert (L, Lab) == (352, 228)
-    g = torch.Generator().manual_seed(23)
-    x = (cx['atom14_gt_positions'][None, :Lab] + 0.3 * torch.randn(B, Lab, 1, 3, generator=g) + 0.05 * torch.randn(B, Lab, 14, 3, generator=g)).to(DEV)
-    sq = cx['seq'][None, :Lab].repeat(B, 1).to(DEV)
+    from abx_amd import relax
+    cx, _, x, sq, _ = l352_designs()
+    B, Lab = sq.shape
     mov = cx['cdr_def'] == 5
     r = relax.ViolationRelaxer({k: v.to(DEV) for k, v in cx.items()}, movable=mov, flank=2)
     assert r.M == int(mov.sum()) + 4 == 17
@@ -266,7 +234,7 @@ def test_a_structure_does_not_depend_on_its_batch(ops):
     assert len({float(v) for v in h[:, 0]}) > 50
     idx7 = [1, 57, 2, 3, 99, 4, 5]
     seven, rep7 = r.relax(x[idx7], sq[idx7])
-    for b in (0, 57, 99):
+    for b in ALONE:
         alone, rep1 = r.relax(x[b:b + 1], sq[b:b + 1])
         assert torch.equal(alone[0], full[b]) and torch.equal(rep1[0].view(torch.int64), rep[b].view(torch.int64)), b
     for j, b in enumerate(idx7):
@@ -282,28 +250,20 @@ def mov_rows(r):
 def test_sampler_relaxes_the_last_record_only(gpu_model, cfg, use_graph):
     """sample_fn(relaxer=, scorer=) on the tiny workload: the three new keys sit on the last record only; atom14_results, seq and scores
     equal a run without the relaxer (same seed).  Plumbing only: with the seeded test weights a design is a heap of clashing atoms."""
-    from abx_amd import features, metrics, relax, sampler, synthetic
+    from abx_amd import metrics, relax, sampler
     model, D = gpu_model
-    B = 3
-    cx = synthetic.make_complex(seed=3, **synthetic.WORKLOADS['tiny'])
-    raw = {k: v.to(DEV) for k, v in synthetic.replicate(cx, B).items()}
-    torch.manual_seed(11)
-    b = features.build_features(raw, D)
-    b['_shared_context'] = True
-    sid = torch.arange(B, device=DEV) + 5
-    model.max_chunk = None
+    b, sid = tiny_batch(gpu_model)
+    B = sid.shape[0]
     scorer, relaxer = metrics.DesignScorer(b), relax.ViolationRelaxer(b)
     Lab = relaxer.Lab
     dm = ((1 - b['fixed_mask'][0]) * b['atom14_gt_exists'][0, :, 0]) != 0
     assert relaxer.M == int(dm.sum()) > 0 and torch.equal(relaxer.movable.bool(), dm)
-    D.seed = 21
-    plain = sampler.sample_fn(b, cfg, D, model, mode='trajectory', num_t=5, sample_ids=sid, scorer=scorer, use_graph=use_graph)
-    D.seed = 21
-    relaxed = sampler.sample_fn(b, cfg, D, model, mode='trajectory', num_t=5, sample_ids=sid, scorer=scorer, relaxer=relaxer, use_graph=use_graph)
+    plain = sample_tiny(gpu_model, cfg, b, sid, scorer=scorer, use_graph=use_graph)
+    relaxed = sample_tiny(gpu_model, cfg, b, sid, scorer=scorer, relaxer=relaxer, use_graph=use_graph)
     assert len(plain) == len(relaxed) == 5
     new = ('atom14_relaxed', 'relax', 'scores_relaxed')
     for k, (p, q) in enumerate(zip(plain, relaxed)):
-        for key in ('rigids_t', 'seq', 'atom14_results', 'pLDDT', 'seq_t'):
+        for key in SHARED:
             assert torch.equal(p[key], q[key]), (k, key)
         assert torch.equal(p['scores'].view(torch.int64), q['scores'].view(torch.int64)), k
         assert all(key not in p for key in new) and all((key in q) == (k == 4) for key in new), k
@@ -325,28 +285,18 @@ def test_sampler_relaxes_the_last_record_only(gpu_model, cfg, use_graph):
 def test_design_driver_writes_relaxed_files(tmp_path, monkeypatch):
     """`abx_amd.design --relax --score` on the shipped 6ct7 complex: four *_relaxed.pdb that read back to the relaxed coordinates within
     1e-3 A, <complex>_relax.tsv with one row per sample; without --relax the output directory is what it is today."""
-    from abx_amd import design, metrics, relax, sampler
+    from abx_amd import design, metrics, relax
     from abx_amd.io import pdb_reader
-    seen = []
-    real = sampler.sample_fn
-
-    def spy(batch, *a, **kw):
-        traj = real(batch, *a, **kw)
-        seen.append(traj)
-        return traj
-
-    monkeypatch.setattr(sampler, 'sample_fn', spy)
-    common = ['--pdb_file', os.path.join(GOLDEN, 'pdb', '6ct7_H_L_S.pdb'), '--num_samples', '4', '--num_t', '4']
+    seen = spy_on_sampler(monkeypatch, lambda batch, kw, traj: traj)
+    common = pdb_args(CODES[:1]) + ['--num_samples', '4', '--num_t', '4']
     files = design.main(common + ['--relax', '--score', '--output_dir', str(tmp_path / 'relaxed')])
     last = seen[-1][-1]
     plain_files = design.main(common + ['--score', '--output_dir', str(tmp_path / 'plain')])
-    names = lambda fs: sorted(os.path.basename(f) for f in fs)
     rel = [f for f in files if f.endswith('_relaxed.pdb')]
     assert names(rel) == [f'6ct7-{i:03d}_H_L_S_relaxed.pdb' for i in range(4)]
     assert names(set(files) - set(rel)) == sorted(names(plain_files) + ['6ct7_H_L_S_relax.tsv'])
     assert sorted(os.listdir(tmp_path / 'relaxed')) == names(files) and sorted(os.listdir(tmp_path / 'plain')) == names(plain_files)
-    for f in plain_files:                                                   # the design files themselves do not change
-        assert open(f, 'rb').read() == open(os.path.join(tmp_path / 'relaxed', os.path.basename(f)), 'rb').read(), f
+    assert_same_bytes(plain_files, tmp_path / 'relaxed')                  # the design files themselves do not change
     x = last['atom14_relaxed'].cpu()
     assert not torch.equal(x, last['atom14_results'].cpu())
     for i in range(4):
@@ -358,13 +308,13 @@ def test_design_driver_writes_relaxed_files(tmp_path, monkeypatch):
         err = float(((coords - x[i]).abs() * m[..., None]).max())
         print('sample', i, 'read-back error', err)
         assert err <= 1e-3
-    lines = [ln.split('\t') for ln in open(os.path.join(tmp_path / 'relaxed', '6ct7_H_L_S_relax.tsv')).read().splitlines()]
+    lines = table_lines(tmp_path / 'relaxed', CODES[0], 'relax')
     assert lines[0] == ['sample'] + list(relax.RELAX_COLUMNS) + list(metrics.SCORE_COLUMNS) and len(lines) == 5
     rep, sc = last['relax'].cpu().tolist(), last['scores_relaxed'].cpu().tolist()
     for i, r in enumerate(lines[1:]):
         assert r[0] == str(i) and r[1:] == relax.format_report(rep[i]) + metrics.format_scores(sc[i]), (i, r)
     # without --score: the report columns alone
     files = design.main(common + ['--relax', '--relax_iters', '20', '--relax_flank', '1', '--relax_restraint', '0.05', '--output_dir', str(tmp_path / 'r2')])
-    lines = [ln.split('\t') for ln in open(os.path.join(tmp_path / 'r2', '6ct7_H_L_S_relax.tsv')).read().splitlines()]
+    lines = table_lines(tmp_path / 'r2', CODES[0], 'relax')
     assert lines[0] == ['sample'] + list(relax.RELAX_COLUMNS) and len(lines) == 5 and all(int(r[8]) <= 20 for r in lines[1:])
     assert len([f for f in files if f.endswith('_relaxed.pdb')]) == 4
