@@ -185,6 +185,21 @@ class AbxGuidanceArgs(C.Structure):
     ]
 
 
+class AbxContactArgs(C.Structure):
+    _fields_ = [
+        ('atom14', c_f), ('atom_mask', c_f),
+        ('moved', c_f),
+        ('target', c_f),
+        ('frame_trans', c_f),
+        ('hotspots', c_f), ('hotspots_host', c_f),
+        ('restr_idx', c_f), ('restr_idx_host', c_f),
+        ('restr_par', c_f), ('restr_par_host', c_f),
+        ('w_contact', F), ('d0', F), ('d1', F), ('w_hot', F), ('d_hot', F), ('beta', F),
+        ('energy', c_f), ('grad_atom', c_f), ('grad_trans', c_f), ('grad_rot', c_f),
+        ('B', I), ('L', I), ('H', I), ('R', I),
+    ]
+
+
 # The leading fields of the five per-design analyses' descriptors (include/abx_hip.h): the structure that csrc/structure_dev.h reads
 _STRUCTURE_FIELDS = [
     ('pred_atom14', c_f), ('pred_sb', LL), ('Lpred', I),
@@ -371,6 +386,8 @@ _PROTOS = {
     'abx_reverse_step': (I, [C.POINTER(AbxReverseArgs), _S]),
     'abx_clash_grad_workspace_bytes': (LL, [I, I]),
     'abx_clash_grad': (I, [C.POINTER(AbxGuidanceArgs), c_f, _S]),
+    'abx_contact_grad_workspace_bytes': (LL, [I, I, I]),
+    'abx_contact_grad': (I, [C.POINTER(AbxContactArgs), c_f, _S]),
     'abx_design_scores_workspace_bytes': (LL, [I, I]),
     'abx_design_scores': (I, [C.POINTER(AbxDesignScoreArgs), c_f, _S]),
     'abx_relax_workspace_bytes': (LL, [I, I, I]),

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "abx_hip.h"
 #include "peptide_dev.h"
+#include "frame_dev.h"
 
 namespace {
 
@@ -155,26 +156,8 @@ __global__ __launch_bounds__(256) void bond_frames_kernel(const AbxGuidanceArgs 
     }
     __threadfence_block();
     __syncthreads();
-    // frame pull-back: translation gradient = sum of the residue's atom gradients, rotation gradient = torque about the frame origin
-    for (int i = tid; i < L; i += 256) {
-        const long long r = ab + i;
-        const float* t = a.frame_trans + r * 3;
-        float ft[3] = {0.f, 0.f, 0.f}, tq[3] = {0.f, 0.f, 0.f};
-        for (int s = 0; s < 14; ++s) {
-            if (!a.atom_mask[r * 14 + s]) continue;
-            const float* x = a.atom14 + (r * 14 + s) * 3;
-            const float* g = a.grad_atom + (r * 14 + s) * 3;
-            const float rx = x[0] - t[0], ry = x[1] - t[1], rz = x[2] - t[2];
-            ft[0] += g[0]; ft[1] += g[1]; ft[2] += g[2];
-            tq[0] += ry * g[2] - rz * g[1];
-            tq[1] += rz * g[0] - rx * g[2];
-            tq[2] += rx * g[1] - ry * g[0];
-        }
-        for (int k = 0; k < 3; ++k) {
-            a.grad_trans[r * 3 + k] = ft[k];
-            a.grad_rot[r * 3 + k] = tq[k];
-        }
-    }
+    // frame pull-back (frame_dev.h): translation gradient = sum of the residue's atom gradients, rotation gradient = torque about the frame origin
+    frame_pullback(a.atom14, a.atom_mask, a.grad_atom, a.frame_trans, a.grad_trans, a.grad_rot, ab, L, tid, 256);
 }
 
 }  // namespace

@@ -5,6 +5,8 @@ and write the PDB files (per step in trajectory mode, asynchronously).
     python -m abx_amd.design --pdb_file 6ct7_H_L_S.pdb --num_samples 100 --mode design --output_dir out/      (raw PDB, 8f-1)
     python -m abx_amd.design --workload L256 --num_samples 4 --mode trajectory --num_t 10 --output_dir out/   (synthetic complex)
     python -m abx_amd.design --pdb_file 6ct7_H_L_S.pdb --mode optimize --optimize_steps 10 --guidance --num_samples 100     (config 4)
+    python -m abx_amd.design --pdb_file 6ct7_H_L_S.pdb --mode optimize --optimize_steps 10 --guidance --guidance_contact 1 \
+        --guidance_hotspots epitope --num_samples 100                           (+ interface guidance: contacts, hotspots, restraints)
     python -m abx_amd.design --pdb_file 6ct7_H_L_S.pdb --num_samples 100 --score --output_dir out/     (+ per-CDR RMSD / AAR, violation and clash counts)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m abx_amd.design \
         --pdb_list diffab_test.txt --pdb_dir pdbs/ --num_samples 100 --output_dir out/                        (a test set on 8 GPUs)
@@ -124,6 +126,16 @@ def build_parser():
     ap.add_argument('--guidance', action='store_true', help='structural-violation guidance (clash + C-N bond terms, abx_clash_grad) on')
     ap.add_argument('--guidance_scale', type=float, nargs=2, default=[1.0, 1.0], metavar=('TRANS', 'ROT'),
                     help='step scales of the guidance gradients on the translation / rotation scores')
+    ap.add_argument('--guidance_contact', type=float, default=0.0, metavar='W', help='interface guidance (abx_contact_grad): weight of the smooth '
+                    'count of heavy-atom contacts between the designed residues and the antigen (0: off)')
+    ap.add_argument('--guidance_contact_range', type=float, nargs=2, default=[4.0, 8.0], metavar=('D0', 'D1'),
+                    help='--guidance_contact: a contact counts fully within D0 and not at all beyond D1 (Angstrom)')
+    ap.add_argument('--guidance_hotspots', nargs='+', default=None, metavar='RES', help="interface guidance: antigen residues that a designed "
+                    "residue should come near, as <chain letter>:<residue index as featurised>, or 'epitope' = the antigen residues the "
+                    "input loop touches")
+    ap.add_argument('--guidance_hotspot_weight', type=float, default=1.0, help='--guidance_hotspots: weight of the hotspot term')
+    ap.add_argument('--guidance_restraints', default=None, metavar='FILE', help='interface guidance: pair-distance restraints, one '
+                    '`res atom res atom lo hi [weight]` per line')
     ap.add_argument('--debug_one_gpu', action='store_true', help='debugging on a 1-GPU box: every rank uses cuda:0 and the gloo backend')
     # the reference's inference.py arguments (inference.py:398-416)
     ap.add_argument('--name_idx', default=None, help='text file with one complex name per line (entries of --data_dir)')
@@ -246,6 +258,28 @@ def main(argv=None):
     if a.guidance:
         from .guidance import ViolationGuidance
         guide = ViolationGuidance(scale_trans=a.guidance_scale[0], scale_rot=a.guidance_scale[1])
+    interface_guided = a.guidance_contact != 0.0 or a.guidance_hotspots is not None or a.guidance_restraints is not None
+
+    def job_guide(batch, J, kind, path):
+        """The guidance of one featurised batch: the violation terms (one object for the run) and, with the --guidance_contact /
+        _hotspots / _restraints options, the interface terms of THIS complex (tables built here, before the sampling loop)."""
+        if not interface_guided:
+            return guide
+        from .guidance import InterfaceGuidance, Sum, parse_residues, parse_restraints
+        if kind in ('pdb', 'npz'):
+            from .data.antibody import parse_pdb_name
+            _, _, heavy, light, antigen = parse_pdb_name(path)
+            chains = [heavy, light] + list(antigen)
+        else:
+            chains = ['H', 'L', 'A']
+        hot = a.guidance_hotspots
+        if hot is not None:
+            hot = 'epitope' if list(hot) == ['epitope'] else parse_residues(hot, J['one'], chains)
+        restraints = parse_restraints(a.guidance_restraints, J['one'], chains) if a.guidance_restraints else None
+        ig = InterfaceGuidance(batch, w_contact=a.guidance_contact, d0=a.guidance_contact_range[0], d1=a.guidance_contact_range[1], hotspots=hot,
+                               w_hot=a.guidance_hotspot_weight, restraints=restraints, scale_trans=a.guidance_scale[0], scale_rot=a.guidance_scale[1])
+        return Sum(guide, ig)
+
     N = a.num_samples
     # jobs: (kind, reference to the complex, output directory, optimize step, inference.py layout?, directory of the ground-truth copy)
     jobs = []
@@ -366,10 +400,11 @@ def main(argv=None):
             scorers = {}                                        # by flag, in the order of the analyses: a later one may build on an earlier one
             for an in active:
                 scorers[an.flag] = an.build(batch, a, model, cfg, scorers) if an.kw else kept_scorer(an, ji, batch)
+            job_guidance = job_guide(batch, J, kind, path)
             torch.cuda.synchronize()
             t_feat = time.perf_counter()
             traj = sampler.sample_fn(batch, cfg, diffuser, model, mode=a.mode, num_t=a.num_t,
-                                     sample_ids=torch.tensor(ids, device=dev, dtype=torch.int64), on_record=writer.submit, guidance=guide,
+                                     sample_ids=torch.tensor(ids, device=dev, dtype=torch.int64), on_record=writer.submit, guidance=job_guidance,
                                      **{an.kw: scorers[an.flag] for an in active if an.kw})
             torch.cuda.synchronize()
             t_samp = time.perf_counter()

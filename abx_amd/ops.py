@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1045,6 +1045,57 @@ def clash_grad(atom14, atom_mask, aatype, chain_id, frame_trans, overlap_toleran
     a.energy, a.grad_atom, a.grad_trans, a.grad_rot = _p(energy), _p(g_atom), _p(g_t), _p(g_r)
     a.B, a.L = B, L
     check(lib.abx_clash_grad(C.byref(a), _p(ws), _stream()), 'abx_clash_grad')
+    return energy, g_atom, g_t, g_r
+
+
+class ContactTables:
+    """The hotspot rows and the restraint table of abx_contact_grad, built once: device copies for the kernels, host copies for the
+    argument checks (no host-to-device copy on the step path).  hotspots: H <= 64 row indices; restraints: None or (idx (R,4) of
+    row_i, slot_i, row_j, slot_j; par (R,3) of lo, hi, weight), R <= 256."""
+
+    def __init__(self, device, hotspots=None, restraints=None):
+        hot = torch.as_tensor([] if hotspots is None else hotspots, dtype=torch.int32).reshape(-1)
+        idx, par = (torch.zeros(0, 4), torch.zeros(0, 3)) if restraints is None else restraints
+        self.hot_host = hot.cpu().contiguous()
+        self.idx_host = torch.as_tensor(idx).to(torch.int32).reshape(-1, 4).cpu().contiguous()
+        self.par_host = torch.as_tensor(par).to(torch.float32).reshape(-1, 3).cpu().contiguous()
+        assert self.idx_host.shape[0] == self.par_host.shape[0], (self.idx_host.shape, self.par_host.shape)
+        self.H, self.R = int(self.hot_host.numel()), int(self.idx_host.shape[0])
+        self.hot = self.hot_host.to(device) if self.H else None
+        self.idx = self.idx_host.to(device) if self.R else None
+        self.par = self.par_host.to(device) if self.R else None
+
+
+def contact_grad(atom14, atom_mask, moved, target, frame_trans, tables=None, w_contact=0.0, d0=4.0, d1=8.0, w_hot=1.0, d_hot=8.0, beta=1.0):
+    """Interface guidance energies and gradients (abx_contact_grad).  atom14 (B,L,14,3) f32 and atom_mask (B,L,14): per row the predicted
+    atoms where moved (B,L) is set, the ground truth elsewhere; target (L): the partner rows; frame_trans (B,L,3); tables: a
+    ContactTables or None.  -> energy (B,3) [contact, hotspot, restraint], grad_atom (B,L,14,3), grad_trans, grad_rot (B,L,3)."""
+    lib = _lib.load()
+    B, L = moved.shape
+    dev = atom14.device
+    a = AbxContactArgs()
+    x = _f32(atom14).contiguous()
+    m = atom_mask.to(torch.uint8).contiguous()
+    mv = moved.to(torch.uint8).contiguous()
+    tg = target.to(torch.uint8).contiguous()
+    ft = _f32(frame_trans).contiguous()
+    assert tuple(x.shape) == (B, L, 14, 3) and tuple(m.shape) == (B, L, 14) and tuple(tg.shape) == (L,) and tuple(ft.shape) == (B, L, 3)
+    H, R = (tables.H, tables.R) if tables is not None else (0, 0)
+    energy = torch.empty(B, 3, device=dev)
+    g_atom = torch.empty(B, L, 14, 3, device=dev)
+    g_t = torch.empty(B, L, 3, device=dev)
+    g_r = torch.empty(B, L, 3, device=dev)
+    ws = torch.empty(max(int(lib.abx_contact_grad_workspace_bytes(B, L, H)) // 4, 1), device=dev)
+    a.atom14, a.atom_mask, a.moved, a.target, a.frame_trans = _p(x), _p(m), _p(mv), _p(tg), _p(ft)
+    if H:
+        a.hotspots, a.hotspots_host = _p(tables.hot), tables.hot_host.data_ptr()
+    if R:
+        a.restr_idx, a.restr_idx_host = _p(tables.idx), tables.idx_host.data_ptr()
+        a.restr_par, a.restr_par_host = _p(tables.par), tables.par_host.data_ptr()
+    a.w_contact, a.d0, a.d1, a.w_hot, a.d_hot, a.beta = float(w_contact), float(d0), float(d1), float(w_hot), float(d_hot), float(beta)
+    a.energy, a.grad_atom, a.grad_trans, a.grad_rot = _p(energy), _p(g_atom), _p(g_t), _p(g_r)
+    a.B, a.L, a.H, a.R = B, L, H, R
+    check(lib.abx_contact_grad(C.byref(a), _p(ws), _stream()), 'abx_contact_grad')
     return energy, g_atom, g_t, g_r
 
 

@@ -29,8 +29,8 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
     per-step PDB files asynchronously (device->host copy on a side stream, formatting and disk I/O on a worker thread).
-    guidance: None (the reference's un-guided sampler, bit-identical code path) or an abx_amd.guidance.ViolationGuidance whose
-    clash / bond gradients on the predicted structure are subtracted from the scores before the reverse step.
+    guidance: None (the reference's un-guided sampler, bit-identical code path) or a callable of abx_amd.guidance - ViolationGuidance,
+    InterfaceGuidance or a Sum of them - whose gradients on the predicted structure are subtracted from the scores before the reverse step.
     use_graph: record the step into two hipGraphs (abx_amd.graph.GraphedSteps) after one eager step and replay them; needs the
     device noise generator (noise_fn None) and gives the same results as the eager loop.
     scorer: None, or an abx_amd.metrics.DesignScorer of the complex: every record gets 'scores' (B, len(metrics.SCORE_COLUMNS)) float64,

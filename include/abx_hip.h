@@ -530,6 +530,43 @@ long long abx_clash_grad_workspace_bytes(int B, int L);
 int abx_clash_grad(const AbxGuidanceArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Interface guidance terms (north_star "the evolutionary/physical/geometric guidance-gradient terms" and "guidance pairwise-distance
+ * / clash terms": the geometric half, beside the physical half of abx_clash_grad).  An EXTENSION WITH NO REFERENCE SITE: the reference
+ * samples without guidance.  Reference constants used: the 4 A heavy-atom contact distance of the interface table
+ * (abx_interface_scores `cutoff`, n_contact_region), the 8 A pseudo-beta contact distance of upstream's MetricDictHead
+ * (abx_distogram_scores `contact_cutoff`) and the pseudo-beta rule (CB, slot 4, else CA, slot 1) of its distogram features.
+ * The caller hands ONE structure per sample: atom14 / atom_mask already hold, per row, the predicted atoms where moved[b, r] is set
+ * and the ground truth elsewhere.  d = sqrt(1e-10 + |x_a - x_b|^2) everywhere (as in abx_clash_grad).  Per sample:
+ *   energy[b][0] = -w_contact * sum s(d_ab),  a: existing atoms of moved rows, b: existing atoms of rows with target[r] set that are
+ *                  not moved;  s = 1 (d <= d0), (1 - u^2)^2 with u = (d - d0) / (d1 - d0) (d0 < d < d1), 0 (d >= d1)
+ *   energy[b][1] = w_hot * sum_h Hub(m_h - d_hot),  m_h = -(1 / beta) log sum_i exp(-beta d(pb_i, pb_h)) over the moved rows i with a
+ *                  pseudo-beta;  Hub(v) = 0 (v <= 0), v^2 / 2 (0 < v < 1), v - 1/2 (v >= 1).  A hotspot row that is moved in the sample or
+ *                  has no pseudo-beta, and a sample without a moved pseudo-beta, contribute exactly 0.
+ *   energy[b][2] = sum_r weight_r * (Hub(d_r - hi_r) + Hub(lo_r - d_r)) over the restraints whose two atoms both exist
+ *   grad_atom = dE/dx (B,L,14,3), exactly 0 on every row that is not moved;  grad_trans = sum_a g_a;
+ *   grad_rot = sum_a (x_a - frame_trans) x g_a   (B,L,3) each, as in abx_clash_grad.
+ * hotspots: H <= 64 row indices.  restr_idx: R <= 256 rows of {row_i, slot_i, row_j, slot_j}; restr_par: R rows of {lo, hi, weight}.
+ * The *_host pointers are host copies of the same tables (required when H / R > 0): the argument checks read them before any launch;
+ * the kernels read the device copies and skip an entry whose indices are out of range.
+ * No atomics, fixed summation order; a sample's numbers do not depend on its neighbours in the batch.
+ * The caller allocates the workspace (abx_contact_grad_workspace_bytes). */
+typedef struct AbxContactArgs {
+    const float* atom14; const unsigned char* atom_mask;   /* (B,L,14,3), (B,L,14) */
+    const unsigned char* moved;                             /* (B,L) */
+    const unsigned char* target;                            /* (L) */
+    const float* frame_trans;                               /* (B,L,3) */
+    const int* hotspots; const int* hotspots_host;          /* (H) */
+    const int* restr_idx; const int* restr_idx_host;        /* (R,4) */
+    const float* restr_par; const float* restr_par_host;    /* (R,3) */
+    float w_contact, d0, d1, w_hot, d_hot, beta;
+    float* energy;                                          /* (B,3): contact, hotspot, restraint */
+    float* grad_atom; float* grad_trans; float* grad_rot;
+    int B, L, H, R;
+} AbxContactArgs;
+long long abx_contact_grad_workspace_bytes(int B, int L, int H);
+int abx_contact_grad(const AbxContactArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Design scores (SURVEY.md 8f-4 "eval metrics"): what the reference computes offline from the written PDB files, per structure of a
  * batch of B designs of ONE complex, on the device.  One row of ABX_SCORE_COLS float64 values per structure:
  *   0-13  {heavy,light}_cdr{1,2,3}_{AAR,RMSD} and heavy_cdr3_Loop_{AAR,RMSD} in the order of abx/common/ab_utils.py:124-167
