@@ -355,6 +355,7 @@ _PROTOS = {
     'abx_tri_rowpack_bytes': (LL, []),
     'abx_tri_rowpack': (I, [C.POINTER(AbxLinearPack), c_f, C.POINTER(AbxTriRowPack), _S]),
     'abx_tri_attn_rowfused_ok': (I, [I]),
+    'abx_tri_row_touch': (I, [I]),
     'abx_tri_attn_rowfused_fwd': (I, [C.POINTER(AbxTriAttn), c_f, LL, LL, LL, C.POINTER(AbxTriRowPack), I, _S]),
     'abx_seq_attn_fwd': (I, [c_f, c_f, c_f, c_f, c_f, I, I, I, I, F, _S]),
     'abx_ipa_pack': (I, [c_f, c_f, c_f, c_f, c_f, c_f, I, I, F, _S]),

@@ -21,10 +21,12 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "common.h"
 #include "abx_hip.h"
+#include "tri_row_touch.h"
 
 namespace {
 
@@ -908,6 +910,11 @@ __device__ __forceinline__ void tri8_row_compute(const AbxTriAttn& a, const Tri8
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) bad |= __builtin_amdgcn_classf(v[r], 0x207);
+#ifdef ABX_TRI_ROW_NT_STORE  // (probe build: non-temporal stores of the row-fused kernel's write-once output rows, 67 KB per slot that pass through an L2
+                             //  the z rows and the bias maps compete for)
+            if constexpr (!CHUNK_BARRIER) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(op + dd));
+            else
+#endif
             *reinterpret_cast<f32x4*>(op + dd) = v;
         }
     }
@@ -1261,7 +1268,8 @@ template <int I0_, int I1_, class F> __device__ __forceinline__ void tri_static_
 //      global_load_lds, issued by the twelfth wave (at L <= 352 it has no rows): the first three stages into a 24 KB ring while the
 //      computing waves are still in phase A of the previous slot, the other twelve into the plane region, which is empty until the tile
 //      epilogues write K / V.  Five block barriers per slot (see the issuing wave); a barrier per stage cost 0.8 ms per launch more.
-//      The issuing wave also touches the z row of the next slot, so that its projection starts from the L2.
+//      The issuing wave can also touch the z row ahead of the walk (TriRowArgs.touch, tri_row_touch.h), so that the projection starts
+//      from the L2; measured, every touch schedule loses to none (RF_DEFAULT_TOUCH).
 //   A  tri8_row_compute on the resident row (one "chunk"), no barrier inside.
 // Every product, sum and rounding is the one the two launches perform: the output is bit-identical to gemm_as + tri_attn8.
 // Slot order (TriRowArgs.order): 0 = (b, row, h) with the four heads of a row on neighbouring workgroups of one XCD (the 270 KB of
@@ -1279,12 +1287,26 @@ constexpr int RF_TILES = 5, RF_SPS = 3 * RF_TILES;           // column tiles (16
 constexpr int RF_HEAD_BYTES = RF_SPS * RF_STAGE;             // 122 880 per head
 constexpr int RF_DEFAULT_ORDER = 0;                          // slot order of slot_order = -1 (AbxTriRowPack / abx_tri_attn_rowfused_fwd)
 constexpr int RF_NK = 12;                                    // k-tiles: 192 input channels
+// The issuing wave's counted waits.  Its vector-memory queue behind barrier (a) holds the DMA instructions of G1 and G2 (RF_VM_GROUP each) and,
+// with TriRowArgs.touch == 2, the RFT_N touch loads of k-group 1 between them and those of k-group 2 behind barrier (b); results return
+// in issue order, so "G1 landed" = at most G2 and the touches in flight, "G2 landed" = at most the touches of k-group 2.
+constexpr int RF_VM_GROUP = (RF_SPS - RF_G0) / 2 * (RF_STAGE / 1024);       // 48 DMA instructions per group
+constexpr int RF_VM_B = RF_VM_GROUP, RF_VM_C = 0;                           // barriers (b), (c) without touches inside phase P
+constexpr int RF_VM_B_JIT = RF_VM_GROUP + RFT_N, RF_VM_C_JIT = RFT_N;       // touch == 2: 60, 12
+static_assert(RF_VM_B_JIT <= 63, "vmcnt is a 6-bit count");
+static_assert(RF_LK == RFT_LMAX && RF_NK * 16 == RFT_CH && RF_NK == 4 * RFT_KGROUPS, "tri_row_touch.h describes this walk");
+// TriRowArgs.touch without ABX_TRI_ROW_TOUCH / abx_tri_row_touch: no touch.  On the counters the whole-row touch (1) costs 9.2 GB of reads per
+// launch at 100 samples of L = 352 (its lines are gone before the walks reach them) and 1 ms; the just-in-time schedule (2) costs
+// 1.5 GB and 0.6 ms; only 0 gains on the whole step (profiles/tri_rowfused_z_once_*.txt)
+constexpr int RF_DEFAULT_TOUCH = 0;
 
 struct TriRowArgs {
     const float* z; long long zb, zs, zl;                    // element (b, s, l, c) at z + b zb + s zs + l zl + c
     const char* wp; const float* csum; const float* bias;    // AbxTriRowPack
     float cs, inv_cs, eps;                                   // 2^-(a_exp + b_exp), its inverse, LayerNorm eps
     int order;
+    int touch;                                               // the issuing wave's touches of z: 0 none, 1 the next slot's whole row at the start of
+                                                             // phase A, 2 per k-group just ahead of the walk (tri_row_touch.h)
 };
 
 __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const AbxTriAttn a, const TriRowArgs p) {
@@ -1337,12 +1359,25 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024),
                                                  (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
         };
+        // touch == 2: the RFT_N loads of k-group g of a row, one per 128-byte line.  They are inline assembly into ONE register that nothing
+        // reads: the compiler places no wait for them (a wait of its own between the DMA instructions would drain the queue), and the
+        // register stays allocated up to barrier (a), whose vmcnt(0) retires the last of them.
+        const bool jit = p.touch == 2;
+        unsigned tv = 0;
+        auto touch_kg = [&](const float* zr, int g) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < RFT_N; ++i) {
+                const float* q = zr + rf_touch_offset(L, p.zl, g, lane, i);
+                asm volatile("global_load_dword %0, %1, off" : "+v"(tv) : "v"(q) : "memory");
+            }
+        };
         if (nmine > 0) {
             decode(0, r);
             dma(r.h, 0, std::integral_constant<int, RF_G0>{}, ring);
         }
         for (int it = 0; it < nmine; ++it) {
             decode(it, r);
+            const float* zcur = p.z + (long long)r.b * p.zb + (long long)r.s * p.zs;
             // key clamps of the slot, applied as logit = min(logit, clamp): +inf valid, finfo.min masked, -inf beyond L (tri_attn8_kernel), and
             // the column constants of its head (read by the tile epilogues).  Their loads are issued HERE, in front of barrier (a) - this wave
             // idles there through phase A of the previous slot - and are UNCONDITIONAL (no key mask: the same number of loads from the
@@ -1365,10 +1400,17 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
             // compiler has no wait of its own to place between the DMA instructions below
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier"
                          : "+v"(kmv[0]), "+v"(kmv[1]), "+v"(kmv[2]), "+v"(kmv[3]), "+v"(kmv[4]), "+v"(kmv[5]), "+v"(csv[0]), "+v"(csv[1]), "+v"(csv[2]),
-                           "+v"(biv[0]), "+v"(biv[1]), "+v"(biv[2])
+                           "+v"(biv[0]), "+v"(biv[1]), "+v"(biv[2]), "+v"(tv)
                          :
                          : "memory");
-            dma(r.h, RF_G0, std::integral_constant<int, RF_SPS - RF_G0>{}, lds);
+            if (jit) {
+                // G1, the touches of k-group 1 (the computing waves walk k-group 0 from here on), G2
+                dma(r.h, RF_G0, std::integral_constant<int, (RF_SPS - RF_G0) / 2>{}, lds);
+                touch_kg(zcur, 1);
+                dma(r.h, RF_G0 + (RF_SPS - RF_G0) / 2, std::integral_constant<int, (RF_SPS - RF_G0) / 2>{}, lds + (RF_SPS - RF_G0) / 2 * RF_STAGE);
+            } else {
+                dma(r.h, RF_G0, std::integral_constant<int, RF_SPS - RF_G0>{}, lds);
+            }
             const bool has_km = r.km != nullptr;
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
@@ -1384,25 +1426,38 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
                 }
             }
             // (b): G1 = the first 48 of the 96 DMA instructions has landed (results return in issue order; the 48 of G2 stay in flight)
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((RF_SPS - RF_G0) / 2 * (RF_STAGE / 1024)) : "memory");
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");                     // (c): G2 has landed
+            // (c): G2 has landed.  touch == 2: the touches of k-group 2 go out behind (b), while the computing waves walk k-group 1
+            if (jit) {
+                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(RF_VM_B_JIT) : "memory");
+                touch_kg(zcur, 2);
+                asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(RF_VM_C_JIT) : "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(RF_VM_B) : "memory");
+                asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(RF_VM_C) : "memory");
+            }
             asm volatile("s_barrier" ::: "memory");                                            // (d)
             asm volatile("s_barrier" ::: "memory");                                            // (e)
             // while the computing waves are in phase A: G0 of the NEXT slot, and a touch of its z row (one load per 128-byte line), so that its
-            // projection starts from the L2 instead of waiting out an HBM round trip in front of every wave's first k-tile
+            // projection starts from the L2 instead of waiting out an HBM round trip in front of every wave's first k-tile: the whole row
+            // (touch == 1: 270 KB that have to survive phase A in the L2) or the lines of k-group 0 alone (touch == 2)
             if (it + 1 < nmine) {
                 decode(it + 1, r);
                 dma(r.h, 0, std::integral_constant<int, RF_G0>{}, ring);
                 const float* zr = p.z + (long long)r.b * p.zb + (long long)r.s * p.zs;
-                unsigned x = 0;
-                for (int l = lane; l < L; l += 64) {
-                    const float* zq = zr + (long long)l * p.zl;
+                if (jit) {
+                    touch_kg(zr, 0);
+                } else if (p.touch == 1) {
+                    unsigned x = 0;
+                    for (int l = lane; l < L; l += 64) {
+                        const float* zq = zr + (long long)l * p.zl;
 #pragma unroll
-                    for (int j = 0; j < 6; ++j) x ^= __builtin_bit_cast(unsigned, zq[j * 32]);
+                        for (int j = 0; j < 6; ++j) x ^= __builtin_bit_cast(unsigned, zq[j * 32]);
+                    }
+                    asm volatile("" ::"v"(x));
                 }
-                asm volatile("" ::"v"(x));
             }
         }
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(tv) : : "memory");
         probe.finish();
         return;
     }
@@ -1444,8 +1499,8 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
         for (int t = 0; t < RF_TILES; ++t)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-        const int pos = min(32 * wave + pr, L - 1);              // positions beyond the row: the last one again (keys clamped to -inf, queries never stored)
-        const float* zp = p.z + (long long)cur.b * p.zb + (long long)cur.s * p.zs + (long long)pos * p.zl + 8 * hh;
+        // (positions beyond the row: the last one again - keys clamped to -inf, queries never stored)
+        const float* zp = p.z + (long long)cur.b * p.zb + (long long)cur.s * p.zs + rf_walk_base(L, p.zl, wave, pr, hh);
         float lshift = 0.f;
         f32x2 ls2 = {0.f, 0.f}, lq2 = {0.f, 0.f};
         tri_static_for<0, 3>([&](auto kg_) __attribute__((always_inline)) {
@@ -1455,8 +1510,8 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
                 f32x4 lo[4], hi[4];
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
-                    lo[kk] = *reinterpret_cast<const f32x4*>(zp + (4 * kg + kk) * 16);
-                    hi[kk] = *reinterpret_cast<const f32x4*>(zp + (4 * kg + kk) * 16 + 4);
+                    lo[kk] = *reinterpret_cast<const f32x4*>(zp + rf_walk_ktile(4 * kg + kk));
+                    hi[kk] = *reinterpret_cast<const f32x4*>(zp + rf_walk_ktile(4 * kg + kk) + 4);
                 }
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
@@ -1908,6 +1963,15 @@ extern "C" int abx_tri_attn_rowfused_ok(int L) {
     return (!off && L > 0 && L <= ABX_TRI_ROWFUSED_LMAX) ? 1 : 0;
 }
 
+extern "C" int abx_tri_row_touch(int v) {
+    // ABX_TRI_ROW_TOUCH = 0 | 1 | 2, read once on the C side (A / B measurements); anything else: the default
+    static std::atomic<int> cur{[] {
+        const char* e = getenv("ABX_TRI_ROW_TOUCH");
+        return (e && e[0] >= '0' && e[0] <= '2' && e[1] == 0) ? e[0] - '0' : RF_DEFAULT_TOUCH;
+    }()};
+    return (v >= 0 && v <= 2) ? cur.exchange(v) : cur.load();
+}
+
 extern "C" int abx_tri_attn_rowfused_fwd(const AbxTriAttn* ap, const float* z, long long zb, long long zs, long long zl, const AbxTriRowPack* pk,
                                          int slot_order, hipStream_t st) {
     ABX_REQUIRE(ap != nullptr && z && pk, "abx_tri_attn_rowfused_fwd: null argument");
@@ -1937,6 +2001,7 @@ extern "C" int abx_tri_attn_rowfused_fwd(const AbxTriAttn* ap, const float* z, l
     p.inv_cs = ldexpf(1.0f, ABX_F16_A_EXP + pk->b_exp);
     p.eps = 1e-5f;
     p.order = slot_order < 0 ? RF_DEFAULT_ORDER : slot_order;
+    p.touch = abx_tri_row_touch(-1);
     static int n_cu = 0;
     if (n_cu == 0) {
         int dev = 0;

@@ -602,6 +602,13 @@ def _tri_rowfused_ok(L):
     return bool(_lib.load().abx_tri_attn_rowfused_ok(int(L)))
 
 
+def tri_row_touch(v=-1):
+    """How the row-fused kernel's issuing wave warms the L2 with the z rows (abx_tri_row_touch): 0 none, 1 the whole next row a phase ahead,
+    2 per k-group just ahead of the walk.  v = 0 | 1 | 2 sets it for later launches of this process, anything else only asks; returns the
+    setting that held before.  The start value is the library's (ABX_TRI_ROW_TOUCH, read on the C side only).  Same bits for all three."""
+    return int(_lib.load().abx_tri_row_touch(int(v)))
+
+
 _TRI_ATTN_LAST = None       # (L, exact, row-fused) of the most recent tri_attn launch: what a caller that times launches asks the name of
 
 

@@ -347,6 +347,12 @@ int abx_tri_attn_rowfused_ok(int L);
  * 1 = (b, h, row): the order of tri_attn8_kernel (one bias map per XCD, z fetched four times); -1 = library default. */
 int abx_tri_attn_rowfused_fwd(const AbxTriAttn* desc, const float* z, long long zb, long long zs, long long zl, const AbxTriRowPack* pack,
                               int slot_order, hipStream_t stream);
+/* How the kernel's issuing wave warms the L2 with the z rows (TriRowArgs.touch, csrc/tri_row_touch.h): 0 = not at all, 1 = the whole
+ * next row at the start of the attention phase, 2 = per k-group just ahead of the projection's walk.  Same bits for all three; the
+ * default is 0 (the one that measures fastest on the whole step).  The start value comes from the environment variable ABX_TRI_ROW_TOUCH (0 | 1 | 2, read once, on the C side only: A / B
+ * measurements).  v = 0, 1, 2: the setting of later launches of this process; any other v changes nothing.  Returns the setting that held
+ * before the call. */
+int abx_tri_row_touch(int v);
 
 /* Sequence attention with pair bias (seqformer.py:314-356 + Attention.forward split_first=False :278-312).
  * qkv: [B*L][H*3*D] with per-head layout [q D | k D | v D]; bias [b][h][q][k]; gate pre-activation [B*L][H*D];
