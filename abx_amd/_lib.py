@@ -349,6 +349,7 @@ _PROTOS = {
     'abx_ipa_tail': (I, [C.POINTER(AbxIpaTail), _S]),
     'abx_heads_tail': (I, [C.POINTER(AbxHeadsTail), _S]),
     'abx_gemm3_occupancy': (I, [I]),
+    'abx_gemm_plan': (I, [C.POINTER(AbxGemm), C.POINTER(AbxGemm), C.c_char_p, I]),
     'abx_row_stats': (I, [c_f, LL, LL, LL, I, I, I, F, c_f, _S]),
     'abx_layernorm': (I, [c_f, LL, LL, I, c_f, c_f, F, c_f, LL, c_f, LL, _S]),
     'abx_tri_attn_fwd': (I, [C.POINTER(AbxTriAttn), _S]),
@@ -356,6 +357,7 @@ _PROTOS = {
     'abx_tri_rowpack': (I, [C.POINTER(AbxLinearPack), c_f, C.POINTER(AbxTriRowPack), _S]),
     'abx_tri_attn_rowfused_ok': (I, [I]),
     'abx_tri_row_touch': (I, [I]),
+    'abx_tri_attn_plan': (I, [C.POINTER(AbxTriAttn), I, C.c_char_p, I]),
     'abx_tri_attn_rowfused_fwd': (I, [C.POINTER(AbxTriAttn), c_f, LL, LL, LL, C.POINTER(AbxTriRowPack), I, _S]),
     'abx_seq_attn_fwd': (I, [c_f, c_f, c_f, c_f, c_f, I, I, I, I, F, _S]),
     'abx_ipa_pack': (I, [c_f, c_f, c_f, c_f, c_f, c_f, I, I, F, _S]),

@@ -191,7 +191,6 @@ extern "C" int abx_assemble_pair_bias(const float* pair_static, long long ps_b, 
     ABX_REQUIRE(pair_static && temb && out && w_planes && csum && biasT && B > 0 && L > 0, "abx_assemble_pair_bias: bad args");
     ABX_REQUIRE(!prev_pair || (gamma && beta), "abx_assemble_pair_bias: LN params missing");
     ABX_REQUIRE(!prev_pos || pos_table, "abx_assemble_pair_bias: pos table missing");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     ABX_REQUIRE(al16(pair_static) && ps_b % 4 == 0 && al16(temb) && al16(out) && al16(w_planes) && (!prev_pair || al16(prev_pair)) &&
                     (!prev_pos || al16(pos_table)),
                 "abx_assemble_pair_bias: 16-byte aligned operands (C = 128, E = 32, 32 heads)");

@@ -1823,7 +1823,8 @@ __global__ __launch_bounds__(NT) void seq_attn2_kernel(const float* __restrict__
 
 }  // namespace
 
-extern "C" int abx_tri_attn_fwd(const AbxTriAttn* ap, hipStream_t st) {
+// abx_tri_attn_fwd (plan == nullptr) / abx_tri_attn_plan: the kernel is launched or named where it is chosen
+static int tri_attn_run(const AbxTriAttn* ap, hipStream_t st, AbxPlan* plan) {
     ABX_REQUIRE(ap != nullptr, "abx_tri_attn_fwd: null descriptor");
     const AbxTriAttn a = *ap;
     ABX_REQUIRE(a.q && a.k && a.v && a.out, "abx_tri_attn_fwd: null operand");
@@ -1832,7 +1833,6 @@ extern "C" int abx_tri_attn_fwd(const AbxTriAttn* ap, hipStream_t st) {
     ABX_REQUIRE(a.S <= 65535 && a.B <= 65535, "abx_tri_attn_fwd: grid too large");
     ABX_REQUIRE((a.sb % 4 == 0) && (a.ss % 4 == 0) && (a.sl % 4 == 0) && (a.ob % 4 == 0) && (a.os % 4 == 0) && (a.ol % 4 == 0),
                 "abx_tri_attn_fwd: strides must be multiples of 4 floats");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     ABX_REQUIRE(al16(a.q) && al16(a.k) && al16(a.v) && al16(a.out) && (!a.gate || al16(a.gate)),
                 "abx_tri_attn_fwd: pointers must be 16-byte aligned");
     ABX_REQUIRE(!a.kv_planes || !a.exact, "abx_tri_attn_fwd: kv_planes goes with the split-f16 kernel (exact = 0)");
@@ -1857,7 +1857,7 @@ extern "C" int abx_tri_attn_fwd(const AbxTriAttn* ap, hipStream_t st) {
         // tri_attn4: one workgroup per (b, h, row, part) slot; tri_attn8: persistent, one workgroup per CU (8 XCDs x CUs / 8), each
         // walking the slots of its XCD with a stride of the workgroups per XCD
         static int n_cu = 0;
-        if (paired && n_cu == 0) {
+        if (paired && n_cu == 0 && !plan) {
             int dev = 0;
             hipDeviceProp_t prop;
             if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
@@ -1869,37 +1869,37 @@ extern "C" int abx_tri_attn_fwd(const AbxTriAttn* ap, hipStream_t st) {
         const long long slots_xcd = nvp8 / 8 * rows_g * aa.q_parts;
         const unsigned wg_xcd = paired ? (unsigned)std::min<long long>(n_cu / 8, slots_xcd) : 0;
         const dim3 grid(paired ? 8 * wg_xcd : (unsigned)(nvp8 * rows_g * aa.q_parts)), block(TRI_THREADS);
-        auto launch = [&](auto kern, size_t lds4) -> int {
-            if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds4, "abx_tri_attn_fwd")) return rc;
-            hipLaunchKernelGGL(kern, grid, block, lds4, st, aa);
-            return abx_check_launch("abx_tri_attn_fwd");
-        };
-        auto lds_of = [](int kc, bool db) { return (size_t)(db ? 2 : 1) * (4 * kc * RST + kc * sizeof(float)); };
+        auto lds_of = [](int kc) { return (size_t)2 * (4 * kc * RST + kc * sizeof(float)); };      // double-buffered key chunks
+#define TRI8_LAUNCH(KC, BVEC)                                                                                                                    \
+    ABX_LAUNCH(plan, ("tri_attn8_kernel<%d, %d, %s>", KC, TRI_THREADS, ABX_BOOL(BVEC)), "abx_tri_attn_fwd", (&tri_attn8_kernel<KC, TRI_THREADS, BVEC>), \
+               (int)lds_of(KC), grid, block, lds_of(KC), st, aa)
+#define TRI4_LAUNCH(KC, PROD)                                                                                                                    \
+    ABX_LAUNCH(plan, ("tri_attn4_kernel<2, %d, true, %d, %s>", KC, TRI_THREADS, ABX_BOOL(PROD)), "abx_tri_attn_fwd",                              \
+               (&tri_attn4_kernel<2, KC, true, TRI_THREADS, PROD>), (int)lds_of(KC), grid, block, lds_of(KC), st, aa)
         if (paired) {
             const float* bb = a.bias;
             const bool bvec = bb && a.bias_sk == 1 && a.bias_sq % 4 == 0 && a.bias_sq >= 4 && a.bias_sb % 4 == 0 && a.bias_sh % 4 == 0 && al16(bb);
             // key chunks of 192 unless 128 gives the same number of chunks (then: less LDS to fill before the first tile, a less ragged
             // last chunk; L = 231: 2.52 vs 2.79 ms at 20 samples, L = 352: 21.2 vs 19.2 ms at 100).  tune bit 1 flips the choice.
             const bool kc128 = (((a.L + 127) / 128 == (a.L + 191) / 192) != ((a.tune & 2) != 0));
-            if (kc128)
-                return bvec ? launch(&tri_attn8_kernel<128, TRI_THREADS, true>, lds_of(128, true))
-                            : launch(&tri_attn8_kernel<128, TRI_THREADS, false>, lds_of(128, true));
-            return bvec ? launch(&tri_attn8_kernel<192, TRI_THREADS, true>, lds_of(192, true))
-                        : launch(&tri_attn8_kernel<192, TRI_THREADS, false>, lds_of(192, true));
+            if (kc128) return bvec ? TRI8_LAUNCH(128, true) : TRI8_LAUNCH(128, false);
+            return bvec ? TRI8_LAUNCH(192, true) : TRI8_LAUNCH(192, false);
         }
-        if (prod && (a.tune & 2)) return launch(&tri_attn4_kernel<2, 128, true, TRI_THREADS, true>, lds_of(128, true));   // benchmarking
-        if (prod) return launch(&tri_attn4_kernel<2, 192, true, TRI_THREADS, true>, lds_of(192, true));
-        return launch(&tri_attn4_kernel<2, 128, true, TRI_THREADS, false>, lds_of(128, true));
+        if (prod && (a.tune & 2)) return TRI4_LAUNCH(128, true);   // benchmarking
+        if (prod) return TRI4_LAUNCH(192, true);
+        return TRI4_LAUNCH(128, false);
+#undef TRI8_LAUNCH
+#undef TRI4_LAUNCH
     }
     // exact fp32 kernel: the whole row's K / V in LDS when it fits (L <= 389), key chunks of 320 otherwise (no length limit)
     auto lds_of_exact = [](int kc) { return ((((size_t)kc * LDK + 3) & ~(size_t)3) + (size_t)kc * LDV + (size_t)((kc + 63) / 64) * 64 + 4) * sizeof(float); };
     const int kc = lds_of_exact(a.L) <= 160 * 1024 ? a.L : 320;      // (chunks start at multiples of 64: aligned bias loads)
     const size_t lds = lds_of_exact(kc);
     ABX_REQUIRE(lds <= 160 * 1024, "abx_tri_attn_fwd: internal: exact-kernel LDS layout");
-    if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(tri_attn_kernel), 160 * 1024, "abx_tri_attn_fwd")) return rc;
-    hipLaunchKernelGGL(tri_attn_kernel, dim3(a.H, a.S, a.B), dim3(TRI_THREADS), lds, st, a, kc);
-    return abx_check_launch("abx_tri_attn_fwd");
+    return ABX_LAUNCH_LIT(plan, "abx_tri_attn_fwd", &tri_attn_kernel, 160 * 1024, dim3(a.H, a.S, a.B), dim3(TRI_THREADS), lds, st, a, kc);
 }
+
+extern "C" int abx_tri_attn_fwd(const AbxTriAttn* ap, hipStream_t st) { return tri_attn_run(ap, st, nullptr); }
 
 extern "C" int abx_seq_attn_fwd(const float* qkv, const float* bias, const float* keymask, const float* gate, float* out,
                                 int B, int L, int H, int D, float scale, hipStream_t st) {
@@ -1972,8 +1972,9 @@ extern "C" int abx_tri_row_touch(int v) {
     return (v >= 0 && v <= 2) ? cur.exchange(v) : cur.load();
 }
 
-extern "C" int abx_tri_attn_rowfused_fwd(const AbxTriAttn* ap, const float* z, long long zb, long long zs, long long zl, const AbxTriRowPack* pk,
-                                         int slot_order, hipStream_t st) {
+// abx_tri_attn_rowfused_fwd (plan == nullptr) / abx_tri_attn_plan
+static int tri_attn_rowfused_run(const AbxTriAttn* ap, const float* z, long long zb, long long zs, long long zl, const AbxTriRowPack* pk,
+                                 int slot_order, hipStream_t st, AbxPlan* plan) {
     ABX_REQUIRE(ap != nullptr && z && pk, "abx_tri_attn_rowfused_fwd: null argument");
     AbxTriAttn a = *ap;
     ABX_REQUIRE(a.out && a.bias && pk->planes && pk->csum && pk->bias, "abx_tri_attn_rowfused_fwd: null operand");
@@ -1982,7 +1983,6 @@ extern "C" int abx_tri_attn_rowfused_fwd(const AbxTriAttn* ap, const float* z, l
     ABX_REQUIRE(a.L <= ABX_TRI_ROWFUSED_LMAX, "abx_tri_attn_rowfused_fwd: L beyond ABX_TRI_ROWFUSED_LMAX (the two launches serve longer rows)");
     ABX_REQUIRE(!a.exact && !a.kv_planes && !a.gate, "abx_tri_attn_rowfused_fwd: split-f16 arithmetic, no gate, no operand images");
     ABX_REQUIRE(slot_order >= -1 && slot_order <= 1, "abx_tri_attn_rowfused_fwd: slot_order is -1, 0 or 1");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     ABX_REQUIRE((zb % 4 == 0) && (zs % 4 == 0) && (zl % 4 == 0) && (a.ob % 4 == 0) && (a.os % 4 == 0) && (a.ol % 4 == 0) && al16(z) && al16(a.out) &&
                     al16(pk->planes) && al16(pk->csum) && al16(pk->bias),
                 "abx_tri_attn_rowfused_fwd: strides must be multiples of 4 floats, pointers 16-byte aligned");
@@ -2003,7 +2003,7 @@ extern "C" int abx_tri_attn_rowfused_fwd(const AbxTriAttn* ap, const float* z, l
     p.order = slot_order < 0 ? RF_DEFAULT_ORDER : slot_order;
     p.touch = abx_tri_row_touch(-1);
     static int n_cu = 0;
-    if (n_cu == 0) {
+    if (n_cu == 0 && !plan) {
         int dev = 0;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
@@ -2015,7 +2015,25 @@ extern "C" int abx_tri_attn_rowfused_fwd(const AbxTriAttn* ap, const float* z, l
     const long long nunit = p.order == 0 ? (long long)a.B * a.S : (long long)a.B * a.H;
     const long long slots_xcd = (nunit + 7) / 8 * (p.order == 0 ? a.H : a.S);
     const unsigned wg_xcd = (unsigned)std::min<long long>(n_cu / 8, slots_xcd);
-    if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&tri_attn8_rowfused_kernel), RF_LDS, "abx_tri_attn_rowfused_fwd")) return rc;
-    hipLaunchKernelGGL(tri_attn8_rowfused_kernel, dim3(8 * wg_xcd), dim3(TRI_THREADS), RF_LDS, st, a, p);
-    return abx_check_launch("abx_tri_attn_rowfused_fwd");
+    return ABX_LAUNCH_LIT(plan, "abx_tri_attn_rowfused_fwd", &tri_attn8_rowfused_kernel, RF_LDS, dim3(8 * wg_xcd), dim3(TRI_THREADS), RF_LDS, st, a, p);
+}
+
+extern "C" int abx_tri_attn_rowfused_fwd(const AbxTriAttn* ap, const float* z, long long zb, long long zs, long long zl, const AbxTriRowPack* pk,
+                                         int slot_order, hipStream_t st) {
+    return tri_attn_rowfused_run(ap, z, zb, zs, zl, pk, slot_order, st, nullptr);
+}
+
+extern "C" int abx_tri_attn_plan(const AbxTriAttn* ap, int rowfused, char* name, int cap) {
+    ABX_REQUIRE(ap && name && cap > 0, "abx_tri_attn_plan: null descriptor or no room for the name");
+    AbxPlan plan = {};
+    // row-fused: the z rows lie where the descriptor's q rows would (strides sb / ss / sl); z and the row pack are stand-ins that pass the operand
+    // checks - an address is looked at, never followed
+    alignas(16) static const char stand_in[16] = {};
+    const AbxTriRowPack pk = {reinterpret_cast<const unsigned short*>(stand_in), reinterpret_cast<const float*>(stand_in),
+                              reinterpret_cast<const float*>(stand_in), 0, 4};
+    if (int rc = rowfused ? tri_attn_rowfused_run(ap, reinterpret_cast<const float*>(stand_in), ap->sb, ap->ss, ap->sl, &pk, -1, nullptr, &plan)
+                          : tri_attn_run(ap, nullptr, &plan))
+        return rc;
+    snprintf(name, (size_t)cap, "%s", plan.name);
+    return ABX_OK;
 }

@@ -1,7 +1,10 @@
 // Shared device/host helpers for libabx_hip (gfx950 / CDNA4 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <string.h>
 
 #define ABX_OK 0
 #define ABX_ERR_ARG (-1)
@@ -23,6 +26,52 @@ int abx_ensure_dynamic_lds(const void* kernel, int bytes, const char* what);
             return ABX_ERR_ARG;           \
         }                                 \
     } while (0)
+
+// ---- one launch path for the GEMM and triangle-attention dispatchers -----------------------------------------------------------
+// The dispatchers take a nullable plan.  Null: they launch.  Non-null (abx_gemm_plan / abx_tri_attn_plan): the branch that would launch
+// writes its kernel's name instead and returns 0 - no HIP runtime call, no operand dereferenced, so it runs without a GPU.  The name
+// stands at the launch (ABX_LAUNCH), printed from the template arguments of that very instantiation: there is no second selection.
+struct AbxPlan { char name[128]; };
+#define ABX_BOOL(b) ((b) ? "true" : "false")
+__attribute__((format(printf, 2, 3))) inline int abx_plan_name(AbxPlan* plan, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(plan->name, sizeof(plan->name), fmt, ap);
+    va_end(ap);
+    return ABX_OK;
+}
+// ensure_lds > 0: the kernel's dynamic-LDS limit is raised to that many bytes first (abx_ensure_dynamic_lds)
+template <typename Kernel, typename... Args>
+inline int abx_launch(const char* what, Kernel kernel, int ensure_lds, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+    if (ensure_lds > 0)
+        if (int e = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), ensure_lds, what)) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    return abx_check_launch(what);
+}
+// the kernel expression as the launch site spells it - "(gemm3_dual_kernel<128, 96, 32, 96, 3>)", "&gemm3_side_kernel" - without parentheses and '&'
+inline int abx_plan_literal(AbxPlan* plan, const char* expr) {
+    while (*expr == '(' || *expr == '&') ++expr;
+    int n = (int)strlen(expr);
+    while (n > 0 && expr[n - 1] == ')') --n;
+    return abx_plan_name(plan, "%.*s", n, expr);
+}
+// Launch or name; both evaluate to the return code.  ABX_LAUNCH: the kernel's template arguments are template parameters of the site, NAME is
+// (format, arguments...) in parentheses.  ABX_LAUNCH_LIT: they are literals, the kernel expression itself is the name.  The rest: abx_launch.
+#define ABX_PLAN_NAME_(plan, ...) abx_plan_name(plan, __VA_ARGS__)
+#define ABX_PLAN_ARGS_(...) __VA_ARGS__
+#define ABX_LAUNCH(plan, NAME, what, kernel, ...) ((plan) ? ABX_PLAN_NAME_(plan, ABX_PLAN_ARGS_ NAME) : abx_launch(what, kernel, __VA_ARGS__))
+#define ABX_LAUNCH_LIT(plan, what, kernel, ...) ((plan) ? abx_plan_literal(plan, #kernel) : abx_launch(what, kernel, __VA_ARGS__))
+
+// 16-byte alignment of an operand address, and the clusters of it that the dispatchers share
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// float16 operand planes [k/16][plane][row][16] (abx_split_weights_f16 / activation images): row, plane, k-tile (and batch) strides in halves
+inline bool planes_ok(const void* p, long long s_row, long long s_plane, long long s_k, long long s_b = 0) {
+    return al16(p) && s_row % 8 == 0 && s_plane % 8 == 0 && s_k % 8 == 0 && s_b % 8 == 0;
+}
+// fp32 rows read with 16-byte loads: the two strides that are not 1, in floats
+inline bool rows_ok(const void* p, long long s_row, long long s_b) { return al16(p) && s_row % 4 == 0 && s_b % 4 == 0; }
+// the power-of-two exponent of weight planes (AbxGemm.b_exp)
+inline bool exp_ok(int e) { return e >= -100 && e <= 100; }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

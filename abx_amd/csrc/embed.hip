@@ -386,7 +386,6 @@ extern "C" int abx_assemble_pair(const float* pair_static, long long ps_b, const
     ABX_REQUIRE(!prev_pair || (gamma && beta), "abx_assemble_pair: LN params missing");
     ABX_REQUIRE(!prev_pos || pos_table, "abx_assemble_pair: pos table missing");
     const long long rows = (long long)B * L * L;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (C == 128 && E == 32 && !stats_out && ps_b % 4 == 0 && al16(pair_static) && al16(temb) && al16(out) &&
         (!prev_pair || (al16(prev_pair) && al16(gamma) && al16(beta))) && (!prev_pos || al16(pos_table))) {
         hipLaunchKernelGGL(assemble_pair192_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, pair_static, ps_b, temb,
@@ -402,7 +401,6 @@ extern "C" int abx_opm_features(const float* left, const float* right, long long
                                 hipStream_t st) {
     ABX_REQUIRE(left && right && feat && B > 0 && L > 0 && C > 0, "abx_opm_features: bad args");
     const long long total = (long long)B * L * L * C;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (C % 4 == 0 && ld % 4 == 0 && al16(left) && al16(right) && al16(feat)) {
         ABX_REQUIRE((total / 4 + 255) / 256 < (1LL << 31), "abx_opm_features: grid too large");
         hipLaunchKernelGGL(opm_features4_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, left, right, ld, feat, B, L,

@@ -25,7 +25,7 @@
 #include "abx_hip.h"
 #include "gemm_epilogue.h"
 
-int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc);     // gemm3.hip
+int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan);     // gemm3.hip
 
 namespace {
 
@@ -400,28 +400,32 @@ __global__ __launch_bounds__(256) void layernorm128_kernel(const float* __restri
 }
 
 template <int BM, int BN, int WM, int WN, int BK = 16, int MINW = 3>
-int launch_cfg(const AbxGemm& g, hipStream_t st) {
+int launch_cfg(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
     const long long mt = ((long long)g.M + BM - 1) / BM, ntn = ((long long)g.N + BN - 1) / BN;
     dim3 grid((unsigned)(mt * ntn), 1, (unsigned)g.batch), block(256);
     const bool akc = g.sAk == 1;
     const bool bnc = g.sBn == 1;
+#define GEMM_LAUNCH(AKC, BNC, TS)                                                                                                        \
+    ABX_LAUNCH(plan, ("gemm_kernel<%d, %d, %d, %d, %d, %s, %s, %s, %d>", BM, BN, WM, WN, BK, ABX_BOOL(AKC), ABX_BOOL(BNC), ABX_BOOL(TS), MINW), \
+               "abx_gemm", (gemm_kernel<BM, BN, WM, WN, BK, AKC, BNC, TS, MINW>), 0, grid, block, 0, st, g)
     if (g.c_transposed) {       // transposed store: weight GEMMs only (A k-contiguous activations, B packed weights)
         if (!(akc && bnc)) { abx_set_error("abx_gemm: transposed store needs k-contiguous A and n-contiguous B"); return ABX_ERR_ARG; }
-        hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, BK, true, true, true, MINW>), grid, block, 0, st, g);
-    } else if (akc && bnc) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, BK, true, true, false, MINW>), grid, block, 0, st, g);
-    else if (akc && !bnc) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, BK, true, false, false, MINW>), grid, block, 0, st, g);
-    else if (!akc && bnc) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, BK, false, true, false, MINW>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, BK, false, false, false, MINW>), grid, block, 0, st, g);
-    return abx_check_launch("abx_gemm");
+        return GEMM_LAUNCH(true, true, true);
+    }
+    if (akc && bnc) return GEMM_LAUNCH(true, true, false);
+    if (akc && !bnc) return GEMM_LAUNCH(true, false, false);
+    if (!akc && bnc) return GEMM_LAUNCH(false, true, false);
+    return GEMM_LAUNCH(false, false, false);
+#undef GEMM_LAUNCH
 }
 
 // tuning variants of the main weight-GEMM configuration (selected by AbxGemm.tune bits 1..3; 0 = default)
 template <int BK, int MINW>
-int launch_main_variant(const AbxGemm& g, hipStream_t st) {
+int launch_main_variant(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
     const long long mt = ((long long)g.M + 127) / 128, ntn = ((long long)g.N + 127) / 128;
     dim3 grid((unsigned)(mt * ntn), 1, (unsigned)g.batch), block(256);
-    hipLaunchKernelGGL((gemm_kernel<128, 128, 64, 64, BK, true, true, false, MINW>), grid, block, 0, st, g);
-    return abx_check_launch("abx_gemm");
+    return ABX_LAUNCH(plan, ("gemm_kernel<128, 128, 64, 64, %d, true, true, false, %d>", BK, MINW), "abx_gemm",
+                      (gemm_kernel<128, 128, 64, 64, BK, true, true, false, MINW>), 0, grid, block, 0, st, g);
 }
 
 }  // namespace
@@ -489,7 +493,6 @@ static int gemm_prepare(const AbxGemm* gp, AbxGemm& g) {
     if (g.out_ln_w && g.out_ln_eps <= 0.f) g.out_ln_eps = 1e-5f;
     const bool akc = g.sAk == 1;
     // 16-byte vector loads need aligned bases and strides that are multiples of 4 elements
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     g.a_vec_ok = al16(g.A) && (g.sAb % 4 == 0) && (akc ? (g.sAm % 4 == 0) : (g.sAk % 4 == 0));
     g.b_vec_ok = al16(g.B) && (g.sBb % 4 == 0) && (g.sBn == 1 ? (g.sBk % 4 == 0) : (g.sBn % 4 == 0));
     g.fast_ok = g.a_vec_ok && g.b_vec_ok;
@@ -507,8 +510,8 @@ static int gemm_prepare(const AbxGemm* gp, AbxGemm& g) {
     return ABX_OK;
 }
 
-int abx_gemm3_side_dispatch(const AbxGemm& g, const AbxGemm& s2, hipStream_t st, int* rc);
-int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, int* rc);      // gemm_as.hip
+int abx_gemm3_side_dispatch(const AbxGemm& g, const AbxGemm& s2, hipStream_t st, int* rc, AbxPlan* plan);
+int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, int* rc, AbxPlan* plan);      // gemm_as.hip
 
 // 1 when a (main, side) pair of M rows takes the A-stationary kernel, i.e. may ask for plane output (AbxGemm.c_planes_from): the size rule of
 // abx_gemm_as_dispatch (the walk pays from 1 024 blocks of 64 rows on).  Callers that switch the k | v format on it stay bit-invariant under
@@ -518,34 +521,16 @@ extern "C" int abx_gemm_planes_ok(long long M) {
     return (!off && (M + 63) / 64 >= 1024) ? 1 : 0;
 }
 
-extern "C" int abx_gemm_side(const AbxGemm* main_gemm, const AbxGemm* side_gemm, hipStream_t st) {
-    ABX_REQUIRE(main_gemm && side_gemm, "abx_gemm_side: null descriptor");
-    AbxGemm g, s2;
-    if (int rc = gemm_prepare(main_gemm, g)) return rc;
-    if (int rc = gemm_prepare(side_gemm, s2)) return rc;
-    int rc = 0;
-    static const bool off = getenv("ABX_NO_GEMM_SIDE") != nullptr;          // (A / B measurements: always the two launches)
-    if (!off && !abx_gemm_as_dispatch(g, &s2, st, &rc)) return rc;      // A-stationary walk: the side rides in the ragged last N-tile
-    // (plane output exists in the A-stationary kernel only: a caller asks for it when the launch qualifies - abx_gemm_planes_ok)
-    ABX_REQUIRE(g.c_planes_from == 0, "abx_gemm_side: c_planes_from is served by the A-stationary kernel only (>= 65 536 rows, K = 192, N % 128 == 64, "
-                                      "planes in groups of 48 from a multiple of 32, a side projection): ask abx_gemm_planes_ok first");
-    if (!off && !abx_gemm3_side_dispatch(g, s2, st, &rc)) return rc;
-    // not a (128 x 128 plain, skinny transposed) split-f16 pair: the two launches
-    if (int r1 = abx_gemm(main_gemm, st)) return r1;
-    return abx_gemm(side_gemm, st);
-}
-
-extern "C" int abx_gemm(const AbxGemm* gp, hipStream_t st) {
+// abx_gemm (plan == nullptr) / abx_gemm_plan: validate, then walk the dispatchers; the kernel is launched or named where it is chosen
+static int gemm_run(const AbxGemm* gp, hipStream_t st, AbxPlan* plan) {
     AbxGemm g;
     if (int rc = gemm_prepare(gp, g)) return rc;
     ABX_REQUIRE(g.c_planes_from == 0, "abx_gemm: c_planes_from is served through abx_gemm_side by the A-stationary kernel only (abx_gemm_planes_ok)");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    (void)al16;
     const bool akc = g.sAk == 1;
     if (g.exact != 1) {
         int rc = 0;
-        if (!abx_gemm_as_dispatch(g, nullptr, st, &rc)) return rc;
-        if (!abx_gemm3_dispatch(g, st, &rc)) return rc;
+        if (!abx_gemm_as_dispatch(g, nullptr, st, &rc, plan)) return rc;
+        if (!abx_gemm3_dispatch(g, st, &rc, plan)) return rc;
     }
     g.range_flag = nullptr;                 // exact fp32 products from here on: no operand range, a non-finite result is the input's
     ABX_REQUIRE(g.A && g.B, "abx_gemm: split-f16 operands given but the problem does not qualify for the split kernels "
@@ -557,23 +542,55 @@ extern "C" int abx_gemm(const AbxGemm* gp, hipStream_t st) {
     ABX_REQUIRE(!g.out_ln_w, "abx_gemm: out_ln is served by the split-f16 kernels only");
     ABX_REQUIRE(!g.mlp, "abx_gemm: the fused transition (mlp) is served by the split-f16 kernels only (exact = 2, K % 16 == 0)");
     const long long mt128 = ((long long)g.M + 127) / 128;
-    if (g.N <= 32) return launch_cfg<128, 32, 32, 32>(g, st);
-    if (g.N <= 64) return launch_cfg<128, 64, 32, 64>(g, st);
-    if (mt128 * (((long long)g.N + 127) / 128) * g.batch < 512) return launch_cfg<64, 64, 32, 32>(g, st);
+    if (g.N <= 32) return launch_cfg<128, 32, 32, 32>(g, st, plan);
+    if (g.N <= 64) return launch_cfg<128, 64, 32, 64>(g, st, plan);
+    if (mt128 * (((long long)g.N + 127) / 128) * g.batch < 512) return launch_cfg<64, 64, 32, 32>(g, st, plan);
     if (g.tune >> 1) {
         ABX_REQUIRE(!g.c_transposed && akc && g.sBn == 1, "abx_gemm: tuning variants exist for the plain weight GEMM only");
         switch (g.tune >> 1) {
-            case 1: return launch_main_variant<16, 2>(g, st);
-            case 2: return launch_main_variant<16, 4>(g, st);
-            case 3: return launch_cfg<128, 128, 64, 64, 16, 3>(g, st);
+            case 1: return launch_main_variant<16, 2>(g, st, plan);
+            case 2: return launch_main_variant<16, 4>(g, st, plan);
+            case 3: return launch_cfg<128, 128, 64, 64, 16, 3>(g, st, plan);
             default: break;
         }
     }
     // 128x192 tiles (96 accumulator registers per lane) when they waste no more columns than 128x128 tiles do: N = 192 (every
     // residual-stream update of the pair stack), 768 (q|k|v|gate, transition hidden), 544 ...
     const long long pad128 = ((g.N + 127) / 128) * 128, pad192 = ((g.N + 191) / 192) * 192;
-    if (pad192 <= pad128 && !(g.tune >> 1)) return launch_cfg<128, 192, 64, 96, 16, 2>(g, st);
-    return launch_cfg<128, 128, 64, 64>(g, st);
+    if (pad192 <= pad128 && !(g.tune >> 1)) return launch_cfg<128, 192, 64, 96, 16, 2>(g, st, plan);
+    return launch_cfg<128, 128, 64, 64>(g, st, plan);
+}
+
+// abx_gemm_side / abx_gemm_plan with a side.  In plan mode a pair that falls back to the two launches is named after its main launch.
+static int gemm_side_run(const AbxGemm* main_gemm, const AbxGemm* side_gemm, hipStream_t st, AbxPlan* plan) {
+    ABX_REQUIRE(main_gemm && side_gemm, "abx_gemm_side: null descriptor");
+    AbxGemm g, s2;
+    if (int rc = gemm_prepare(main_gemm, g)) return rc;
+    if (int rc = gemm_prepare(side_gemm, s2)) return rc;
+    int rc = 0;
+    static const bool off = getenv("ABX_NO_GEMM_SIDE") != nullptr;          // (A / B measurements: always the two launches)
+    if (!off && !abx_gemm_as_dispatch(g, &s2, st, &rc, plan)) return rc;      // A-stationary walk: the side rides in the ragged last N-tile
+    // (plane output exists in the A-stationary kernel only: a caller asks for it when the launch qualifies - abx_gemm_planes_ok)
+    ABX_REQUIRE(g.c_planes_from == 0, "abx_gemm_side: c_planes_from is served by the A-stationary kernel only (>= 65 536 rows, K = 192, N % 128 == 64, "
+                                      "planes in groups of 48 from a multiple of 32, a side projection): ask abx_gemm_planes_ok first");
+    if (!off && !abx_gemm3_side_dispatch(g, s2, st, &rc, plan)) return rc;
+    // not a (128 x 128 plain, skinny transposed) split-f16 pair: the two launches
+    if (int r1 = gemm_run(main_gemm, st, plan)) return r1;
+    return plan ? ABX_OK : gemm_run(side_gemm, st, nullptr);
+}
+
+extern "C" int abx_gemm(const AbxGemm* gp, hipStream_t st) { return gemm_run(gp, st, nullptr); }
+
+extern "C" int abx_gemm_side(const AbxGemm* main_gemm, const AbxGemm* side_gemm, hipStream_t st) {
+    return gemm_side_run(main_gemm, side_gemm, st, nullptr);
+}
+
+extern "C" int abx_gemm_plan(const AbxGemm* main_gemm, const AbxGemm* side_gemm, char* name, int cap) {
+    ABX_REQUIRE(name && cap > 0, "abx_gemm_plan: no room for the name");
+    AbxPlan plan = {};
+    if (int rc = side_gemm ? gemm_side_run(main_gemm, side_gemm, nullptr, &plan) : gemm_run(main_gemm, nullptr, &plan)) return rc;
+    snprintf(name, (size_t)cap, "%s", plan.name);
+    return ABX_OK;
 }
 
 extern "C" int abx_row_stats(const float* x, long long s_b, long long s_row, long long s_k, int batch, int rows, int K,
@@ -594,9 +611,8 @@ extern "C" int abx_row_stats(const float* x, long long s_b, long long s_row, lon
 extern "C" int abx_layernorm(const float* x, long long s_row, long long rows, int K, const float* gamma, const float* beta,
                              float eps, float* out, long long s_out, const float* res, long long s_res, hipStream_t st) {
     ABX_REQUIRE(x && out && gamma && beta && rows > 0 && K > 0, "abx_layernorm: bad args");
-    auto al16v = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (K == 128 && s_row % 4 == 0 && s_out % 4 == 0 && al16v(x) && al16v(out) && al16v(gamma) && al16v(beta) &&
-        (!res || (al16v(res) && s_res % 4 == 0))) {
+    if (K == 128 && s_row % 4 == 0 && s_out % 4 == 0 && al16(x) && al16(out) && al16(gamma) && al16(beta) &&
+        (!res || (al16(res) && s_res % 4 == 0))) {
         hipLaunchKernelGGL(layernorm128_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, st, x, s_row, rows, gamma, beta, eps,
                            out, s_out, res, s_res);
         return abx_check_launch("abx_layernorm");

@@ -1468,20 +1468,24 @@ __global__ __launch_bounds__(256, 1) void heads_tail_kernel(const AbxHeadsTail a
 }
 
 template <int BM, int BN, int WM, int WN, int MINW>
-int launch3(const AbxGemm& g, hipStream_t st) {
+int launch3(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
     const long long mt = ((long long)g.M + BM - 1) / BM, ntn = ((long long)g.N + BN - 1) / BN;
     dim3 grid((unsigned)(mt * ntn * g.batch), 1, 1), block(256);
 #ifdef ABX_PERSIST
     if ((g.tune & 256) && grid.x > 256u * MINW) grid.x = 256u * MINW;
 #endif
     const int amode = g.A_split ? 2 : (g.sAk == 1 ? 0 : 1);
+#define GEMM3_LAUNCH(AMODE, TS)                                                                                         \
+    ABX_LAUNCH(plan, ("gemm3_kernel<%d, %d, %d, %d, %d, %s, %d>", BM, BN, WM, WN, AMODE, ABX_BOOL(TS), MINW), "abx_gemm", \
+               (gemm3_kernel<BM, BN, WM, WN, AMODE, TS, MINW>), 0, grid, block, 0, st, g)
     if (g.c_transposed) {
         if (amode != 0) { abx_set_error("abx_gemm: transposed store needs a k-contiguous fp32 A"); return ABX_ERR_ARG; }
-        hipLaunchKernelGGL((gemm3_kernel<BM, BN, WM, WN, 0, true, MINW>), grid, block, 0, st, g);
-    } else if (amode == 0) hipLaunchKernelGGL((gemm3_kernel<BM, BN, WM, WN, 0, false, MINW>), grid, block, 0, st, g);
-    else if (amode == 1) hipLaunchKernelGGL((gemm3_kernel<BM, BN, WM, WN, 1, false, MINW>), grid, block, 0, st, g);
-    else hipLaunchKernelGGL((gemm3_kernel<BM, BN, WM, WN, 2, false, MINW>), grid, block, 0, st, g);
-    return abx_check_launch("abx_gemm");
+        return GEMM3_LAUNCH(0, true);
+    }
+    if (amode == 0) return GEMM3_LAUNCH(0, false);
+    if (amode == 1) return GEMM3_LAUNCH(1, false);
+    return GEMM3_LAUNCH(2, false);
+#undef GEMM3_LAUNCH
 }
 
 // fp32 weights -> k-tiled float16 planes [Kp/16][2][N][16] of w' = w * scale: p0 = f16(w'), p1 = f16(w' - p0) (AbxGemm.b_f16)
@@ -1502,14 +1506,13 @@ __global__ __launch_bounds__(256) void split_weights_f16_kernel(const float* __r
 
 // Called by abx_gemm (gemm.hip) once the descriptor has been validated and the vector flags filled.
 // Returns 1 when the problem is not served by this path (the caller falls back to the exact kernel).
-int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan) {
     // N <= 32 with split weights: the skinny projections of the pair stack (4 / 12 / 32 bias channels from 192- / 128-wide rows):
     // HBM streams of the A operand, served by a 128 x 32 tile of the same DMA pipeline (7 blocks per CU keep the stream fed)
     const bool narrow = g.B_split && g.N <= 32 && !g.A_split && g.sAk == 1 && !g.glu && !g.C_split && !g.A2 && !g.out_ln_w &&
                         g.a_pair_transpose <= 0 && g.pair_Lp == 0;
     if (!g.B_split || g.K % 16 != 0 || (g.N <= 64 && !narrow)) return 1;
-    if ((g.A_split != nullptr) == (g.b_f16 != 0) || g.b_exp < -100 || g.b_exp > 100 || g.b2_exp < -100 || g.b2_exp > 100) {
+    if ((g.A_split != nullptr) == (g.b_f16 != 0) || !exp_ok(g.b_exp) || !exp_ok(g.b2_exp)) {
         abx_set_error("abx_gemm: B_split must be float16 weight planes (abx_split_weights_f16, b_f16 = 1, |b_exp| <= 100) with an fp32 A "
                       "and activation images (b_f16 = 0) with A_split");
         *rc = ABX_ERR_ARG;
@@ -1518,15 +1521,15 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
     const long long mt128 = ((long long)g.M + 127) / 128;
     // exact == 2: the caller fixed the arithmetic class of this op (results must not depend on how many samples share a launch)
     if (g.exact != 2 && mt128 * (((long long)g.N + 127) / 128) * g.batch < ABX_SPLIT_MIN_TILES) return 1;
-    if (!al16(g.B_split) || g.sB3n % 8 != 0 || g.sB3p % 8 != 0 || g.sB3b % 8 != 0 || g.sB3k % 8 != 0) return 1;
+    if (!planes_ok(g.B_split, g.sB3n, g.sB3p, g.sB3k, g.sB3b)) return 1;
     if (g.A_split) {
-        if (!al16(g.A_split) || g.sA3m % 8 != 0 || g.sA3p % 8 != 0 || g.sA3b % 8 != 0 || g.sA3k % 8 != 0 || g.c_transposed) return 1;
+        if (!planes_ok(g.A_split, g.sA3m, g.sA3p, g.sA3k, g.sA3b) || g.c_transposed) return 1;
         if (g.batch_inner > 0 && (g.sA3i % 8 != 0 || g.sB3i % 8 != 0)) return 1;
     } else if (g.sAk == 1) {
-        if (!al16(g.A) || g.sAm % 4 != 0 || g.sAb % 4 != 0) return 1;
+        if (!rows_ok(g.A, g.sAm, g.sAb)) return 1;
         if (g.a_pair_transpose > 0 && !g.a_pair && (long long)g.a_pair_transpose * g.a_pair_transpose != g.M) return 1;
     } else {
-        if (!al16(g.A) || g.sAk % 4 != 0 || g.sAb % 4 != 0 || g.M % 4 != 0 || g.M < 4 || g.a_pair_transpose > 0) return 1;
+        if (!rows_ok(g.A, g.sAk, g.sAb) || g.M % 4 != 0 || g.M < 4 || g.a_pair_transpose > 0) return 1;
     }
     // 128x128 tiles run 3 blocks per CU (48 KB LDS, ~150 VGPRs), 128x192 tiles 2: the narrow tile wins whenever it wastes no
     // columns (N = 768: q|k|v|gate, transition hidden); N = 192 / 448 take the wide tile
@@ -1546,39 +1549,34 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
             return 0;
         }
         const long long mt = ((long long)g.M + 127) / 128;
-        hipLaunchKernelGGL((gemm3_oln_kernel<128, 128, 32, 128, 4>), dim3((unsigned)(mt * g.batch)), dim3(256), 0, st, g);
-        *rc = abx_check_launch("abx_gemm(out_ln)");
+        *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(out_ln)", (gemm3_oln_kernel<128, 128, 32, 128, 4>), 0, dim3((unsigned)(mt * g.batch)), dim3(256), 0, st, g);
         return 0;
     }
     if (g.mlp == 2) {
         // gated attention tail: out = (sigmoid(LN(A) B + bias) * gate) B2 + bias2 (+ resid)
         if (g.A_split || g.sAk != 1 || g.c_transposed || g.C_split || g.glu || g.A2 || g.out_ln_w || !g.B2_split || g.N2 <= 0 || g.N2 > 192 ||
             g.N % 16 != 0 || g.N > GT_NG || g.act != 2 || g.alpha != 1.0f || g.rowscale || !g.gate || !g.ln_csum || g.ln_stats || g.a_relu ||
-            g.a_pair_transpose > 0 || g.pair_Lp > 0 || !al16(g.B2_split) || g.sB23n % 8 != 0 || g.sB23p % 8 != 0 || g.sB23k % 8 != 0 ||
-            (long long)(g.N / 16) * g.sB23k >= (1LL << 31) || !al16(g.ln_csum) || (g.bias && !al16(g.bias)) || !al16(g.gate) || g.sGm % 4 != 0 ||
-            g.sGb % 4 != 0 || 128LL * g.sGm >= (1LL << 30)) {
+            g.a_pair_transpose > 0 || g.pair_Lp > 0 || !planes_ok(g.B2_split, g.sB23n, g.sB23p, g.sB23k) ||
+            (long long)(g.N / 16) * g.sB23k >= (1LL << 31) || !al16(g.ln_csum) || (g.bias && !al16(g.bias)) || !rows_ok(g.gate, g.sGm, g.sGb) ||
+            128LL * g.sGm >= (1LL << 30)) {
             abx_set_error("abx_gemm: mlp = 2 (gated tail) needs a k-contiguous fp32 A with folded LayerNorm, act = 2, a 16-byte aligned gate "
                           "operand [M][N], N % 16 == 0, N2 <= 192, plain store, B2_split planes in the permuted k order");
             *rc = ABX_ERR_ARG;
             return 0;
         }
         const long long mt = ((long long)g.M + 127) / 128;
-        if (g.tune & 64) {                                                   // tune bit 6: the two-walk form of round 5 (A / B runs, cross-check)
-            if (int e = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm3_gtail2w_kernel), GT_LDS, "abx_gemm(gated tail)")) { *rc = e; return 0; }
-            hipLaunchKernelGGL(gemm3_gtail2w_kernel, dim3((unsigned)(mt * g.batch)), dim3(256), GT_LDS, st, g);
-            *rc = abx_check_launch("abx_gemm(gated tail, two walks)");
-            return 0;
-        }
-        if (int e = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm3_gtail_kernel), GT1_LDS, "abx_gemm(gated tail)")) { *rc = e; return 0; }
-        hipLaunchKernelGGL(gemm3_gtail_kernel, dim3((unsigned)(mt * g.batch)), dim3(256), GT1_LDS, st, g);
-        *rc = abx_check_launch("abx_gemm(gated tail)");
+        const dim3 grid((unsigned)(mt * g.batch)), block(256);
+        if (g.tune & 64)                                                     // tune bit 6: the two-walk form of round 5 (A / B runs, cross-check)
+            *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(gated tail, two walks)", &gemm3_gtail2w_kernel, GT_LDS, grid, block, GT_LDS, st, g);
+        else
+            *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(gated tail)", &gemm3_gtail_kernel, GT1_LDS, grid, block, GT1_LDS, st, g);
         return 0;
     }
     if (g.mlp) {
         // fused two-layer transition: hidden = relu(LN(A) B + bias) never stored, out = hidden B2 + bias2 (+ resid)
         if (g.A_split || g.sAk != 1 || g.c_transposed || g.C_split || g.glu || g.A2 || g.out_ln_w || !g.B2_split || g.N2 <= 0 || g.N2 > 192 ||
             g.N % 16 != 0 || g.N > MLP_NH || g.act != 1 || g.alpha != 1.0f || g.rowscale || g.gate || !g.ln_csum || g.ln_stats || g.a_relu ||
-            g.a_pair_transpose > 0 || g.pair_Lp > 0 || !al16(g.B2_split) || g.sB23n % 8 != 0 || g.sB23p % 8 != 0 || g.sB23k % 8 != 0 ||
+            g.a_pair_transpose > 0 || g.pair_Lp > 0 || !planes_ok(g.B2_split, g.sB23n, g.sB23p, g.sB23k) ||
             (long long)(g.N / 16) * g.sB23k >= (1LL << 31) || !al16(g.ln_csum) || (g.bias && !al16(g.bias))) {
             abx_set_error("abx_gemm: mlp needs a k-contiguous fp32 A with folded LayerNorm, relu, N % 16 == 0, N <= 768, N2 <= 192, plain store, "
                           "B2_split planes in the permuted k order");
@@ -1586,18 +1584,16 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
             return 0;
         }
         const long long mt = ((long long)g.M + 127) / 128;
-        if ((g.tune >> 5) & 1) {                                                                                                   // benchmarking
-            if (int e = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm3_mlp3_kernel), MLP3_LDS, "abx_gemm(mlp)")) { *rc = e; return 0; }
-            hipLaunchKernelGGL(gemm3_mlp3_kernel, dim3((unsigned)(mt * g.batch)), dim3(256), MLP3_LDS, st, g);
-        } else if ((g.tune >> 4) & 1) hipLaunchKernelGGL(gemm3_mlp_kernel<1>, dim3((unsigned)(mt * g.batch)), dim3(256), 0, st, g);       // benchmarking
-        else hipLaunchKernelGGL(gemm3_mlp_kernel<2>, dim3((unsigned)(mt * g.batch)), dim3(256), 0, st, g);
-        *rc = abx_check_launch("abx_gemm(mlp)");
+        const dim3 grid((unsigned)(mt * g.batch)), block(256);
+        if ((g.tune >> 5) & 1) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp3_kernel, MLP3_LDS, grid, block, MLP3_LDS, st, g);     // benchmarking
+        else if ((g.tune >> 4) & 1) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp_kernel<1>, 0, grid, block, 0, st, g);         // benchmarking
+        else *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp_kernel<2>, 0, grid, block, 0, st, g);
         return 0;
     }
     if (g.A2) {
         // dual GEMM: 128 x 96 tiles (two accumulator sets of 48 registers)
-        if (g.A_split || g.c_transposed || g.glu || !g.B2_split || g.K2 % 16 != 0 || !al16(g.A2) || g.sA2m % 4 != 0 || g.sA2b % 4 != 0 ||
-            !al16(g.B2_split) || g.sB23n % 8 != 0 || g.sB23p % 8 != 0 || g.sB23k % 8 != 0 || !g.ln2_csum ||
+        if (g.A_split || g.c_transposed || g.glu || !g.B2_split || g.K2 % 16 != 0 || !rows_ok(g.A2, g.sA2m, g.sA2b) ||
+            !planes_ok(g.B2_split, g.sB23n, g.sB23p, g.sB23k) || !g.ln2_csum ||
             (g.pair_Lp > 0 ? (long long)g.pair_L * g.pair_L * g.sA2m : 128LL * g.sA2m) >= (1LL << 30) ||
             (long long)(g.K2 / 16) * g.sB23k >= (1LL << 31)) {
             abx_set_error("abx_gemm: dual (A2 / B2_split) operands do not qualify for the split-f16 dual kernel");
@@ -1612,10 +1608,10 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
         // tune bit 7 (round 6 probe, 96 < N <= 192): one block per row tile, z walked once (gemm3_dual1_kernel) - bit-identical, but its 96 kept
         // gate registers + 48 accumulators leave two blocks per CU instead of three (256 VGPRs, 7 spilled): 10.97 vs 10.30 ms at 100 samples
         // (profiles/r06c_kb_dual.txt); NOT the default
-        if (g.N > 96 && g.N <= 192 && (g.tune & 128)) hipLaunchKernelGGL(gemm3_dual1_kernel, dim3((unsigned)(mt * g.batch)), dim3(256), 0, st, g);
-        else if (g.tune & 1024) hipLaunchKernelGGL((gemm3_dual_kernel<128, 96, 32, 96, 4>), dim3((unsigned)(mt * ntn * g.batch)), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((gemm3_dual_kernel<128, 96, 32, 96, 3>), dim3((unsigned)(mt * ntn * g.batch)), dim3(256), 0, st, g);
-        *rc = abx_check_launch("abx_gemm(dual)");
+        const dim3 grid((unsigned)(mt * ntn * g.batch)), block(256);
+        if (g.N > 96 && g.N <= 192 && (g.tune & 128)) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", &gemm3_dual1_kernel, 0, dim3((unsigned)(mt * g.batch)), block, 0, st, g);
+        else if (g.tune & 1024) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", (gemm3_dual_kernel<128, 96, 32, 96, 4>), 0, grid, block, 0, st, g);
+        else *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", (gemm3_dual_kernel<128, 96, 32, 96, 3>), 0, grid, block, 0, st, g);
         return 0;
     }
     if (narrow) {
@@ -1623,14 +1619,15 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
         dim3 grid((unsigned)(mt * g.batch), 1, 1), block(256);
         if ((g.tune >> 9) & 3) {                                     // probe: deeper ring (1: 3 stages at 4 blocks per CU, 2: 4 stages at 3)
             const int v = (g.tune >> 9) & 3;
-            if (g.c_transposed) { if (v == 1) hipLaunchKernelGGL((gemm3_narrow_ring_kernel<true, 3, 4>), grid, block, 0, st, g); else hipLaunchKernelGGL((gemm3_narrow_ring_kernel<true, 4, 3>), grid, block, 0, st, g); }
-            else { if (v == 1) hipLaunchKernelGGL((gemm3_narrow_ring_kernel<false, 3, 4>), grid, block, 0, st, g); else hipLaunchKernelGGL((gemm3_narrow_ring_kernel<false, 4, 3>), grid, block, 0, st, g); }
-            *rc = abx_check_launch("abx_gemm(narrow, ring)");
+            const char* what = "abx_gemm(narrow, ring)";
+            if (g.c_transposed && v == 1) *rc = ABX_LAUNCH_LIT(plan, what, (gemm3_narrow_ring_kernel<true, 3, 4>), 0, grid, block, 0, st, g);
+            else if (g.c_transposed) *rc = ABX_LAUNCH_LIT(plan, what, (gemm3_narrow_ring_kernel<true, 4, 3>), 0, grid, block, 0, st, g);
+            else if (v == 1) *rc = ABX_LAUNCH_LIT(plan, what, (gemm3_narrow_ring_kernel<false, 3, 4>), 0, grid, block, 0, st, g);
+            else *rc = ABX_LAUNCH_LIT(plan, what, (gemm3_narrow_ring_kernel<false, 4, 3>), 0, grid, block, 0, st, g);
             return 0;
         }
-        if (g.c_transposed) hipLaunchKernelGGL((gemm3_kernel<128, 32, 32, 32, 0, true, 6>), grid, block, 0, st, g);
-        else hipLaunchKernelGGL((gemm3_kernel<128, 32, 32, 32, 0, false, 6>), grid, block, 0, st, g);
-        *rc = abx_check_launch("abx_gemm(narrow)");
+        if (g.c_transposed) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(narrow)", (gemm3_kernel<128, 32, 32, 32, 0, true, 6>), 0, grid, block, 0, st, g);
+        else *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(narrow)", (gemm3_kernel<128, 32, 32, 32, 0, false, 6>), 0, grid, block, 0, st, g);
         return 0;
     }
     const long long pad128 = ((g.N + 127) / 128) * 128, pad192 = ((g.N + 191) / 192) * 192;
@@ -1644,19 +1641,18 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
     // in the same order (same MFMA, same term order, same row statistics), so the tile choice does not change a single bit and
     // results stay independent of how many samples share a launch.
     const long long ntn128 = ((long long)g.N + 127) / 128;
-    if (!wide && !g.glu && !force && mt128 * ntn128 * g.batch < 384 && g.M > 64) *rc = launch3<64, 128, 32, 64, 4>(g, st);
-    else if (wide) *rc = launch3<128, 192, 32, 192, 3>(g, st);
-    else *rc = launch3<128, 128, 32, 128, 4>(g, st);
+    if (!wide && !g.glu && !force && mt128 * ntn128 * g.batch < 384 && g.M > 64) *rc = launch3<64, 128, 32, 64, 4>(g, st, plan);
+    else if (wide) *rc = launch3<128, 192, 32, 192, 3>(g, st, plan);
+    else *rc = launch3<128, 128, 32, 128, 4>(g, st, plan);
     return 0;
 }
 
 // abx_gemm_side (gemm.hip): both descriptors validated and their vector flags filled.  Returns 1 when the pair is not served by
 // the side kernel (the caller then issues two launches).
-int abx_gemm3_side_dispatch(const AbxGemm& g, const AbxGemm& s2, hipStream_t st, int* rc) {
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+int abx_gemm3_side_dispatch(const AbxGemm& g, const AbxGemm& s2, hipStream_t st, int* rc, AbxPlan* plan) {
     auto plain_a = [&](const AbxGemm& d) {
-        return d.B_split && d.b_f16 && !d.A_split && d.A && d.sAk == 1 && d.K % 16 == 0 && al16(d.A) && d.sAm % 4 == 0 && d.sAb % 4 == 0 &&
-               al16(d.B_split) && d.sB3n % 8 == 0 && d.sB3p % 8 == 0 && d.sB3k % 8 == 0 && d.sB3b % 8 == 0 && d.b_exp >= -100 && d.b_exp <= 100 &&
+        return d.B_split && d.b_f16 && !d.A_split && d.A && d.sAk == 1 && d.K % 16 == 0 && rows_ok(d.A, d.sAm, d.sAb) &&
+               planes_ok(d.B_split, d.sB3n, d.sB3p, d.sB3k, d.sB3b) && exp_ok(d.b_exp) &&
                !d.glu && !d.C_split && !d.A2 && !d.out_ln_w && !d.mlp && d.a_pair_transpose <= 0 && d.pair_Lp == 0 && d.batch_inner == 0 &&
                128LL * d.sAm < (1LL << 30) && (long long)(d.K / 16) * d.sB3k < (1LL << 31) && d.exact != 1;
     };
@@ -1665,8 +1661,7 @@ int abx_gemm3_side_dispatch(const AbxGemm& g, const AbxGemm& s2, hipStream_t st,
     if (!s2.c_transposed || s2.N > 32) return 1;                                      // side: the 128 x 32 transposed-store tile
     const long long tq = ((long long)g.M + 127) / 128 * (g.N / 128) * g.batch, ts = ((long long)s2.M + 127) / 128 * s2.batch;
     if (tq < 384 || ts <= 0 || ts > tq || tq + ts >= (1LL << 31)) return 1;           // (small problems keep their own tile choice)
-    hipLaunchKernelGGL(gemm3_side_kernel, dim3((unsigned)(tq + ts)), dim3(256), 0, st, g, s2);
-    *rc = abx_check_launch("abx_gemm_side");
+    *rc = ABX_LAUNCH_LIT(plan, "abx_gemm_side", &gemm3_side_kernel, 0, dim3((unsigned)(tq + ts)), dim3(256), 0, st, g, s2);
     return 0;
 }
 

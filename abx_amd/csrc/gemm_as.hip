@@ -1026,8 +1026,7 @@ __global__ __launch_bounds__(256, 2) void gemm_as_dual_kernel(const AbxGemm g) {
 }
 
 // The dual descriptor of the TriangleMultiplication tail -> gemm_as_dual_kernel.  Returns 1 when the tile kernel (gemm3_dual_kernel) keeps it.
-int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan) {
     static const bool off = [] {
         const char* e = getenv("ABX_NO_DUAL_AS");               // (A / B measurements: the tile kernel everywhere)
         return e != nullptr && !(e[0] == '0' && e[1] == 0);
@@ -1048,10 +1047,10 @@ int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
         return g.C < p1 && p < c1;
     };
     if (overlaps(g.A2, g.sA2b, g.sA2m) || overlaps(g.resid, g.sRb, g.sRm)) return 1;
-    if (!al16(g.A) || g.sAk % 4 != 0 || g.sAb % 4 != 0 || !al16(g.A2) || g.sA2m % 4 != 0 || g.sA2b % 4 != 0) return 1;
-    if (!al16(g.B_split) || g.sB3n % 8 != 0 || g.sB3p % 8 != 0 || g.sB3k % 8 != 0 || g.sB3b % 8 != 0) return 1;
-    if (!al16(g.B2_split) || g.sB23n % 8 != 0 || g.sB23p % 8 != 0 || g.sB23k % 8 != 0) return 1;
-    if (g.b_exp < -100 || g.b_exp > 100 || g.b2_exp < -100 || g.b2_exp > 100) return 1;
+    if (!rows_ok(g.A, g.sAk, g.sAb) || !rows_ok(g.A2, g.sA2m, g.sA2b)) return 1;
+    if (!planes_ok(g.B_split, g.sB3n, g.sB3p, g.sB3k, g.sB3b)) return 1;
+    if (!planes_ok(g.B2_split, g.sB23n, g.sB23p, g.sB23k)) return 1;
+    if (!exp_ok(g.b_exp) || !exp_ok(g.b2_exp)) return 1;
     // 32-bit per-lane DMA offsets: the z rows (from the batch base under the pair-row map), the product columns, the weight planes
     if ((g.pair_Lp > 0 ? (long long)g.pair_L * g.pair_L * g.sA2m : 64LL * g.sA2m) >= (1LL << 30)) return 1;
     if (16LL * g.sAk + g.M >= (1LL << 30)) return 1;
@@ -1062,12 +1061,7 @@ int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
     // the launch-size rule of the walk below (and its INVARIANT: bit-identical to the tile kernel, test_gpu_tri_mul_tail_as.py);
     // tune bit 14 forces the kernel on an eligible shape of any size
     if (!(g.tune & 16384) && ntm * g.batch < 1024) return 1;
-    if (int e = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm_as_dual_kernel), AD_LDS, "abx_gemm(as, dual)")) {
-        *rc = e;
-        return 0;
-    }
-    hipLaunchKernelGGL(gemm_as_dual_kernel, dim3((unsigned)(ntm * g.batch)), dim3(256), AD_LDS, st, g);
-    *rc = abx_check_launch("abx_gemm(as, dual)");
+    *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(as, dual)", &gemm_as_dual_kernel, AD_LDS, dim3((unsigned)(ntm * g.batch)), dim3(256), AD_LDS, st, g);
     return 0;
 }
 
@@ -1075,16 +1069,15 @@ int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc) {
 
 // Called by abx_gemm / abx_gemm_side (gemm.hip) with validated descriptors (vector flags filled).  side == nullptr: no side GEMM.
 // Returns 1 when the problem is not served here (the caller goes on to the tile kernels of gemm3.hip).
-int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, int* rc) {
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, int* rc, AbxPlan* plan) {
     static const bool off = getenv("ABX_NO_GEMM_AS") != nullptr;          // (A / B measurements: always the tile kernels)
     if (off || (g.tune & 2048)) return 1;                       // tune bit 11: the tile kernels for this call
-    if (g.A2) return side ? 1 : as_dual_dispatch(g, st, rc);    // the TriangleMultiplication tail
+    if (g.A2) return side ? 1 : as_dual_dispatch(g, st, rc, plan);    // the TriangleMultiplication tail
     if (g.exact == 1 || !g.B_split || !g.b_f16 || g.A_split || !g.A || g.sAk != 1 || g.K != AS_NK * 16) return 1;
     if (g.A2 || g.out_ln_w || g.mlp || g.ln_stats || g.gate || g.resid || g.batch_inner || !g.ln_csum || !g.bias) return 1;
     if (g.act != 0 || g.alpha != 1.0f) return 1;
-    if (!al16(g.A) || g.sAm % 4 != 0 || g.sAb % 4 != 0 || !al16(g.B_split) || g.sB3n % 8 != 0 || g.sB3p % 8 != 0 || g.sB3k % 8 != 0) return 1;
-    if (g.b_exp < -100 || g.b_exp > 100) return 1;
+    if (!rows_ok(g.A, g.sAm, g.sAb) || !planes_ok(g.B_split, g.sB3n, g.sB3p, g.sB3k)) return 1;
+    if (!exp_ok(g.b_exp)) return 1;
     if (((g.a_pair_transpose > 0 || g.a_pair) ? (long long)g.M * g.sAm : 64LL * g.sAm) >= (1LL << 30)) return 1;
     if ((long long)(g.K / 16) * g.sB3k >= (1LL << 31)) return 1;
     const long long ntm = ((long long)g.M + AS_BM - 1) / AS_BM;
@@ -1113,33 +1106,28 @@ int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, 
                 s.exact == 1 || (long long)s.M * s.batch != (long long)g.M || (s.batch > 1 && s.sAb != (long long)s.M * s.sAm) ||
                 (s.ln_csum == nullptr) != (g.ln_csum == nullptr) || s.ln_stats || s.gate || s.resid || s.rowscale || s.act != 0 || s.glu || s.C_split ||
                 s.A2 || s.out_ln_w || s.mlp || s.a_pair_transpose > 0 || s.pair_Lp != 0 || s.a_relu != g.a_relu ||
-                !al16(s.B_split) || s.sB3n % 8 != 0 || s.sB3p % 8 != 0 || s.sB3k % 8 != 0 || s.b_exp < -100 || s.b_exp > 100 ||
+                !planes_ok(s.B_split, s.sB3n, s.sB3p, s.sB3k) || !exp_ok(s.b_exp) ||
                 (long long)(s.K / 16) * s.sB3k >= (1LL << 31) || (g.ln_csum && s.ln_eps != g.ln_eps))
                 return 1;
         }
     }
     static const AbxGemm none = {};
     const dim3 grid((unsigned)(ntm * g.batch)), block(256);
-#define AS_LAUNCH(EPI, SIDE, ABL, ...)                                                                                                   \
-    do {                                                                                                                                 \
-        if (int e = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm_as_kernel<EPI, SIDE, ABL, ##__VA_ARGS__>), AS_LDS, "abx_gemm(as)")) { \
-            *rc = e;                                                                                                                     \
-            return 0;                                                                                                                    \
-        }                                                                                                                                \
-        hipLaunchKernelGGL((gemm_as_kernel<EPI, SIDE, ABL, ##__VA_ARGS__>), grid, block, AS_LDS, st, g, side ? *side : none);            \
-    } while (0)
+// (PL: plane output of the columns from c_planes_from on; the name spells the template's default out)
+#define AS_LAUNCH(EPI, SIDE, ABL, PL)                                                                                                     \
+    ABX_LAUNCH(plan, ("gemm_as_kernel<%d, %s, %d, %s>", EPI, ABX_BOOL(SIDE), ABL, ABX_BOOL(PL)), "abx_gemm(as)", (gemm_as_kernel<EPI, SIDE, ABL, PL>), \
+               AS_LDS, grid, block, AS_LDS, st, g, side ? *side : none)
 #ifdef ABX_AS_ABLATE
     const int abl = (g.tune >> 12) & 3;
-    if (abl == 1) { if (glu) AS_LAUNCH(AS_EPI_GLU, false, 1); else if (side) AS_LAUNCH(AS_EPI_PLAIN, true, 1); else AS_LAUNCH(AS_EPI_PLAIN, false, 1); }
-    else if (abl == 2) { if (glu) AS_LAUNCH(AS_EPI_GLU, false, 2); else if (side) AS_LAUNCH(AS_EPI_PLAIN, true, 2); else AS_LAUNCH(AS_EPI_PLAIN, false, 2); }
-    else if (abl == 3) { if (glu) AS_LAUNCH(AS_EPI_GLU, false, 3); else if (side) AS_LAUNCH(AS_EPI_PLAIN, true, 3); else AS_LAUNCH(AS_EPI_PLAIN, false, 3); }
+    if (abl == 1) *rc = glu ? AS_LAUNCH(AS_EPI_GLU, false, 1, false) : side ? AS_LAUNCH(AS_EPI_PLAIN, true, 1, false) : AS_LAUNCH(AS_EPI_PLAIN, false, 1, false);
+    else if (abl == 2) *rc = glu ? AS_LAUNCH(AS_EPI_GLU, false, 2, false) : side ? AS_LAUNCH(AS_EPI_PLAIN, true, 2, false) : AS_LAUNCH(AS_EPI_PLAIN, false, 2, false);
+    else if (abl == 3) *rc = glu ? AS_LAUNCH(AS_EPI_GLU, false, 3, false) : side ? AS_LAUNCH(AS_EPI_PLAIN, true, 3, false) : AS_LAUNCH(AS_EPI_PLAIN, false, 3, false);
     else
 #endif
-    if (glu) AS_LAUNCH(AS_EPI_GLU, false, 0);
-    else if (side && g.c_planes_from > 0) AS_LAUNCH(AS_EPI_PLAIN, true, 0, true);
-    else if (side) AS_LAUNCH(AS_EPI_PLAIN, true, 0);
-    else AS_LAUNCH(AS_EPI_PLAIN, false, 0);
+    if (glu) *rc = AS_LAUNCH(AS_EPI_GLU, false, 0, false);
+    else if (side && g.c_planes_from > 0) *rc = AS_LAUNCH(AS_EPI_PLAIN, true, 0, true);
+    else if (side) *rc = AS_LAUNCH(AS_EPI_PLAIN, true, 0, false);
+    else *rc = AS_LAUNCH(AS_EPI_PLAIN, false, 0, false);
 #undef AS_LAUNCH
-    *rc = abx_check_launch("abx_gemm(as)");
     return 0;
 }

@@ -172,7 +172,6 @@ __global__ __launch_bounds__(256, 3) void opm_out_kernel(const float* __restrict
 extern "C" int abx_opm_out_fwd(const float* lr, long long ld, const float* Wt, const float* bias, float* z, int B, int L, int* range_flag,
                                int range_tag, hipStream_t st) {
     ABX_REQUIRE(lr && Wt && z && B > 0 && L > 0, "abx_opm_out_fwd: bad args");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     ABX_REQUIRE(al16(lr) && al16(z) && ld % 4 == 0 && ld >= 2 * OPM_C, "abx_opm_out_fwd: lr rows of [left 64 | right 64] floats, 16-byte aligned");
     ABX_REQUIRE((long long)B * L < (1LL << 31), "abx_opm_out_fwd: grid too large");
     if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(opm_out_kernel), OPM_LDS, "abx_opm_out_fwd")) return rc;

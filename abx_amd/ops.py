@@ -86,69 +86,61 @@ GEMM_EXACT = False   # True: every GEMM on the exact fp32 MFMA kernel (v_mfma_f3
                      # split-f16 kernels of csrc/gemm3.hip (fp32-accurate)
 
 
+def _plan_name(fn, *args):
+    """(return code, kernel name) of abx_gemm_plan / abx_tri_attn_plan: the library's own dispatch run up to the launch.  Needs no GPU."""
+    buf = C.create_string_buffer(128)
+    rc = fn(*args, buf, len(buf))
+    return rc, buf.value.decode()
+
+
+def _placeholders():
+    """Stand-in device addresses for a descriptor that is only planned: non-null, 16-byte aligned, 1 TiB apart (disjoint for any tensor).
+    The library looks at their alignment and overlap and never follows them."""
+    return iter(range(1 << 40, 1 << 62, 1 << 40))
+
+
 def gemm_kernel_name(M, N, K, batch, a_kcontig=True, b_ncontig=True, transposed=False, split=False, exact=None, a_split=False, dual=False, out_ln=False):
-    """Name of the kernel instantiation abx_gemm launches for a problem (mirror of the selection in csrc/gemm.hip and
-    csrc/gemm3.hip); used by bench.py to aggregate per KERNEL exactly like `rocprofv3 --stats` does."""
-    b = lambda x: 'true' if x else 'false'
-    if dual:
-        # the tri-mul tail (K2 = 192 gate rows next to the K = 128 channel-major product): from 1 024 blocks of 64 rows on the A-stationary
-        # dual kernel of csrc/gemm_as.hip (mirror of as_dual_dispatch; GEMM_TUNE bit 11 keeps the tile kernel, bit 14 forces the new one)
-        tune = GEMM_TUNE or 0
-        if (not GEMM_EXACT and int(exact or 0) != 1 and not (tune & 2048) and N == 192 and K == 128 and not a_kcontig and M % 4 == 0
-                and not transposed and split and (((M + 63) // 64) * batch >= 1024 or (tune & 16384))):
-            return 'gemm_as_dual_kernel'
-        return 'gemm3_dual_kernel<128, 96, 32, 96, 3>'
-    if out_ln:
-        return 'gemm3_oln_kernel<128, 128, 32, 128, 4>'
-    exact = 1 if GEMM_EXACT else int(exact or 0)
-    blocks128 = ((M + 127) // 128) * ((N + 127) // 128) * batch
-    wide192 = ((N + 191) // 192) * 192 <= ((N + 127) // 128) * 128
-    if exact != 1 and split and N <= 32 and a_kcontig and not a_split and K % 16 == 0:
-        return f'gemm3_kernel<128, 32, 32, 32, 0, {b(transposed)}, 6>'
-    if exact != 1 and split and N > 64 and (blocks128 >= 256 or exact == 2) and K % 16 == 0 and (a_kcontig or a_split or M % 4 == 0):
-        amode = 2 if a_split else (0 if a_kcontig else 1)
-        pad128, pad192 = ((N + 127) // 128) * 128, ((N + 191) // 192) * 192
-        wide = pad192 <= pad128 if a_split else (wide192 and N % 128 != 0)
-        cfg = (128, 192, 32, 192, 3) if wide else (128, 128, 32, 128, 4)
-        if not wide and blocks128 < 384 and M > 64:
-            cfg = (64, 128, 32, 64, 4)
-        return f'gemm3_kernel<{cfg[0]}, {cfg[1]}, {cfg[2]}, {cfg[3]}, {amode}, {b(transposed)}, {cfg[4]}>'
-    if N <= 32:
-        cfg = (128, 32, 32, 32, 3)
-    elif N <= 64:
-        cfg = (128, 64, 32, 64, 3)
-    elif blocks128 < 512:
-        cfg = (64, 64, 32, 32, 3)
-    elif wide192:
-        cfg = (128, 192, 64, 96, 2)
+    """Name of the kernel instantiation abx_gemm launches for a problem, as `rocprofv3 --stats` spells it; used by bench.py to aggregate per
+    KERNEL.  The answer is the library's (abx_gemm_plan: the dispatch of csrc/gemm.hip, gemm3.hip and gemm_as.hip itself, environment
+    switches and GEMM_TUNE included) for a descriptor of dense tensors of this shape at placeholder addresses: fp32 A (k- or m-contiguous) and
+    B, weight planes with `split`, operand images on both sides with `a_split`, no epilogue operands; `dual`: the tri-mul tail (K2 = 192 gate
+    rows, both LayerNorms folded, residual); `out_ln`: the output LayerNorm."""
+    P = _placeholders()
+    g = AbxGemm()
+    g.M, g.N, g.K, g.batch = M, N, K, batch
+    g.exact, g.tune, g.alpha = (1 if GEMM_EXACT else int(exact or 0)), GEMM_TUNE, 1.0
+    KT = (K + 15) // 16
+    if a_split:
+        g.A_split, g.sA3m, g.sA3p, g.sA3k, g.sA3b = next(P), 16, 16 * M, 32 * M, (KT * 32 * M if batch > 1 else 0)
+        g.B_split, g.sB3n, g.sB3p, g.sB3k, g.sB3b = next(P), 16, 16 * N, 32 * N, (KT * 32 * N if batch > 1 else 0)
     else:
-        cfg = (128, 128, 64, 64, 3)
-    return f'gemm_kernel<{cfg[0]}, {cfg[1]}, {cfg[2]}, {cfg[3]}, 16, {b(a_kcontig)}, {b(b_ncontig)}, {b(transposed)}, {cfg[4]}>'
+        g.A, g.sAb = next(P), (M * K if batch > 1 else 0)
+        g.sAm, g.sAk = (K, 1) if a_kcontig else (1, M)
+        g.B, g.sBb = next(P), (K * N if batch > 1 else 0)
+        g.sBk, g.sBn = (N, 1) if b_ncontig else (1, K)
+        if split:
+            g.B_split, g.sB3n, g.sB3p, g.sB3k, g.b_f16 = next(P), 16, 16 * N, 32 * N, 1
+    g.C, g.sCb, g.c_transposed, g.sCm = next(P), (M * N if batch > 1 else 0), int(bool(transposed)), (M if transposed else N)
+    if dual:
+        g.A2, g.K2, g.sA2m, g.sA2b = next(P), 192, 192, (M * 192 if batch > 1 else 0)
+        g.B2_split, g.sB23n, g.sB23p, g.sB23k = next(P), 16, 16 * N, 32 * N
+        g.ln_csum, g.bias, g.ln2_csum, g.bias2, g.ln_eps = next(P), next(P), next(P), next(P), 1e-5
+        g.resid, g.sRb, g.sRm = next(P), g.sCb, g.sCm
+    if out_ln:
+        g.out_ln_w, g.out_ln_b = next(P), next(P)
+    rc, name = _plan_name(_lib.load().abx_gemm_plan, C.byref(g), None)
+    if rc and dual:       # no launch to name (the exact fp32 kernels have no dual form; M % 4 with a channel-major product): the tile kernel's
+        return 'gemm3_dual_kernel<128, 96, 32, 96, 3>'
+    check(rc, 'abx_gemm_plan')
+    return name
 
 
 def gemm_as_kernel_name(g, side=None):
     """Name of the A-stationary kernel instantiation (csrc/gemm_as.hip) that abx_gemm / abx_gemm_side launch for a filled descriptor, or
-    None when the problem goes to the tile kernels (mirror of abx_gemm_as_dispatch; alignment is taken for granted: the tensors of
-    model/forward.py are 16-byte aligned)."""
-    if GEMM_EXACT or (g.tune & 2048) or g.exact == 1 or not g.B_split or not g.b_f16 or g.A_split or not g.A or g.sAk != 1 or g.K != 192:
-        return None
-    if g.A2 or g.out_ln_w or g.mlp or g.ln_stats or g.gate or g.resid or g.batch_inner or not g.ln_csum or not g.bias or g.act != 0 or g.alpha != 1.0:
-        return None
-    ntm = (g.M + 63) // 64
-    if g.N < 256 or ntm * g.batch < 1024:
-        return None
-    if g.glu:
-        if side is not None or not g.C_split or not g.c_split_tile or not g.c_transposed or g.N % 128 != 0 or not g.a_pair or g.pair_Lp <= 0:
-            return None
-        return 'gemm_as_kernel<1, false, 0, false>'
-    if g.c_transposed or g.C_split or g.rowscale or g.a_pair_transpose > 0 or g.pair_Lp != 0 or g.batch != 1 or g.N % 64 != 0:
-        return None
-    if side is not None:
-        s2 = side
-        if g.N % 128 != 64 or not s2.B_split or not s2.c_transposed or s2.N > 32 or s2.K != g.K or s2.M * s2.batch != g.M or s2.act != 0 or s2.exact == 1:
-            return None
-        return 'gemm_as_kernel<0, true, 0, true>' if g.c_planes_from > 0 else 'gemm_as_kernel<0, true, 0, false>'
-    return 'gemm_as_kernel<0, false, 0, false>'
+    None when the problem goes to the tile kernels - or is the dual GEMM, which gemm_kernel_name names (abx_gemm_plan on the descriptors
+    themselves: alignment, switches and tune bits count as they do for the launch)."""
+    rc, name = _plan_name(_lib.load().abx_gemm_plan, C.byref(g), None if side is None else C.byref(side))
+    return name if rc == 0 and name.startswith('gemm_as_kernel') else None
 
 
 SPLIT_MIN_L = 64
@@ -162,9 +154,8 @@ def gemm_mode(L):
 
 
 def gemm_split_eligible(M, N, K, batch=1):
-    """True when abx_gemm serves an (aligned) problem of this size on the split-f16 kernels (mirror of
-    abx_gemm3_dispatch in csrc/gemm3.hip)."""
-    return (not GEMM_EXACT) and N > 64 and K % 16 == 0 and ((M + 127) // 128) * ((N + 127) // 128) * batch >= 256
+    """True when abx_gemm serves an (aligned) problem of this size on the split-f16 kernels of csrc/gemm3.hip (gemm_kernel_name)."""
+    return gemm_kernel_name(M, N, K, batch, split=True).startswith('gemm3_')
 
 
 def pack_glu_weights(Wv, Wg, bv=None, bg=None):
@@ -613,24 +604,32 @@ _TRI_ATTN_LAST = None       # (L, exact, row-fused) of the most recent tri_attn 
 
 
 def tri_attn_kernel_name(L, exact=None, bias_vec=True, rowfused=None):
-    """Name of the kernel the triangle attention of a row of length L runs on (mirror of the selection in csrc/attention.hip), for
-    per-kernel aggregation.  rowfused: True = tri_attn on the z rows with a row pack (abx_tri_attn_rowfused_fwd), False = tri_attn on projected
+    """Name of the kernel the triangle attention of a row of length L runs on, for per-kernel aggregation: the library's answer
+    (abx_tri_attn_plan, the dispatch of csrc/attention.hip itself) for one sample in the model's row layout - projected q | k | v rows 576 wide,
+    4 heads, key-contiguous bias rows padded to 4 floats (bias_vec=False: query-contiguous, unpadded).
+    rowfused: True = tri_attn on the z rows with a row pack (abx_tri_attn_rowfused_fwd), False = tri_attn on projected
     q | k | v rows (abx_tri_attn_fwd); None = whatever the most recent tri_attn call of this (L, exact) launched - the caller that times a
     launch asks right behind it - and, with no such call, what the model path does for a complex of this length: the fused kernel when the
     library admits L (abx_tri_attn_rowfused_ok: a function of L and of the ABX_NO_TRI_ROWFUSED switch, read on the C side only), the GEMMs
     of the pass are the split-f16 ones (gemm_mode) and the k | v operand images are off."""
     ex = bool(GEMM_EXACT if exact is None else exact)
-    if ex:
-        return 'tri_attn_kernel'
     if rowfused is None:
         if _TRI_ATTN_LAST is not None and _TRI_ATTN_LAST[:2] == (int(L), ex):
             rowfused = _TRI_ATTN_LAST[2]
         else:
-            rowfused = _tri_rowfused_ok(L) and gemm_mode(L) == 2 and not KV_PLANES
-    if rowfused:
-        return 'tri_attn8_rowfused_kernel'
-    kc = 128 if (L + 127) // 128 == (L + 191) // 192 else 192
-    return 'tri_attn8_kernel<%d, 768, %s>' % (kc, 'true' if bias_vec else 'false')
+            rowfused = not ex and _tri_rowfused_ok(L) and gemm_mode(L) == 2 and not KV_PLANES
+    P = _placeholders()
+    H, D, W, Lp = 4, 48, 576, ((L + 3) // 4 * 4 if bias_vec else L)
+    a = AbxTriAttn()
+    base = next(P)
+    a.q, a.k, a.v, a.sb, a.ss, a.sl = base, base + 4 * H * D, base + 8 * H * D, L * L * W, L * W, W
+    a.bias, a.bias_sb, a.bias_sh = next(P), H * L * Lp, L * Lp
+    a.bias_sq, a.bias_sk = (Lp, 1) if bias_vec else (1, L)
+    a.out, a.ob, a.os, a.ol = next(P), L * L * H * D, L * H * D, H * D
+    a.B, a.S, a.L, a.H, a.D, a.exact = 1, L, L, H, D, int(ex)
+    rc, name = _plan_name(_lib.load().abx_tri_attn_plan, C.byref(a), int(bool(rowfused)))
+    check(rc, 'abx_tri_attn_plan')
+    return name
 
 
 # float(log2 e) * 2^7 (include/abx_hip.h ABX_TRI_BIAS_LOG2): the factor the pair-bias projection applies (gemm(..., alpha=)) when the attention

@@ -268,6 +268,12 @@ int abx_heads_tail(const AbxHeadsTail* desc, hipStream_t stream);
 /* diagnostics: resident workgroups per CU of the main split-f16 GEMM instantiations (0: 128x192, 1: 128x128,
  * 2: 128x128 transposed store, 3: 128x192 plane operands); negative on error */
 int abx_gemm3_occupancy(int which);
+/* diagnostics: the name of the kernel instantiation abx_gemm(main_gemm) (side_gemm == NULL) or abx_gemm_side(main_gemm, side_gemm) would
+ * launch, as `rocprofv3 --stats` spells it ("gemm3_kernel<128, 128, 32, 128, 0, false, 4>"), written to name[cap].  The dispatch itself
+ * runs, up to the launch: the same validation (a rejected descriptor returns the same negative code), the same environment switches and
+ * tune bits; a pair that falls back to two launches gives the main launch's name.  No HIP runtime call and no operand is dereferenced:
+ * works without a GPU, on placeholder addresses (their alignment and overlap are looked at). */
+int abx_gemm_plan(const AbxGemm* main_gemm, const AbxGemm* side_gemm, char* name, int cap);
 
 /* LayerNorm statistics (mean, rstd) per row for the LN-on-load GEMM prologue (torch.nn.LayerNorm, eps 1e-5).
  * s_k == 1: rows dense over batch (row stride s_row); else channel-major: element (b,row,k) at x + b*s_b + k*s_k + row. */
@@ -353,6 +359,10 @@ int abx_tri_attn_rowfused_fwd(const AbxTriAttn* desc, const float* z, long long 
  * measurements).  v = 0, 1, 2: the setting of later launches of this process; any other v changes nothing.  Returns the setting that held
  * before the call. */
 int abx_tri_row_touch(int v);
+/* diagnostics: the name of the kernel abx_tri_attn_fwd(desc) (rowfused == 0) or abx_tri_attn_rowfused_fwd(desc, z rows with the strides
+ * desc->sb / ss / sl, ...) (rowfused != 0) would launch, written to name[cap]; the descriptor is validated as by the entry point and a
+ * rejected one returns the same negative code.  No HIP runtime call, no operand dereferenced: works without a GPU (see abx_gemm_plan). */
+int abx_tri_attn_plan(const AbxTriAttn* desc, int rowfused, char* name, int cap);
 
 /* Sequence attention with pair bias (seqformer.py:314-356 + Attention.forward split_first=False :278-312).
  * qkv: [B*L][H*3*D] with per-head layout [q D | k D | v D]; bias [b][h][q][k]; gate pre-activation [B*L][H*D];

@@ -275,7 +275,7 @@ def test_gather_rows_gloo_world2():
 
 def test_glu_weight_packing_and_kernel_name_mirror():
     """Host-side helpers of the split-f16 path (no GPU): the (value, gate) column interleave of a glu GEMM and the
-    kernel-selection mirror that bench.py uses to label launches."""
+    kernel names that bench.py labels launches with (the library's dispatch, asked through abx_gemm_plan)."""
     import torch
     from abx_amd import ops
     K, C_ = 8, 128

@@ -1,0 +1,127 @@
+"""Kernel names come from the library's own dispatch (abx_gemm_plan / abx_tri_attn_plan: the dispatchers of csrc/gemm.hip, gemm3.hip,
+gemm_as.hip and attention.hip run up to the launch and name the kernel there).  Descriptors on placeholder addresses, literal names; no GPU.
+Run as a script with a case name, this file prints that case's name: the environment-switch tests start it as a fresh child process,
+because the library reads its switches once."""
+import ctypes
+import os
+import subprocess
+import sys
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
+P = 1 << 40                                         # placeholder "device addresses": 16-byte aligned, 1 TiB apart, never dereferenced
+ROWS = 1024 * 64                                    # 1 024 blocks of 64 rows: where the A-stationary walk starts to pay
+
+
+def _ln_gemm(M, N, K=192, a=1 * P):
+    """LayerNorm-folded weight GEMM on split-f16 planes: fp32 rows (M, K), planes [K/16][2][N][16], plain fp32 store."""
+    from abx_amd._lib import AbxGemm
+    g = AbxGemm()
+    g.M, g.N, g.K, g.batch, g.alpha, g.exact = M, N, K, 1, 1.0, 2
+    g.A, g.sAm, g.sAk = a, K, 1
+    g.B, g.sBk, g.sBn = 2 * P, N, 1
+    g.B_split, g.sB3n, g.sB3p, g.sB3k, g.b_f16 = 3 * P, 16, 16 * N, 32 * N, 1
+    g.C, g.sCm = 4 * P, N
+    g.ln_csum, g.bias, g.ln_eps = 5 * P, 6 * P, 1e-5
+    return g
+
+
+def _side(M, N=4, K=192):
+    """The skinny transposed-store projection over the same rows (the pair bias next to q | k | v)."""
+    s = _ln_gemm(M, N, K)
+    s.B, s.B_split, s.C, s.ln_csum, s.bias = 7 * P, 8 * P, 9 * P, 10 * P, 11 * P
+    s.c_transposed, s.sCm = 1, M
+    return s
+
+
+def _glu(L=256):
+    """The tri-mul projection: glu column pairs, unpadded pair rows in through the pair-row map, operand images out in (8 i x 16 k) blocks."""
+    g = _ln_gemm(L * L, 512)
+    g.glu, g.c_transposed, g.C = 1, 1, None
+    g.pair_L, g.pair_Lp, g.a_pair = L, L, 1
+    g.C_split, g.c_split_L, g.c_split_nA, g.c_split_tile = 4 * P, L, 128, 1
+    g.sCp, g.sCk, g.sCm = 16 * L, 32 * L, (L // 16) * 32 * L
+    return g
+
+
+def _plan(main, side=None):
+    from abx_amd import _lib
+    buf = ctypes.create_string_buffer(128)
+    rc = _lib.load().abx_gemm_plan(ctypes.byref(main), None if side is None else ctypes.byref(side), buf, len(buf))
+    return rc, buf.value.decode()
+
+
+TILE = 'gemm3_kernel<128, 128, 32, 128, 0, false, 4>'
+
+
+def test_a_stationary_kernel_routes():
+    from abx_amd import ops
+    assert ops.gemm_as_kernel_name(_ln_gemm(ROWS, 768)) == 'gemm_as_kernel<0, false, 0, false>'
+    assert _plan(_ln_gemm(ROWS, 768)) == (0, 'gemm_as_kernel<0, false, 0, false>')
+    assert ops.gemm_as_kernel_name(_ln_gemm(ROWS, 576), _side(ROWS)) == 'gemm_as_kernel<0, true, 0, false>'
+    g = _ln_gemm(ROWS, 576)
+    g.c_planes_from, g.c_planes_group = 192, 48
+    assert ops.gemm_as_kernel_name(g, _side(ROWS)) == 'gemm_as_kernel<0, true, 0, true>'
+    assert ops.gemm_as_kernel_name(_glu()) == 'gemm_as_kernel<1, false, 0, false>'
+    # one block of 64 rows short of the launch-size rule: the tile kernel
+    assert ops.gemm_as_kernel_name(_ln_gemm(1023 * 64, 768)) is None and _plan(_ln_gemm(1023 * 64, 768)) == (0, TILE)
+    # rows that are not 16-byte aligned: neither split-f16 kernel takes them, the exact fp32 kernel does
+    g = _ln_gemm(ROWS, 768, a=P + 4)
+    assert ops.gemm_as_kernel_name(g) is None and _plan(g) == (0, 'gemm_kernel<128, 192, 64, 96, 16, true, true, false, 2>')
+
+
+def test_pairs():
+    from abx_amd import ops
+    # N % 128 == 0: no ragged last tile for the side to ride in, the tile side kernel serves the pair
+    assert _plan(_ln_gemm(ROWS, 768), _side(ROWS)) == (0, 'gemm3_side_kernel')
+    assert ops.gemm_as_kernel_name(_ln_gemm(ROWS, 768), _side(ROWS)) is None
+    # N = 192: below the A-stationary kernel's two N-tiles and no multiple of 128: two launches, named after the main one
+    assert _plan(_ln_gemm(ROWS, 192), _side(ROWS)) == (0, 'gemm3_kernel<128, 192, 32, 192, 0, false, 3>')
+    assert _plan(_ln_gemm(ROWS, 192)) == (0, 'gemm3_kernel<128, 192, 32, 192, 0, false, 3>')
+
+
+def test_triangle_attention():
+    from abx_amd import ops
+    assert ops.tri_attn_kernel_name(352, exact=False, rowfused=False) == 'tri_attn8_kernel<192, 768, true>'
+    assert ops.tri_attn_kernel_name(231, exact=False, rowfused=False) == 'tri_attn8_kernel<128, 768, true>'
+    assert ops.tri_attn_kernel_name(97, exact=False, rowfused=False) == 'tri_attn8_kernel<128, 768, true>'
+    assert ops.tri_attn_kernel_name(352, exact=True) == 'tri_attn_kernel'
+    assert ops.tri_attn_kernel_name(352, exact=False, rowfused=True) == 'tri_attn8_rowfused_kernel'
+
+
+def test_rejected_descriptor_returns_the_code_of_the_mode_check():
+    from abx_amd import _lib
+    lib = _lib.load()
+    g = _ln_gemm(ROWS, 768)
+    g.out_ln_w, g.out_ln_b, g.A2, g.B2_split, g.ln2_csum = 12 * P, 13 * P, 14 * P, 15 * P, 16 * P      # out_ln and dual: exclusive
+    rc = lib.abx_gemm_check_modes(ctypes.byref(g))
+    assert rc < 0 and b'mutually exclusive' in lib.abx_last_error_string()
+    assert _plan(g) == (rc, '') and b'mutually exclusive' in lib.abx_last_error_string()
+
+
+def _child(case, switch):
+    """The name of `case` in a fresh process that has `switch` set and nothing else changed."""
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), case], env=dict(os.environ, **{switch: '1'}), capture_output=True,
+                         text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    return out.stdout.strip().splitlines()[-1]
+
+
+def test_abx_no_gemm_as_switches_the_name_too():
+    from abx_amd import ops
+    assert ops.gemm_as_kernel_name(_ln_gemm(ROWS, 768)) == 'gemm_as_kernel<0, false, 0, false>'
+    assert _child('as_plain', 'ABX_NO_GEMM_AS') == 'None'
+
+
+def test_abx_no_dual_as_switches_the_name_too():
+    from abx_amd import ops
+    assert ops.gemm_kernel_name(352 * 352, 192, 128, 100, a_kcontig=False, split=True, exact=2, dual=True) == 'gemm_as_dual_kernel'
+    assert _child('dual', 'ABX_NO_DUAL_AS') == 'gemm3_dual_kernel<128, 96, 32, 96, 3>'
+
+
+if __name__ == '__main__':
+    sys.path.insert(0, ROOT)
+    from abx_amd import ops
+    if sys.argv[1] == 'as_plain':
+        print(ops.gemm_as_kernel_name(_ln_gemm(ROWS, 768)))
+    elif sys.argv[1] == 'dual':
+        print(ops.gemm_kernel_name(352 * 352, 192, 128, 100, a_kcontig=False, split=True, exact=2, dual=True))

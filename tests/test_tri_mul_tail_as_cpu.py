@@ -1,5 +1,5 @@
-"""Host-side mirror of the tri-mul tail's dispatch (abx_amd.ops.gemm_kernel_name(dual=True, ...); csrc/gemm_as.hip as_dual_dispatch): the name
-bench.py prices the launch under.  No GPU needed."""
+"""The tri-mul tail's dispatch as abx_amd.ops.gemm_kernel_name(dual=True, ...) reports it (abx_gemm_plan: csrc/gemm_as.hip as_dual_dispatch
+itself, run up to the launch): the name bench.py prices the launch under.  No GPU needed."""
 
 
 def test_dual_kernel_name_follows_the_launch_size_rule():
