@@ -171,6 +171,7 @@ class AbxReverseArgs(C.Structure):
         ('noise_scale', F), ('center', I),
         ('rigid_out', c_f), ('seq_out', c_f), ('rates_out', c_f), ('jumps_out', c_f),
         ('B', I), ('L', I),
+        ('seq_bias', c_f),
     ]
 
 
@@ -383,6 +384,7 @@ _PROTOS = {
     'abx_scores': (I, [C.POINTER(AbxScoreArgs), _S]),
     'abx_torsion_finalize': (I, [c_f, c_f, c_f, c_f, I, _S]),
     'abx_seq_head_atoms': (I, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, I, _S]),
+    'abx_seq_head_atoms_biased': (I, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, I, c_f, I, _S]),
     'abx_prev_pos': (I, [c_f, c_f, I, c_f, I, I, _S]),
     'abx_plddt': (I, [c_f, c_f, I, I, _S]),
     'abx_igso3_tables': (I, [c_f, c_f, I, I, I, c_f, c_f, c_f, _S]),

@@ -127,6 +127,71 @@ __device__ __forceinline__ void quat_to_rotvec_ff(const float* qi, float* v) {
     v[0] = q[1] / s; v[1] = q[2] / s; v[2] = q[3] / s;
 }
 
+// The token part of the step under a sequence-constraint table (AbxReverseArgs.seq_bias, row l of (L,20): a finite logit bias or
+// -inf = this letter is forbidden at this residue).  The arithmetic of the unconstrained block below on logits + bias (a table of
+// zeros gives its bits), and on top of it: the rate of a forbidden target is exactly 0 (the q_diff * sum ratio term would leave it
+// positive), one uniform is consumed per target all the same (the Philox stream of a residue does not depend on its row), and a leap
+// that lands on a forbidden letter - the ordinal sum of discrete_diffuser.py:184-188 can land on a letter no jump aimed at - is
+// rejected: the token stays.  A row without a finite entry has all rates 0.  Returns the landing token; xt is the clamped token.
+__device__ __forceinline__ int biased_token_step(const AbxReverseArgs& a, long long i, int b, int l, int step, long long xt,
+                                                 float q_same, float q_diff, float dtf) {
+    const float* lg = a.logits + i * 20;
+    const float* bs = a.seq_bias + (long long)l * 20;
+    float p[20], mx = -INFINITY;
+    uint32_t allowed = 0u;
+#pragma unroll
+    for (int s = 0; s < 20; ++s) {
+        const float bv = bs[s];
+        allowed |= (bv != -INFINITY ? 1u : 0u) << s;
+        p[s] = lg[s] + bv;
+        mx = fmaxf(mx, p[s]);
+    }
+    const bool live = mx > -INFINITY;                               // some letter has a finite logit: the softmax is defined
+    float sm = 0.f;
+#pragma unroll
+    for (int s = 0; s < 20; ++s) { p[s] = live ? expf(p[s] - mx) : 0.f; sm += p[s]; }
+    if (!live) sm = 1.f;
+#pragma unroll
+    for (int s = 0; s < 20; ++s) {
+        const float ps = p[s] / sm;
+        const float den = ((long long)s == xt ? q_same : q_diff) + 1e-9f;
+        const float r = ps / den;
+        p[s] = r;
+    }
+    float overall = 0.f;
+    Philox ph2(a.seed ^ 0x5851F42D4C957F2Dull, (uint32_t)(a.sample_ids ? a.sample_ids[b] : b), (uint32_t)l, (uint32_t)step, 1u);
+#pragma unroll 1
+    for (int s2 = 0; s2 < 20; ++s2) {
+        float inner = 0.f;
+#pragma unroll
+        for (int s = 0; s < 20; ++s) inner += p[s] * (s == s2 ? q_same : q_diff);
+        const bool open = ((allowed >> s2) & 1u) != 0u;
+        const float rate = (open && (long long)s2 != xt) ? a.rate_const * inner : 0.f;
+        const float lam = rate * dtf;
+        if (a.rates_out) a.rates_out[i * 20 + s2] = lam;
+        float jumps;
+        if (a.jumps) {
+            jumps = open ? a.jumps[i * 20 + s2] : 0.f;
+        } else {
+            float u;
+            if (a.u_jumps) {
+                u = a.u_jumps[i * 20 + s2];
+            } else {
+                uint32_t r4[4];
+                ph2.next(r4);
+                u = u01(r4[0]);
+            }
+            jumps = (float)poisson_icdf(lam, u);                    // lam == 0: p_0 = 1 >= u, no jump
+        }
+        if (a.jumps_out) a.jumps_out[i * 20 + s2] = jumps;
+        overall += jumps * (float)((long long)s2 - xt);
+    }
+    float xp = (float)xt + overall;
+    xp = fminf(fmaxf(xp, 0.f), 19.f);
+    const int xnew = (int)xp;
+    return ((allowed >> xnew) & 1u) ? xnew : (int)xt;
+}
+
 // one workgroup per sample (the R^3 update is centred over ALL residues of the sample, r3_diffuser.py:141-146)
 __global__ __launch_bounds__(256) void reverse_step_kernel(const AbxReverseArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sh[];     // [L][3] un-centred x_{t-1} + [3*4] partials
@@ -222,53 +287,58 @@ __global__ __launch_bounds__(256) void reverse_step_kernel(const AbxReverseArgs 
             lsum[k] += x1;
         }
         // ---------------- tokens: tau-leaping with Poisson jump counts (discrete_diffuser.py:150-188)
-        const float* lg = a.logits + i * 20;
         long long xt = a.seq_in[i];
         xt = xt < 0 ? 0 : (xt > 19 ? 19 : xt);
-        float p[20], mx = lg[0];
+        int xnew;
+        if (a.seq_bias) {
+            xnew = biased_token_step(a, i, b, l, step, xt, q_same, q_diff, dtf);
+        } else {
+            const float* lg = a.logits + i * 20;
+            float p[20], mx = lg[0];
 #pragma unroll
-        for (int s = 1; s < 20; ++s) mx = fmaxf(mx, lg[s]);
-        float sm = 0.f;
+            for (int s = 1; s < 20; ++s) mx = fmaxf(mx, lg[s]);
+            float sm = 0.f;
 #pragma unroll
-        for (int s = 0; s < 20; ++s) { p[s] = expf(lg[s] - mx); sm += p[s]; }
+            for (int s = 0; s < 20; ++s) { p[s] = expf(lg[s] - mx); sm += p[s]; }
 #pragma unroll
-        for (int s = 0; s < 20; ++s) {
-            const float ps = p[s] / sm;
-            const float den = ((long long)s == xt ? q_same : q_diff) + 1e-9f;
-            const float r = ps / den;
-            p[s] = r;
-        }
-        float overall = 0.f;
-        Philox ph2(a.seed ^ 0x5851F42D4C957F2Dull, (uint32_t)(a.sample_ids ? a.sample_ids[b] : b), (uint32_t)l, (uint32_t)step, 1u);
-#pragma unroll 1
-        for (int s2 = 0; s2 < 20; ++s2) {
-            // inner[s2] = sum_s ratio[s] * q_t0[s][s2] = q_diff * sum_s ratio[s] + (q_same - q_diff) * ratio[s2]
-            float inner = 0.f;
-#pragma unroll
-            for (int s = 0; s < 20; ++s) inner += p[s] * (s == s2 ? q_same : q_diff);
-            float rate = ((long long)s2 == xt) ? 0.f : a.rate_const * inner;
-            const float lam = rate * dtf;
-            if (a.rates_out) a.rates_out[i * 20 + s2] = lam;
-            float jumps;
-            if (a.jumps) {
-                jumps = a.jumps[i * 20 + s2];
-            } else {
-                float u;
-                if (a.u_jumps) {
-                    u = a.u_jumps[i * 20 + s2];
-                } else {
-                    uint32_t r4[4];
-                    ph2.next(r4);
-                    u = u01(r4[0]);
-                }
-                jumps = (float)poisson_icdf(lam, u);
+            for (int s = 0; s < 20; ++s) {
+                const float ps = p[s] / sm;
+                const float den = ((long long)s == xt ? q_same : q_diff) + 1e-9f;
+                const float r = ps / den;
+                p[s] = r;
             }
-            if (a.jumps_out) a.jumps_out[i * 20 + s2] = jumps;
-            overall += jumps * (float)((long long)s2 - xt);
+            float overall = 0.f;
+            Philox ph2(a.seed ^ 0x5851F42D4C957F2Dull, (uint32_t)(a.sample_ids ? a.sample_ids[b] : b), (uint32_t)l, (uint32_t)step, 1u);
+#pragma unroll 1
+            for (int s2 = 0; s2 < 20; ++s2) {
+                // inner[s2] = sum_s ratio[s] * q_t0[s][s2] = q_diff * sum_s ratio[s] + (q_same - q_diff) * ratio[s2]
+                float inner = 0.f;
+#pragma unroll
+                for (int s = 0; s < 20; ++s) inner += p[s] * (s == s2 ? q_same : q_diff);
+                float rate = ((long long)s2 == xt) ? 0.f : a.rate_const * inner;
+                const float lam = rate * dtf;
+                if (a.rates_out) a.rates_out[i * 20 + s2] = lam;
+                float jumps;
+                if (a.jumps) {
+                    jumps = a.jumps[i * 20 + s2];
+                } else {
+                    float u;
+                    if (a.u_jumps) {
+                        u = a.u_jumps[i * 20 + s2];
+                    } else {
+                        uint32_t r4[4];
+                        ph2.next(r4);
+                        u = u01(r4[0]);
+                    }
+                    jumps = (float)poisson_icdf(lam, u);
+                }
+                if (a.jumps_out) a.jumps_out[i * 20 + s2] = jumps;
+                overall += jumps * (float)((long long)s2 - xt);
+            }
+            float xp = (float)xt + overall;
+            xp = fminf(fmaxf(xp, 0.f), 19.f);
+            xnew = (int)xp;
         }
-        float xp = (float)xt + overall;
-        xp = fminf(fmaxf(xp, 0.f), 19.f);
-        const int xnew = (int)xp;
         const long long m = a.diffuse_mask[i];
         a.seq_out[i] = m * (long long)xnew + (1 - m) * a.seq_in[i];
         // rotation merge + quaternion now; translation after the centring reduction

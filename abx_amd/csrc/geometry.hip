@@ -161,16 +161,28 @@ __global__ __launch_bounds__(128) void seq_head_atoms_kernel(const float* __rest
                                                              const long long* __restrict__ a37to14,
                                                              const float* __restrict__ dframes, const int* __restrict__ gidx,
                                                              const float* __restrict__ lit, long long* __restrict__ seq_0,
-                                                             float* __restrict__ atom14, float* __restrict__ atom37, int n) {
+                                                             float* __restrict__ atom14, float* __restrict__ atom37, int n,
+                                                             const float* __restrict__ seq_bias, int L) {
     const int i = blockIdx.x * 128 + threadIdx.x;
     if (i >= n) return;
     // argmax over 20 logits, first maximum wins (torch.max on softmax probabilities, head.py:166-167)
     int best = 0;
-    float bv = logits[(long long)i * 20];
+    if (seq_bias) {
+        // sequence constraints: argmax(logits + bias row of residue i % L), -inf = forbidden letter; the logits themselves stay as they are
+        const float* bs = seq_bias + (long long)(i % L) * 20;
+        float bv = logits[(long long)i * 20] + bs[0];
 #pragma unroll
-    for (int k = 1; k < 20; ++k) {
-        const float v = logits[(long long)i * 20 + k];
-        if (v > bv) { bv = v; best = k; }
+        for (int k = 1; k < 20; ++k) {
+            const float v = logits[(long long)i * 20 + k] + bs[k];
+            if (v > bv) { bv = v; best = k; }
+        }
+    } else {
+        float bv = logits[(long long)i * 20];
+#pragma unroll
+        for (int k = 1; k < 20; ++k) {
+            const float v = logits[(long long)i * 20 + k];
+            if (v > bv) { bv = v; best = k; }
+        }
     }
     const long long fx = fixed[i];
     const long long aa = (long long)best * (1 - fx) + seq_t[i] * fx;
@@ -339,8 +351,20 @@ extern "C" int abx_seq_head_atoms(const float* logits, const int* fixed_mask, co
     ABX_REQUIRE(logits && fixed_mask && seq_t && rigids && angles && atom37_to_atom14 && default_frames && group_idx && lit_pos &&
                     seq_0 && atom14 && atom37 && n > 0, "abx_seq_head_atoms: bad args");
     hipLaunchKernelGGL(seq_head_atoms_kernel, dim3((n + 127) / 128), dim3(128), 0, st, logits, fixed_mask, seq_t, rigids, angles,
-                       atom37_to_atom14, default_frames, group_idx, lit_pos, seq_0, atom14, atom37, n);
+                       atom37_to_atom14, default_frames, group_idx, lit_pos, seq_0, atom14, atom37, n, (const float*)nullptr, 1);
     return abx_check_launch("abx_seq_head_atoms");
+}
+
+extern "C" int abx_seq_head_atoms_biased(const float* logits, const int* fixed_mask, const long long* seq_t, const float* rigids,
+                                         const float* angles, const long long* atom37_to_atom14, const float* default_frames,
+                                         const int* group_idx, const float* lit_pos, long long* seq_0, float* atom14, float* atom37,
+                                         int n, const float* seq_bias, int L, hipStream_t st) {
+    ABX_REQUIRE(logits && fixed_mask && seq_t && rigids && angles && atom37_to_atom14 && default_frames && group_idx && lit_pos &&
+                    seq_0 && atom14 && atom37 && n > 0, "abx_seq_head_atoms_biased: bad args");
+    ABX_REQUIRE(seq_bias && L > 0 && n % L == 0, "abx_seq_head_atoms_biased: seq_bias is (L,20) and n a multiple of L");
+    hipLaunchKernelGGL(seq_head_atoms_kernel, dim3((n + 127) / 128), dim3(128), 0, st, logits, fixed_mask, seq_t, rigids, angles,
+                       atom37_to_atom14, default_frames, group_idx, lit_pos, seq_0, atom14, atom37, n, seq_bias, L);
+    return abx_check_launch("abx_seq_head_atoms_biased");
 }
 
 extern "C" int abx_prev_pos(const float* atom37, const float* sq_breaks, int num_breaks, long long* prev_pos, int B, int L,

@@ -42,6 +42,9 @@ salt bridges and unsatisfied polar atoms across the interface, <complex>_polar.t
 --ensemble: the designs of a complex compared with each other, Daura clusters and their centres, <complex>_ensemble.tsv
 (--ensemble_matrix: also <complex>_ensemble_rmsd.npy).  No flag changes a file that another one writes; the _rows / _planes tables need
 the sample-sharded schedule (--shard_samples).
+--seq_bias / --seq_forbid / --seq_fix: sequence constraints inside the step (abx_amd.constraints): per-residue logit biases, letters
+forbidden at every designed residue, a residue held to given letters; with any of them <complex>_sequence.tsv, one line per designed
+residue: the letter counts among the designs and `violations` (0).
 Weights: a checkpoint with the reference's `model_state_dict`, or seeded random weights (no checkpoint ships with the reference)."""
 import argparse
 import os
@@ -136,6 +139,13 @@ def build_parser():
     ap.add_argument('--guidance_hotspot_weight', type=float, default=1.0, help='--guidance_hotspots: weight of the hotspot term')
     ap.add_argument('--guidance_restraints', default=None, metavar='FILE', help='interface guidance: pair-distance restraints, one '
                     '`res atom res atom lo hi [weight]` per line')
+    ap.add_argument('--seq_bias', default=None, metavar='FILE', help='sequence constraints (abx_amd.constraints): per-residue logit biases, one '
+                    '`RES|* LETTERS VALUE` per line; RES as <chain letter>:<residue index as featurised>, * = every designed residue, VALUE a '
+                    'float or -inf (the letters are forbidden there)')
+    ap.add_argument('--seq_forbid', nargs='+', default=None, metavar='LETTERS', help='sequence constraints: letters forbidden at every designed '
+                    'residue, e.g. C M')
+    ap.add_argument('--seq_fix', nargs='+', default=None, metavar='RES=LETTERS', help='sequence constraints: only these letters at RES, e.g. '
+                    'H:100=Y; wins over --seq_forbid, the kept letters keep their --seq_bias value')
     ap.add_argument('--debug_one_gpu', action='store_true', help='debugging on a 1-GPU box: every rank uses cuda:0 and the gloo backend')
     # the reference's inference.py arguments (inference.py:398-416)
     ap.add_argument('--name_idx', default=None, help='text file with one complex name per line (entries of --data_dir)')
@@ -260,18 +270,23 @@ def main(argv=None):
         guide = ViolationGuidance(scale_trans=a.guidance_scale[0], scale_rot=a.guidance_scale[1])
     interface_guided = a.guidance_contact != 0.0 or a.guidance_hotspots is not None or a.guidance_restraints is not None
 
+    constrained = a.seq_bias is not None or a.seq_forbid is not None or a.seq_fix is not None
+
+    def job_chains(kind, path):
+        """The chain letters of a job in the order of the chain ids: from the file name, `H L A` for a synthetic workload."""
+        if kind in ('pdb', 'npz'):
+            from .data.antibody import parse_pdb_name
+            _, _, heavy, light, antigen = parse_pdb_name(path)
+            return [heavy, light] + list(antigen)
+        return ['H', 'L', 'A']
+
     def job_guide(batch, J, kind, path):
         """The guidance of one featurised batch: the violation terms (one object for the run) and, with the --guidance_contact /
         _hotspots / _restraints options, the interface terms of THIS complex (tables built here, before the sampling loop)."""
         if not interface_guided:
             return guide
         from .guidance import InterfaceGuidance, Sum, parse_residues, parse_restraints
-        if kind in ('pdb', 'npz'):
-            from .data.antibody import parse_pdb_name
-            _, _, heavy, light, antigen = parse_pdb_name(path)
-            chains = [heavy, light] + list(antigen)
-        else:
-            chains = ['H', 'L', 'A']
+        chains = job_chains(kind, path)
         hot = a.guidance_hotspots
         if hot is not None:
             hot = 'epitope' if list(hot) == ['epitope'] else parse_residues(hot, J['one'], chains)
@@ -359,6 +374,25 @@ def main(argv=None):
             kept[an.flag, ji] = an.build(batch if batch is not None else featurise(ji, [0]), a, model, cfg, {})
         return kept[an.flag, ji]
 
+    kept_cons = {}
+
+    def job_constraints(ji, batch=None):
+        """The sequence constraints of job ji (None without the --seq_* options): one per complex, from the first batch this rank sampled
+        of it or, for a complex the rank did not sample, from one featurised sample (the table reads what all samples share)."""
+        if not constrained:
+            return None
+        if ji not in kept_cons:
+            from .constraints import SequenceConstraints
+            kept_cons[ji] = SequenceConstraints(batch if batch is not None else featurise(ji, [0]), job_chains(jobs[ji][0], jobs[ji][1]),
+                                                bias_file=a.seq_bias, forbid=a.seq_forbid or (), fix=a.seq_fix or ())
+        return kept_cons[ji]
+
+    def write_sequence_table(ji, out_dir, cname, F):
+        """<complex>_sequence.tsv from the gathered designs (rank 0, after write_job; nothing without the --seq_* options)."""
+        if not constrained:
+            return []
+        return [job_constraints(ji).write_report(os.path.join(out_dir, f'{cname}_sequence.tsv'), F['seq'])]
+
     ref_written = set()
     for ji, ids in work:
         kind, path, out_dir, opt_step, ref_layout, ref_dir = jobs[ji]
@@ -401,10 +435,12 @@ def main(argv=None):
             for an in active:
                 scorers[an.flag] = an.build(batch, a, model, cfg, scorers) if an.kw else kept_scorer(an, ji, batch)
             job_guidance = job_guide(batch, J, kind, path)
+            job_cons = job_constraints(ji, batch)
             torch.cuda.synchronize()
             t_feat = time.perf_counter()
             traj = sampler.sample_fn(batch, cfg, diffuser, model, mode=a.mode, num_t=a.num_t,
                                      sample_ids=torch.tensor(ids, device=dev, dtype=torch.int64), on_record=writer.submit, guidance=job_guidance,
+                                     **({'constraints': job_cons} if job_cons is not None else {}),
                                      **{an.kw: scorers[an.flag] for an in active if an.kw})
             torch.cuda.synchronize()
             t_samp = time.perf_counter()
@@ -432,6 +468,7 @@ def main(argv=None):
         if rank == 0:                                           # (the float32 mean of every sample alone: what a set-level row carries)
             res['mean_pLDDT'] = [float(res['pLDDT'][i].float().mean()) for i in range(N)]
             files += analyses.write_job(active, a, out_dir, cname, list(range(N)), res, lambda an: kept_scorer(an, ji))
+            files += write_sequence_table(ji, out_dir, cname, res)
     if plan is not None:
         # ---- the one collective of the set: every rank's rows of the designs table (counts known from the common plan)
         table = torch.cat(set_rows, 0) if set_rows else torch.zeros(0, layout.WIDTH, dtype=torch.float64)
@@ -443,7 +480,9 @@ def main(argv=None):
             for ji in range(len(jobs)):
                 rows = full[full[:, 0] == ji]
                 assert rows.shape[0] == N, (jobs[ji][1], rows.shape)
-                files += analyses.write_job(active, a, jobs[ji][2], load_job(ji)['cname'], *layout.unpack(rows), lambda an: kept_scorer(an, ji))
+                ids_, F_ = layout.unpack(rows)
+                files += analyses.write_job(active, a, jobs[ji][2], load_job(ji)['cname'], ids_, F_, lambda an: kept_scorer(an, ji))
+                files += write_sequence_table(ji, jobs[ji][2], load_job(ji)['cname'], F_)
     if world > 1 or a.force_collective:
         import torch.distributed as dist
         dist.barrier()

@@ -169,10 +169,12 @@ class FullDiffuser:
 
     # ---- reverse step -------------------------------------------------------------------------------------------------------
     def reverse(self, rigid_t, seq_t, rot_score, trans_score, logits_t, t, dt, diffuse_mask=None, center=True,
-                noise_scale=1.0, noise=None, sample_ids=None, step=None, step_dev=None, rates_out=None, jumps_out=None):
+                noise_scale=1.0, noise=None, sample_ids=None, step=None, step_dev=None, rates_out=None, jumps_out=None, seq_bias=None):
         """full_diffuser.py:174-227.  Extension kwargs (not in the reference): `noise` = recorded draws {'z_rot','z_trans'[,'jumps']}
         or {'u_jumps'} (B,L,20) uniforms that drive the Poisson inverse cdf; `sample_ids` / `step` / `step_dev` key the device
-        Philox streams; `rates_out` / `jumps_out` (B,L,20) fp32 receive the Poisson rates * dt and the applied jump counts."""
+        Philox streams; `rates_out` / `jumps_out` (B,L,20) fp32 receive the Poisson rates * dt and the applied jump counts; `seq_bias`
+        (L,20) fp32 on the device, the table of abx_amd.constraints: logit bias / -inf = forbidden letter per residue (None: the
+        reference's token step)."""
         dev = rigid_t.device
         self.to(dev)
         B, L = rigid_t.shape[:2]
@@ -216,6 +218,8 @@ class FullDiffuser:
         if step_dev is not None:
             assert step_dev.dtype == torch.int32 and step_dev.is_cuda
             kw.update(step_dev=step_dev)
+        if seq_bias is not None:
+            kw.update(seq_bias=seq_bias)
         ops.reverse_step(**kw)
         return out_r, out_s
 

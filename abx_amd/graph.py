@@ -20,7 +20,9 @@ from abx_amd.model.abx import get_prev
 
 
 class GraphedSteps:
-    def __init__(self, batch, config, diffuser, model, diffuse_mask, dt, sample_ids, center=True, noise_scale=1.0, guidance=None):
+    def __init__(self, batch, config, diffuser, model, diffuse_mask, dt, sample_ids, center=True, noise_scale=1.0, guidance=None,
+                 seq_bias=None):
+        self.seq_bias = seq_bias         # (L,20) sequence-constraint table or None: a static device tensor, read by every replay
         self.batch, self.cfg, self.D, self.model = batch, config, diffuser, model
         self.dm, self.dt, self.sid, self.center, self.noise_scale, self.guidance = diffuse_mask, dt, sample_ids, center, noise_scale, guidance
         dev = batch['rigids_t'].device
@@ -49,7 +51,8 @@ class GraphedSteps:
             rot_score, trans_score = self.guidance(b, out, rot_score, trans_score, self.dm)
         rig, seq = self.D.reverse(rigid_t=b['rigids_t'], seq_t=b['seq_t'], rot_score=rot_score, trans_score=trans_score,
                                   logits_t=out['heads']['sequence_module']['logits'], diffuse_mask=self.dm, t=self.t, dt=self.dt,
-                                  center=self.center, noise_scale=self.noise_scale, sample_ids=self.sid, step=0, step_dev=self.step)
+                                  center=self.center, noise_scale=self.noise_scale, sample_ids=self.sid, step=0, step_dev=self.step,
+                                  seq_bias=self.seq_bias)
         self.rig.copy_(rig)
         self.seq.copy_(seq)
         return out

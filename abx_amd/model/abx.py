@@ -302,6 +302,7 @@ class ScoreNetwork(nn.Module):
             torsion_gt=batch['torsion_angles_sin_cos'].to(f32), a37to14=batch['residx_atom37_to_atom14'].to(i64),
             prev_seq=batch.get('prev_seq'), prev_pair=batch.get('prev_pair'), prev_pos=batch.get('prev_pos'),
             esm_embed=self._esm_embed(batch),
+            seq_bias=batch.get('seq_bias'),     # (L,20) sequence-constraint table (abx_amd.constraints) or None: the masked argmax of every pass
             t64=t.to(torch.float64).contiguous(), t_is_f32=t_is_f32,
             rep_seq_out=self._buf('rep_seq' + tag, (B, L, WS_), f32, device),
             rep_pair_out=self._buf('rep_pair' + tag, (B, L, L, WZ), f32, device),

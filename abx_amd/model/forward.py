@@ -697,7 +697,7 @@ class Engine:
             _lin(P, pre + '5', tb, logits.view(M1, 20))
         ops.seq_head_atoms(logits, fixed.reshape(-1), seq_t.contiguous(), st['rigids'][b0:b1], angles,
                            st['a37to14'][b0:b1].contiguous(), P.default_frames, P.group_idx, P.lit_pos,
-                           st['seq_0'][b0:b1], st['atom14'][b0:b1], st['atom37'][b0:b1], M1)
+                           st['seq_0'][b0:b1], st['atom14'][b0:b1], st['atom37'][b0:b1], M1, seq_bias=st.get('seq_bias'), L=L)
         if final:
             if heads is None:
                 pre = 'impl.predicted_lddt.net.'

@@ -964,8 +964,18 @@ def torsion_finalize(unnorm, gt, fixed_i32, angles, n):
     check(_lib.load().abx_torsion_finalize(_p(unnorm), _p(gt), _p(fixed_i32), _p(angles), n, _stream()), 'abx_torsion_finalize')
 
 
-def seq_head_atoms(logits, fixed_i32, seq_t, rigids, angles, a37to14, dframes, gidx, lit, seq_0, atom14, atom37, n):
+def seq_head_atoms(logits, fixed_i32, seq_t, rigids, angles, a37to14, dframes, gidx, lit, seq_0, atom14, atom37, n, seq_bias=None, L=None):
+    """seq_bias: None, or the (L,20) float32 device table of abx_amd.constraints (row i % L for residue i): abx_seq_head_atoms_biased."""
     assert seq_t.dtype == torch.int64 and a37to14.dtype == torch.int64 and gidx.dtype == torch.int32
+    if seq_bias is not None:
+        L = seq_bias.shape[0] if L is None else int(L)
+        assert seq_bias.dtype == torch.float32 and seq_bias.is_cuda and seq_bias.is_contiguous() and tuple(seq_bias.shape) == (L, 20), \
+            (seq_bias.dtype, tuple(seq_bias.shape), L)
+        assert n % L == 0, (n, L)
+        check(_lib.load().abx_seq_head_atoms_biased(_p(logits), _p(fixed_i32), _p(seq_t), _p(rigids), _p(angles), _p(a37to14), _p(dframes),
+                                                    _p(gidx), _p(lit), _p(seq_0), _p(atom14), _p(atom37), n, _p(seq_bias), L, _stream()),
+              'abx_seq_head_atoms_biased')
+        return
     check(_lib.load().abx_seq_head_atoms(_p(logits), _p(fixed_i32), _p(seq_t), _p(rigids), _p(angles), _p(a37to14), _p(dframes),
                                          _p(gidx), _p(lit), _p(seq_0), _p(atom14), _p(atom37), n, _stream()), 'abx_seq_head_atoms')
 
@@ -987,7 +997,11 @@ def igso3_tables(sigma, omega, pdf, cdf, score_norms, L_terms=1000):
 
 
 def reverse_step(**kw):
+    """Keywords = the fields of AbxReverseArgs (include/abx_hip.h); seq_bias: the (L,20) float32 device table of abx_amd.constraints."""
     a = AbxReverseArgs()
+    sb = kw.get('seq_bias')
+    if sb is not None:
+        assert sb.dtype == torch.float32 and sb.is_cuda and sb.is_contiguous() and tuple(sb.shape) == (kw['L'], 20), (sb.dtype, tuple(sb.shape))
     for k, v in kw.items():
         setattr(a, k, _p(v) if torch.is_tensor(v) else v)
     check(_lib.load().abx_reverse_step(C.byref(a), _stream()), 'abx_reverse_step')

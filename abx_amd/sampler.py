@@ -24,7 +24,7 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None):
+              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -56,7 +56,12 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     hydrogen bonds and salt bridges across the interface, polar atoms buried without a partner - with a relaxer 'polar_relaxed', and
     with `polar.want_rows` 'polar_bonds' (B, L, 14, 2) and 'polar_rows' (B, L, 4) int32 of the designs.  When `interface` is the
     scorer's own InterfaceScorer, its point counts serve both tables: the surface kernel runs once per structure set.  One launch per
-    table, outside any captured step, no host synchronisation."""
+    table, outside any captured step, no host synchronisation.
+    constraints: None (the reference's unconstrained sampler, bit-identical code path, the records have exactly today's keys) or an
+    abx_amd.constraints.SequenceConstraints of the complex: its (L,20) table goes into this call's copy of the batch as 'seq_bias' (the
+    masked argmax of every network pass), a designed residue's forbidden start token is projected onto the nearest allowed letter before
+    the warm-up call, and every reverse step reads the table (no rate towards a forbidden letter, a leap onto one is rejected).  The
+    table's address is static, so a captured step stays replayable."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -73,6 +78,10 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
         if opt_step < 1.0:
             steps = steps[steps <= opt_step + eps]
     batch.pop('_static', None)          # trajectory-invariant embeddings: rebuilt once per trajectory from THIS batch
+    seq_bias = None
+    if constraints is not None:
+        seq_bias = batch['seq_bias'] = constraints.table.to(device)
+        batch['seq_t'] = constraints.project(batch['seq_t'], diffuse_mask)
     log_start = len(getattr(model, 'range_log', None) or [])     # (the model's range log is cumulative: report this trajectory's part)
     traj = []
     score_table = scorer.new_table(len(steps) if mode == 'trajectory' else 1, B) if scorer is not None else None
@@ -86,7 +95,8 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
         if use_graph:
             assert noise_fn is None, 'graph replay uses the device Philox generator (no injected noise)'
             from abx_amd.graph import GraphedSteps
-            graphed = GraphedSteps(batch, config, diffuser, model, diffuse_mask, dt, sample_ids, center, noise_scale, guidance)
+            graphed = GraphedSteps(batch, config, diffuser, model, diffuse_mask, dt, sample_ids, center, noise_scale, guidance,
+                                   seq_bias=seq_bias)
         for k, t in enumerate(steps):
             if t > min_t and graphed is not None:
                 out = graphed.run(k, t)
@@ -105,7 +115,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                     rigid_t=batch['rigids_t'], seq_t=batch['seq_t'], rot_score=rot_score, trans_score=trans_score,
                     logits_t=out['heads']['sequence_module']['logits'], diffuse_mask=diffuse_mask, t=t_, dt=dt,
                     center=center, noise_scale=noise_scale, noise=noise_fn(k) if noise_fn else None,
-                    sample_ids=sample_ids, step=k)
+                    sample_ids=sample_ids, step=k, seq_bias=seq_bias)
             else:
                 out = model(batch)
                 rigids_t = out['heads']['folding']['rigids']

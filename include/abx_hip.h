@@ -478,6 +478,14 @@ int abx_seq_head_atoms(const float* logits, const int* fixed_mask, const long lo
                        const float* angles, const long long* atom37_to_atom14, const float* default_frames,
                        const int* group_idx, const float* lit_pos, long long* seq_0, float* atom14, float* atom37, int n,
                        hipStream_t stream);
+/* The same under a sequence-constraint table (NOT in the reference: head.py:166-167 takes the plain maximum): seq_bias DEVICE float32
+ * (L,20), row i % L for residue i of the n = B * L, a finite logit bias or -inf (forbidden letter).  seq_0 = argmax(logits + seq_bias),
+ * first maximum wins, merged with seq_t at fixed positions; frames and atoms are built from that residue type by the same kernel body.
+ * The logits buffer is read only: the caller's logits stay the network's own. */
+int abx_seq_head_atoms_biased(const float* logits, const int* fixed_mask, const long long* seq_t, const float* rigids,
+                              const float* angles, const long long* atom37_to_atom14, const float* default_frames,
+                              const int* group_idx, const float* lit_pos, long long* seq_0, float* atom14, float* atom37, int n,
+                              const float* seq_bias, int L, hipStream_t stream);
 /* get_prev (abx.py:17-26): virtual C-beta from N,CA,C (common_modules.py:62-83) and 15-bin distogram -> int64 (B,L,L) */
 int abx_prev_pos(const float* atom37, const float* sq_breaks, int num_breaks, long long* prev_pos, int B, int L,
                  hipStream_t stream);
@@ -497,7 +505,14 @@ int abx_igso3_tables(const float* sigma, const float* omega, int num_sigma, int 
  * Poisson(rate*dt) (fp32 pmf recurrence from (float)exp(-(double)lam), see diffuser.hip::poisson_icdf) evaluated at
  * u_jumps[b,l,s] in (0,1) when given (jumps == NULL), else at the Philox uniform of (sample id, residue, step, draw s).
  * Outputs rigid_out f64 (B,L,7), seq_out int64 (B,L).  Optional: rates_out (B,L,20) = the Poisson rates * dt,
- * jumps_out (B,L,20) = the jump counts that were applied. */
+ * jumps_out (B,L,20) = the jump counts that were applied.
+ * Sequence constraints (NOT in the reference: discrete_diffuser.py:150-188 has no such handle): seq_bias, optional DEVICE float32
+ * (L,20) shared by all samples, row l = residue l: a finite logit bias (0: no opinion) or -inf (the letter is forbidden there).  With
+ * it the softmax of discrete_diffuser.py:160 runs over logits + seq_bias, the Poisson rate of a forbidden target is exactly 0 (as it is
+ * for the current token; rates_out / jumps_out report the zeros), one uniform is consumed per target all the same, and a leap whose
+ * ordinal landing token clamp(x_t + sum jumps * (s - x_t)) (discrete_diffuser.py:184-188) is forbidden is rejected: the token stays.
+ * A forbidden x_t leaves with the first leap that lands on an allowed letter; a row without a finite entry keeps its token.  The
+ * caller keeps rows of residues outside diffuse_mask at 0 and refuses +inf / NaN.  seq_bias == NULL is the reference's step. */
 typedef struct AbxReverseArgs {
     const void* rigid_in; int rigid_is_f64;
     const long long* seq_in;
@@ -514,6 +529,7 @@ typedef struct AbxReverseArgs {
     float noise_scale; int center;
     double* rigid_out; long long* seq_out; float* rates_out; float* jumps_out;
     int B, L;
+    const float* seq_bias;                   /* optional DEVICE (L,20): logit bias / -inf = forbidden letter per residue (see above) */
 } AbxReverseArgs;
 int abx_reverse_step(const AbxReverseArgs* a, hipStream_t stream);
 
