@@ -336,6 +336,27 @@ class AbxPolarArgs(C.Structure):
     ]
 
 
+DEV_COLS = 21             # ABX_DEV_COLS
+
+
+class AbxDevelopabilityArgs(C.Structure):
+    _fields_ = _STRUCTURE_FIELDS + [
+        ('region', c_f),
+        ('radius', c_f),
+        ('chain_id', c_f), ('residx', c_f),
+        ('cdr_def', c_f),
+        ('q', c_f), ('q_max', LL),
+        ('a', c_f), ('ref', c_f),
+        ('points', c_f), ('P', I),
+        ('radius2', C.c_double),
+        ('exposed', C.c_double),
+        ('out', c_f), ('out_stride', LL),
+        ('rows', c_f),
+        ('j_chunk', I),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -410,6 +431,8 @@ _PROTOS = {
     'abx_polar_scores_workspace_bytes': (LL, [I, I]),
     'abx_polar_scores_lds_bytes': (LL, [I]),
     'abx_polar_scores': (I, [C.POINTER(AbxPolarArgs), c_f, _S]),
+    'abx_developability_scores_workspace_bytes': (LL, [I, I]),
+    'abx_developability_scores': (I, [C.POINTER(AbxDevelopabilityArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

@@ -1,7 +1,8 @@
-"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES beside the writers of its tables, and
-RowLayout, the columns of the row table that a set-level run gathers.  design.main walks ANALYSES in their order for the option checks,
-the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and zero-row blocks come from the same declarations), the
-set-level rows and the files of rank 0: the next analysis is one more entry here and nothing in main."""
+"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES (or, the later ones, in EXTENSIONS) beside
+the writers of its tables, and RowLayout, the columns of the row table that a set-level run gathers.  design.main walks ANALYSES +
+EXTENSIONS in their order for the option checks, the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and
+zero-row blocks come from the same declarations), the set-level rows and the files of rank 0: the next analysis is one more entry here
+and nothing in main."""
 import functools
 import math
 import os
@@ -10,7 +11,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import accuracy, confidence, ensemble, interface, metrics, polar, relax
+from . import accuracy, confidence, developability, ensemble, interface, metrics, polar, relax
 from .io import index_to_str_seq
 
 F64 = torch.float64
@@ -99,11 +100,11 @@ RELAX = Analysis('relax', 'relaxer', lambda batch, a, *_: relax.ViolationRelaxer
 
 
 def _write_with_wild_deltas(kind, out_dir, cname, wild, rows, relaxed):
-    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence): the `wild` line, then (sample
+    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence, developability): the `wild` line, then (sample
     id, values) per sample; values = the module's <KIND>_COLUMNS row and, when relaxed, the row of the relaxed structure.  After the
     columns: delta_<column> = row minus wild for the module's DELTA_COLUMNS.  wild None: every sample has a wild row of its own, the
     last columns of its values, and the `wild` line is their mean."""
-    mod = {'interface': interface, 'polar': polar, 'confidence': confidence}[kind]
+    mod = {'interface': interface, 'polar': polar, 'confidence': confidence, 'developability': developability}[kind]
     columns, fmt = getattr(mod, f'{kind.upper()}_COLUMNS'), getattr(mod, f'format_{kind}')
     N = len(columns)
     wilds = [wild if wild is not None else v[len(v) - N:] for _, v in rows]
@@ -212,10 +213,12 @@ def _polar_build(batch, a, model, cfg, scorers):
 
 
 def _shared_wild_points(scorers):
-    """--polar with --interface: the (1, L, 14, 2) point counts of the wild type that interface.wild() fills and polar.wild() reads
-    instead of running the surface kernel again, kept with the scorers of the batch; None without both."""
-    if 'polar' in scorers and 'interface' in scorers and 'wild_points' not in scorers:
-        scorers['wild_points'] = scorers['polar'].new_points(1)
+    """--polar or --developability with --interface: the (1, L, 14, 2) point counts of the wild type that interface.wild() fills and
+    polar.wild() / developability.wild() read instead of running the surface kernel again, kept with the scorers of the batch; None
+    without --interface or without either of the two."""
+    users = [scorers[k] for k in ('polar', 'developability') if k in scorers]
+    if users and 'interface' in scorers and 'wild_points' not in scorers:
+        scorers['wild_points'] = users[0].new_points(1)
     return scorers.get('wild_points')
 
 
@@ -266,10 +269,34 @@ ENSEMBLE = Analysis('ensemble', None, lambda batch, a, *_: ensemble.EnsembleAnal
 ANALYSES = (SCORE, RELAX, INTERFACE, CONFIDENCE, ACCURACY, POLAR, ENSEMBLE)
 
 
+# --developability: aggregation propensity, chain charges and sequence liabilities of the free antibody.  Its exposure comes from the
+# point counts of the interface analysis, so it is coupled to --interface exactly as --polar is (the three places named there).
+DEVELOPABILITY_CHECKS = [(lambda a: not a.developability_radius > 0 or not 0.0 <= a.developability_exposed <= 1.0,
+                          '--developability_radius must be > 0, --developability_exposed in [0, 1]'),
+                         (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')]
+
+
+def _developability_build(batch, a, model, cfg, scorers):
+    dev = developability.DevelopabilityScorer(batch, radius=a.developability_radius, exposed=a.developability_exposed, n_points=a.interface_points,
+                                              probe=a.interface_probe, interface=scorers.get('interface'))
+    dev.want_rows = a.developability_rows
+    return dev
+
+
+_write_developability = functools.partial(_write_with_wild_deltas, 'developability')
+DEVELOPABILITY = _wild_table('developability', developability.DEVELOPABILITY_COLUMNS, _write_developability, _developability_build,
+                             lambda last, scorers: scorers['developability'].wild(points=_shared_wild_points(scorers)), DEVELOPABILITY_CHECKS,
+                             Extra('developability_rows', Field('developability_rows', F64, ('L', 4), False), lambda last: last['developability_rows'],
+                                   lambda t: t.cpu().numpy()))
+
+# The analyses added after ANALYSES was pinned: walked after it, declared the same way
+EXTENSIONS = (DEVELOPABILITY,)
+
+
 def check_options(a, set_level):
     """The analyses that the parsed options `a` switch on, in order, after their option checks.  set_level: the run gathers rows."""
     active = []
-    for an in ANALYSES:
+    for an in ANALYSES + EXTENSIONS:
         if getattr(a, an.flag):
             for bad, text in an.checks:
                 if bad(a):

@@ -6,7 +6,7 @@ import math
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1315,6 +1315,43 @@ def polar_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, table, Lab=None, reg
     _side_output(a, 'bonds', bonds, torch.int32, (B, L, 14, 2))
     _side_output(a, 'rows', rows, torch.int32, (B, L, 4))
     check(lib.abx_polar_scores(C.byref(a), None, _stream()), 'abx_polar_scores')
+    return out
+
+
+def developability_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, cdr_def, tables, points, Lab=None, residx=None, region=None,
+                          mask=None, res_mask=None, n_points=128, q_max=None, radius=10.0, exposed=0.075, out=None, rows=None, j_chunk=0):
+    """Developability of B structures of one complex (abx_developability_scores; columns: abx_amd.developability.DEVELOPABILITY_COLUMNS):
+    spatial aggregation propensity, chain charges and sequence liabilities of the free antibody, the rows < Lab.
+    atom14, seq, the complex, region, mask, res_mask as for interface_scores; chain_id, cdr_def (L) int32, residx (L) int32 or None as for
+    design_scores; tables = (q (21,14) int64, a (21,14) float64, ref (21) float64) on the device (abx_amd.developability.weight_table for
+    n_points and the probe of the surface); q_max: the largest |q| (None: read from q, one host synchronisation); points (B,L,14,2) int32
+    contiguous, the acc_alone / acc_cplx that interface_scores returned for the SAME structures with n_points sphere points.
+    radius: of the SAP sphere (Angstrom); exposed: smallest relative side-chain area of an exposed residue; j_chunk: weighted atoms per LDS
+    chunk (0: the kernel's default).
+    out: (B, 21) float64 with unit column stride and any row stride, or None; rows: (B,L,4) float64 contiguous to receive
+    abx_amd.developability.ROW_COLUMNS of every row, or None.  Three launches, no synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = gt_seq.shape[-1]
+    q, ar, ref = tables
+    assert q.dtype == torch.int64 and tuple(q.shape) == (21, 14) and ar.dtype == torch.float64 and tuple(ar.shape) == (21, 14) and \
+        ref.dtype == torch.float64 and tuple(ref.shape) == (21,) and all(t.is_contiguous() and t.device == dev for t in tables), \
+        'tables: q (21,14) int64, a (21,14) float64, ref (21) float64 on the device of atom14'
+    a = AbxDevelopabilityArgs()
+    B, _, _, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region, extra=(chain_id, cdr_def))
+    a.chain_id, a.cdr_def = own(chain_id, torch.int32), own(cdr_def, torch.int32)
+    if residx is not None:
+        assert tuple(residx.shape) == (L,), residx.shape
+        a.residx = own(residx, torch.int32)
+    a.q, a.a, a.ref = _p(q), _p(ar), _p(ref)
+    a.q_max = int(q.abs().max()) if q_max is None else int(q_max)
+    assert points is not None, 'points: the (B,L,14,2) int32 counts of interface_scores'
+    _side_output(a, 'points', points, torch.int32, (B, L, 14, 2))
+    a.P, a.radius2, a.exposed, a.j_chunk = int(n_points), float(radius) * float(radius), float(exposed), int(j_chunk)
+    out = _out_rows(a, out, B, _lib.DEV_COLS, dev)
+    _side_output(a, 'rows', rows, torch.float64, (B, L, 4))
+    ws = torch.empty(max(int(lib.abx_developability_scores_workspace_bytes(B, L)), 16), dtype=torch.uint8, device=dev)
+    check(lib.abx_developability_scores(C.byref(a), _p(ws), _stream()), 'abx_developability_scores')
     return out
 
 

@@ -24,7 +24,7 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None):
+              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None, developability=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -61,7 +61,13 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     abx_amd.constraints.SequenceConstraints of the complex: its (L,20) table goes into this call's copy of the batch as 'seq_bias' (the
     masked argmax of every network pass), a designed residue's forbidden start token is projected onto the nearest allowed letter before
     the warm-up call, and every reverse step reads the table (no rate towards a forbidden letter, a leap onto one is rejected).  The
-    table's address is static, so a captured step stays replayable."""
+    table's address is static, so a captured step stays replayable.
+    developability: None (the records have exactly today's keys and bits), or an abx_amd.developability.DevelopabilityScorer of the
+    complex: the LAST record gets 'developability' (B, len(developability.DEVELOPABILITY_COLUMNS)) float64 - aggregation propensity,
+    chain charges and sequence liabilities of the free antibody - with a relaxer 'developability_relaxed', and with
+    `developability.want_rows` 'developability_rows' (B, L, 4) float64 of the designs.  It shares the point counts of `interface` like
+    `polar`: with all three the surface kernel still runs once per structure set.  Three launches per table, outside any captured step,
+    no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -132,7 +138,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 if scorer is not None:
                     traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
                 if k == len(steps) - 1:
-                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar)
+                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability)
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)
@@ -154,7 +160,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     return traj
 
 
-def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar):
+def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None):
     """What the analyses of sample_fn add to the LAST record, from the model's output `out` of the call that made it and its per-residue
     pLDDT, each on the design and, with a relaxer, on the relaxed structure.  Launches only, no host synchronisation."""
     x, seq, B = rec['atom14_results'], rec['seq'], rec['seq'].shape[0]
@@ -162,11 +168,12 @@ def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accu
         rec['atom14_relaxed'], rec['relax'] = relaxer.relax(x, seq)
         if scorer is not None:
             rec['scores_relaxed'] = scorer.score(rec['atom14_relaxed'], seq)
-    pts = pts_relaxed = None                                    # point counts of the interface call, when the polar scorer shares it
+    pts = pts_relaxed = None                                    # point counts of the interface call, when a later scorer shares it
     if interface is not None:
-        if polar is not None and polar.interface is interface:
-            pts = polar.new_points(B)
-            pts_relaxed = polar.new_points(B) if relaxer is not None else None
+        sharing = [sc for sc in (polar, developability) if sc is not None and sc.interface is interface]
+        if sharing:
+            pts = sharing[0].new_points(B)
+            pts_relaxed = sharing[0].new_points(B) if relaxer is not None else None
         rec['interface'] = interface.score(x, seq, points=pts)
         if relaxer is not None:
             rec['interface_relaxed'] = interface.score(rec['atom14_relaxed'], seq, points=pts_relaxed)
@@ -174,9 +181,17 @@ def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accu
         if polar.want_rows:
             rec['polar_bonds'] = torch.empty(B, polar.L, 14, 2, dtype=torch.int32, device=x.device)
             rec['polar_rows'] = torch.empty(B, polar.L, 4, dtype=torch.int32, device=x.device)
-        rec['polar'] = polar.score(x, seq, points=pts, bonds=rec.get('polar_bonds'), rows=rec.get('polar_rows'))
+        shared = polar.interface is interface
+        rec['polar'] = polar.score(x, seq, points=pts if shared else None, bonds=rec.get('polar_bonds'), rows=rec.get('polar_rows'))
         if relaxer is not None:
-            rec['polar_relaxed'] = polar.score(rec['atom14_relaxed'], seq, points=pts_relaxed)
+            rec['polar_relaxed'] = polar.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
+    if developability is not None:
+        shared = developability.interface is interface
+        if developability.want_rows:
+            rec['developability_rows'] = developability.new_rows(B)
+        rec['developability'] = developability.score(x, seq, points=pts if shared else None, rows=rec.get('developability_rows'))
+        if relaxer is not None:
+            rec['developability_relaxed'] = developability.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
     if confidence is not None:
         pair = out['representations']['pair']                   # of the call just made: nothing between it and here runs the network
         got = confidence.score(pair, x, seq, planes=bool(confidence.want_planes))

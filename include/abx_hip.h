@@ -1002,6 +1002,79 @@ long long abx_polar_scores_lds_bytes(int L);
 int abx_polar_scores(const AbxPolarArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Developability of designs: spatial aggregation propensity (SAP, Chennamsetty et al. 2009), chain charges and sequence liabilities of
+ * the FREE antibody, rows < Lab (the antigen enters only through acc_alone, the antibody's surface with the antigen taken away).  One
+ * row of ABX_DEV_COLS float64 values per structure of a batch of B designs of ONE complex (abx_amd.developability.
+ * DEVELOPABILITY_COLUMNS).  No pI, no patch metrics, no hydrogens; His carries no charge.
+ * The structure and the complex are given as for abx_polar_scores (pred_* rows < Lpred, residue types of rows < Lab from pred_seq,
+ * clamped to 0..20; pred_mask / res_mask optional; region (L) bytes shared by the batch, optional), with chain_id (L), residx (L,
+ * optional) and cdr_def (L) as for abx_design_scores.  points: (B, L, 14, 2) int32, the output of abx_interface_scores for the same
+ * structures with P sphere points; only acc_alone (points[..., 0]) is read.
+ * COUNTED ATOMS: the slots of rows < Lab that exist and have radius > 0.  A row is PRESENT if it has a counted atom.
+ * Tables of the caller (abx_amd.developability.weight_table), per (residue type, atom14 slot): a [21][14] doubles, the area of one sphere
+ * point, 4 pi (r + probe)^2 / P; ref [21] doubles, the side-chain area of the isolated residue (0: Gly, X); q [21][14] int64, the
+ * fixed-point weight of one accessible point, rint(2^30 a h / ref), 0 on slots < 4 (the kernel knows no hydrophobicity scale).
+ * q_max: the largest |q| of the table.
+ *   w_j   = acc_alone_j * q[type_j][slot_j]                                                     (int64)
+ *   SAP_i = sum of w_j over the counted atoms j with (dx*dx + dy*dy) + dz*dz <= radius2, j = i included;  dx = (double)x_j - (double)x_i
+ *           (likewise y, z) in float64 without fused multiply-add                                (int64: the order does not matter)
+ * EXPOSED row: ref[type] > 0 and rel >= exposed * ref[type], rel = sum over the slots s = 4..13 in slot order of (double)acc_alone_s *
+ * a[type][s] (0 for a slot that is not counted).  LINKED rows r - 1, r: both present, the same chain_id and (residx given)
+ * residx[r] == residx[r-1] + 1.  Heavy chain: the chain_id of row 0; light: every other chain id of the rows < Lab.  CDR rows: cdr_def
+ * in {1, 3, 5, 8, 10, 12}.  A liability belongs to its first row (the N, D, M, W or C).
+ *   0 sap_pos              sum of max(SAP_i, 0) / 2^30              10 n_glyc        N-x-[ST], x != P, three linked rows, N exposed
+ *   1 sap_pos_cdr          the same over atoms of CDR rows          11 n_deamid      N-[GS], two linked rows, N exposed
+ *   2 sap_pos_region       the same over atoms of region rows       12 n_isomer      D-[GS], D exposed
+ *   3 sap_max_res          max over present rows of                 13 n_frag        D-P, D exposed
+ *                          (row's sum of SAP_i / its atoms) / 2^30  14 n_met_ox      exposed Met
+ *   4 n_res_sap_pos        rows whose sum of SAP_i > 0              15 n_trp_ox      exposed Trp
+ *   5 n_res_sap_pos_region those in the region                      16 n_cys_free    Cys with a counted SG and no other counted SG of the
+ *   6 charge_heavy         (K + R) - (D + E), present heavy rows                     antibody with d2 <= 6.25 (2.5 A); no exposure rule
+ *   7 charge_light         the same for the light rows              17 n_liab        sum of 10-16
+ *   8 charge_product       column 6 x column 7                      18 n_liab_region those whose first row is a region row
+ *   9 n_his                His among the present rows               19 n_liab_cdr    those whose first row is a CDR row
+ *                                                                   20 n_atoms       counted atoms
+ * The divisions are float64 divisions of the exact integers converted to float64 (row sum / atom count, then / 2^30).  Without a present
+ * row column 3 is 0.
+ * rows: optional (B, L, 4) doubles per row: mean SAP of its atoms (column 3's quantity), rel / ref[type] (0 where ref is 0), the
+ * liability mask (bit k: the row starts a liability of column 10 + k), the charge (+1, -1, 0); rows >= Lab and absent rows are 0.
+ * Bounds: |w_j| <= P q_max.  With the shipped tables P q_max < 0.5 * 2^30 at P = 128 ... 1024 (q shrinks as P grows; a coarse surface of
+ * a few points has coarse reference areas and up to three times that, which is why q_max is an argument), at most 10 weighted and 14
+ * counted atoms per row: |SAP_i| < 5 * 2^30 Lab and a structure's sum < 70 * 2^30 Lab^2 in the worst case (every atom fully exposed and
+ * within the radius of every other), below 2^53 - the division by 2^30 is exact - up to Lab = 346 at P = 1024 as at P = 128; real
+ * antibodies stay four orders of magnitude below (7 10^11 at Lab = 231).  A problem with 140 P q_max Lab^2 >= 2^63 could leave int64 and
+ * is an argument error, as is Lab > 2048 (the row tables of the last kernel live in LDS).
+ * Three launches: (1) one workgroup per structure weighs the counted atoms and compacts them into the workspace, all of them as the
+ * i-list, those with w != 0 as the j-list; (2) grid (tile of 256 i-atoms, structure): one thread per atom i, the j-list through LDS in
+ * chunks of j_chunk atoms (0: the default of 2048, 40 KB; 1..2048 otherwise - it exists so that a test can force several chunks on a
+ * small complex), every lane reads the same j (a broadcast), SAP_i goes to the workspace; (3) one workgroup per structure for the row
+ * sums, the counts and the row.  Integer LDS atomics only, no global atomics, no allocation, no synchronisation: a structure's row
+ * depends on nothing but its own inputs.  The caller allocates the workspace (abx_developability_scores_workspace_bytes). */
+#define ABX_DEV_COLS 21
+typedef struct AbxDevelopabilityArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const unsigned char* region;                    /* optional (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs */
+    const int* chain_id; const int* residx;         /* (L); residx optional */
+    const int* cdr_def;                             /* (L) */
+    const long long* q; long long q_max;            /* [21][14] fixed-point weights of a sphere point, the largest |q| */
+    const double* a; const double* ref;             /* [21][14] area of a sphere point, [21] reference side-chain areas */
+    const int* points; int P;                       /* (B,L,14,2) of abx_interface_scores and its P */
+    double radius2;                                 /* squared radius of the SAP sphere (100.0), square Angstrom */
+    double exposed;                                 /* smallest relative side-chain area of an exposed residue (0.075), in [0, 1] */
+    double* out; long long out_stride;
+    double* rows;                                   /* optional (B,L,4) */
+    int j_chunk;                                    /* 0: the default */
+    int B, L, Lab;
+} AbxDevelopabilityArgs;
+long long abx_developability_scores_workspace_bytes(int B, int L);
+int abx_developability_scores(const AbxDevelopabilityArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
