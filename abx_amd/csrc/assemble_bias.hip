@@ -17,6 +17,8 @@
 // used by the model unless ABX_ASSEMBLE_BIAS is set.
 #include "common.h"
 #include "abx_hip.h"
+#include "split_dev.h"
+#include "grid_map.h"
 
 namespace {
 
@@ -27,10 +29,6 @@ constexpr int AB_OFF_BT = AB_NK * AB_IMG;                    // 24 576
 constexpr int AB_OFF_ST = AB_OFF_BT + AB_H * AB_BT * 4;      // + 16 512: per wave [32 rows][2] (dmean, rstd) of the projection's LayerNorm
 constexpr int AB_OFF_CONST = AB_OFF_ST + 4 * 32 * 2 * 4;     // + 1 024: gamma 192 | beta 192 | csum 32 | bias 32
 constexpr int AB_LDS = AB_OFF_CONST + (2 * AB_W + 2 * AB_H) * 4;      // 43 904 bytes; two workgroups per CU (the 96 registers of the prev_pair row: 168 VGPRs spill)
-
-__device__ __forceinline__ int ab_plane_off(int plane, int row, int half) {
-    return plane * (AB_H * 32) + row * 32 + ((half ^ ((row >> 3) & 1)) << 4);
-}
 
 __global__ __launch_bounds__(256, 2) void assemble_pair_bias_kernel(const float* __restrict__ pair_static, long long ps_b, const float* __restrict__ temb,
                                                                     const float* __restrict__ prev, const float* __restrict__ gamma,
@@ -45,9 +43,7 @@ __global__ __launch_bounds__(256, 2) void assemble_pair_bias_kernel(const float*
     float* stw = reinterpret_cast<float*>(lds + AB_OFF_ST);
     float* cst = reinterpret_cast<float*>(lds + AB_OFF_CONST);          // gamma | beta | csum | bias'
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5, r = lane & 31;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)L), i = (int)(wgid - (unsigned)b * (unsigned)L);
     const long long LL = (long long)L * L;
 
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(256, 2) void assemble_pair_bias_kernel(const float*
     for (int it = tid; it < AB_NK * 2 * AB_H * 2; it += 256) {          // 16-byte pieces: (kt, plane, head, k half)
         const int hh = it & 1, n = (it >> 1) & (AB_H - 1), p = (it >> 6) & 1, kt = it >> 7;
         const u32x4 v = *reinterpret_cast<const u32x4*>(Wp + ((long long)(kt * 2 + p) * AB_H + n) * 16 + hh * 8);
-        *reinterpret_cast<u32x4*>(lds + kt * AB_IMG + ab_plane_off(p, n, hh)) = v;
+        *reinterpret_cast<u32x4*>(lds + kt * AB_IMG + plane_off<AB_H>(p, n, hh)) = v;
     }
     for (int it = tid; it < 2 * AB_W + 2 * AB_H; it += 256)
         cst[it] = it < AB_W ? (gamma ? gamma[it] : 1.f) : it < 2 * AB_W ? (beta ? beta[it - AB_W] : 0.f) : it < 2 * AB_W + AB_H ? csum[it - 2 * AB_W] : (pbias ? pbias[it - 2 * AB_W - AB_H] : 0.f);
@@ -141,8 +137,8 @@ __global__ __launch_bounds__(256, 2) void assemble_pair_bias_kernel(const float*
 #pragma unroll
                 for (int e = 0; e < 4; ++e) split2h(v[2 * e], v[2 * e + 1], q0[e], q1[e]);
                 const u32x4 a0 = {q0[0], q0[1], q0[2], q0[3]}, a1 = {q1[0], q1[1], q1[2], q1[3]};
-                const u32x4 p0 = *reinterpret_cast<const u32x4*>(lds + kt * AB_IMG + ab_plane_off(0, r, h));
-                const u32x4 p1 = *reinterpret_cast<const u32x4*>(lds + kt * AB_IMG + ab_plane_off(1, r, h));
+                const u32x4 p0 = *reinterpret_cast<const u32x4*>(lds + kt * AB_IMG + plane_off<AB_H>(0, r, h));
+                const u32x4 p1 = *reinterpret_cast<const u32x4*>(lds + kt * AB_IMG + plane_off<AB_H>(1, r, h));
                 acc = mfma_split(a1, f16x8_lo(p0), acc);                    // a1 p2, a0 p1, a0 p0: smallest first
                 acc = mfma_split(a0, p1, acc);
                 acc = mfma_split(a0, p0, acc);

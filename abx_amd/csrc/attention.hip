@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "abx_hip.h"
+#include "split_dev.h"
 #include "tri_row_touch.h"
 
 namespace {
@@ -1045,10 +1046,8 @@ __global__ __launch_bounds__(NTH) void tri_attn8_kernel(const AbxTriAttn a) {
                     const unsigned off = __umul24((unsigned)min(c0 + 32 * (i / 3) + kt[i % 3], L - 1), sl4) + cb[i % 3];
 #pragma unroll
                     for (int p = 0; p < 2; ++p) {
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kb + off + p * RST),
-                                                         (__attribute__((address_space(3))) void*)(Kp + p * PLN + i * 1024), 16, 0, 0);
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vb + off + p * RST),
-                                                         (__attribute__((address_space(3))) void*)(Vp + p * PLN + i * 1024), 16, 0, 0);
+                        glds16(kb + off + p * RST, Kp + p * PLN + i * 1024);
+                        glds16(vb + off + p * RST, Vp + p * PLN + i * 1024);
                     }
                 }
                 for (int t = lane; t < KC4; t += 64)
@@ -1243,13 +1242,6 @@ __global__ __launch_bounds__(NTH) void tri_attn8_kernel(const AbxTriAttn a) {
     probe.finish();
 }
 
-template <int I0_, int I1_, class F> __device__ __forceinline__ void tri_static_for(F&& f) {
-    if constexpr (I0_ < I1_) {
-        f(std::integral_constant<int, I0_>{});
-        tri_static_for<I0_ + 1, I1_>(f);
-    }
-}
-
 // ---- triangle attention with the q | k | v projection of the row inside (split-f16) ------------------------------------------------
 // tri_attn8_kernel reads q | k | v of a pair row (b, s) from memory, where the LayerNorm -> Linear projection (gemm_as.hip) has just put
 // them: 576 fp32 per pair position written and read back, 57 GB per launch at 100 samples of L = 352, for values only this row's
@@ -1355,9 +1347,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
             constexpr int NI = decltype(ns_)::value * (RF_STAGE / 1024);
             const char* src = p.wp + (long long)hd * RF_HEAD_BYTES + s0 * RF_STAGE + lane * 16;
 #pragma unroll 8
-            for (int i = 0; i < NI; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024),
-                                                 (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
+            for (int i = 0; i < NI; ++i) glds16(src + i * 1024, dst + i * 1024);
         };
         // touch == 2: the RFT_N loads of k-group g of a row, one per 128-byte line.  They are inline assembly into ONE register that nothing
         // reads: the compiler places no wait for them (a wait of its own between the DMA instructions would drain the queue), and the
@@ -1503,7 +1493,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
         const float* zp = p.z + (long long)cur.b * p.zb + (long long)cur.s * p.zs + rf_walk_base(L, p.zl, wave, pr, hh);
         float lshift = 0.f;
         f32x2 ls2 = {0.f, 0.f}, lq2 = {0.f, 0.f};
-        tri_static_for<0, 3>([&](auto kg_) __attribute__((always_inline)) {
+        static_for<0, 3>([&](auto kg_) __attribute__((always_inline)) {
             constexpr int kg = decltype(kg_)::value;
             u32x4 a0[4], a1[4];
             if (has_tile) {
@@ -1536,7 +1526,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
                     a1[kk] = u32x4{q1[0], q1[1], q1[2], q1[3]};
                 }
             }
-            tri_static_for<0, RF_TILES>([&](auto t_) __attribute__((always_inline)) {
+            static_for<0, RF_TILES>([&](auto t_) __attribute__((always_inline)) {
                 constexpr int t = decltype(t_)::value;
                 constexpr int n = kg * RF_TILES + t;                                  // stage of the slot
                 // (the issuing wave's barriers (a), (b), (c): the stage's group has landed)
@@ -1567,7 +1557,7 @@ __global__ __launch_bounds__(TRI_THREADS) void tri_attn8_rowfused_kernel(const A
         // ---- the five column tiles: k 0..31 | k 32..47, v 0..15 | v 16..47 | q (16 hh ..) | q 32..47 (both halves)
         const float* cst_l = cst + 4 * hh;
         char* kdst = lds + (32 * wave + pr) * RST + hh * 16;            // (plane p1: + PLN; V planes: + 2 PLN)
-        tri_static_for<0, RF_TILES>([&](auto t_) __attribute__((always_inline)) {
+        static_for<0, RF_TILES>([&](auto t_) __attribute__((always_inline)) {
             constexpr int t = decltype(t_)::value;
             if (has_tile) {
                 // folded-LayerNorm epilogue (gemm_as plain_slice): register 4 i + c = packed column 8 i + 4 hh + c of the tile
@@ -1958,8 +1948,8 @@ extern "C" int abx_tri_rowpack(const AbxLinearPack* qkv, void* buf, AbxTriRowPac
 }
 
 extern "C" int abx_tri_attn_rowfused_ok(int L) {
-    // ("set and not 0", the reading of ABX_NO_OPM_FUSED; the Python side asks this function instead of reading the variable itself)
-    static const bool off = [] { const char* e = getenv("ABX_NO_TRI_ROWFUSED"); return e && *e && !(e[0] == '0' && e[1] == 0); }();
+    // (the Python side asks this function instead of reading the variable itself)
+    static const bool off = abx_env_on("ABX_NO_TRI_ROWFUSED");
     return (!off && L > 0 && L <= ABX_TRI_ROWFUSED_LMAX) ? 1 : 0;
 }
 

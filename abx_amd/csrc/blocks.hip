@@ -6,8 +6,6 @@
 #include <math.h>
 #include <string.h>
 
-#include <stdlib.h>
-
 #include "common.h"
 #include "abx_hip.h"
 
@@ -326,7 +324,7 @@ extern "C" int abx_tri_attn_block_fwd(const AbxTriAttnPack* wp, float* z, const 
     // attention's producer wave then stages them by DMA.  Bit-identical to the fp32 route (the attention computes exactly these pieces from
     // fp32 k | v) - and measured SLOWER: the attention does not gain (17.19 -> 17.42 ms per launch at 100 samples: its producer wave was
     // never on the critical path), the projection pays for the split and the 8-byte stores (13.7 -> 15.6 ms): profiles/r06h_kb_kvplanes.txt.
-    static const bool kv_planes_on = getenv("ABX_KV_PLANES") != nullptr;
+    static const bool kv_planes_on = abx_env_on("ABX_KV_PLANES");
     const int planes = (kv_planes_on && !exact && !attn_exact && abx_gemm_planes_ok(M2)) ? 1 : 0;
     // Row-fused route (attention.hip tri_attn8_rowfused_kernel): q | k | v of a pair row are projected inside the attention workgroup of that row
     // and never written - the launches are the pair-bias projection alone, the transpose, the fused kernel, the tail.  Chosen by L alone

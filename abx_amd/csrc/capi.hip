@@ -1,4 +1,5 @@
 // Library-level entry points: version, thread-local error text, device check.
+#include <stdlib.h>
 #include <string.h>
 
 #include <mutex>
@@ -40,6 +41,11 @@ int abx_ensure_dynamic_lds(const void* kernel, int bytes, const char* what) {
         return (int)e;
     }
     return ABX_OK;
+}
+
+bool abx_env_on(const char* name) {
+    const char* e = getenv(name);
+    return e && *e && !(e[0] == '0' && e[1] == 0);
 }
 
 extern "C" int abx_version(void) { return ABX_HIP_ABI_VERSION; }

@@ -19,6 +19,10 @@ int abx_check_launch(const char* what);
 // Returns 0 or the hipError_t; never called inside a graph capture after the first eager launch on a device.
 int abx_ensure_dynamic_lds(const void* kernel, int bytes, const char* what);
 
+// The one rule for the on / off environment switches (ABX_NO_GEMM_AS, ABX_NO_GEMM_SIDE, ABX_NO_DUAL_AS, ABX_NO_TRI_ROWFUSED, ABX_KV_PLANES):
+// ON when the variable is set, not empty and not "0".  abx_amd/ops.py env_on reads the Python-side switches by the same rule.
+bool abx_env_on(const char* name);
+
 #define ABX_REQUIRE(cond, msg)            \
     do {                                  \
         if (!(cond)) {                    \
@@ -64,6 +68,8 @@ inline int abx_plan_literal(AbxPlan* plan, const char* expr) {
 
 // 16-byte alignment of an operand address, and the clusters of it that the dispatchers share
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// a REQUIRED operand: present and 16-byte aligned (al16 alone passes a null pointer)
+inline bool al16_nonnull(const void* p) { return p && al16(p); }
 // float16 operand planes [k/16][plane][row][16] (abx_split_weights_f16 / activation images): row, plane, k-tile (and batch) strides in halves
 inline bool planes_ok(const void* p, long long s_row, long long s_plane, long long s_k, long long s_b = 0) {
     return al16(p) && s_row % 8 == 0 && s_plane % 8 == 0 && s_k % 8 == 0 && s_b % 8 == 0;

@@ -20,7 +20,6 @@
 // MFMA operand reads (lane -> m, lane>>5 -> k) are conflict-free; tile t+1 is prefetched into registers while tile t is on
 // the matrix cores; one barrier per k-tile.  Interior blocks run a guard-free path; edge blocks a fully predicated one.
 // Block ids are remapped so that the N-tiles of one M-panel run on the same XCD (private L2) back to back.
-#include <stdlib.h>
 #include "common.h"
 #include "abx_hip.h"
 #include "gemm_epilogue.h"
@@ -284,8 +283,10 @@ __global__ __launch_bounds__(256, MINW) void gemm_kernel(const AbxGemm g) {
     const int ntn = (g.N + BN - 1) / BN;
     // XCD-aware remap (blocks are dispatched round-robin over the 8 XCDs): give each XCD a contiguous range of tiles so the
     // N-tiles that share an A panel hit the same private L2.  Bijective for any grid size.
+    // (xcd_contiguous of grid_map.h written out in SIGNED arithmetic, as this kernel was always compiled: the shared unsigned function
+    // turns its two arithmetic shifts into logical ones - the same values, another instruction)
     int wgid = blockIdx.x;
-    if (!(g.tune & 1)) {
+    if (!(g.tune & ABX_TUNE_NO_REMAP)) {
         const int nwg = gridDim.x, bid = blockIdx.x;
         const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
         wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
@@ -419,7 +420,7 @@ int launch_cfg(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
 #undef GEMM_LAUNCH
 }
 
-// tuning variants of the main weight-GEMM configuration (selected by AbxGemm.tune bits 1..3; 0 = default)
+// tuning variants of the main weight-GEMM configuration (selected by AbxGemm.tune, ABX_TUNE_FORCE_MASK; 0 = default)
 template <int BK, int MINW>
 int launch_main_variant(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
     const long long mt = ((long long)g.M + 127) / 128, ntn = ((long long)g.N + 127) / 128;
@@ -517,7 +518,7 @@ int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, 
 // abx_gemm_as_dispatch (the walk pays from 1 024 blocks of 64 rows on).  Callers that switch the k | v format on it stay bit-invariant under
 // chunking: the attention kernel computes the same pieces from fp32 k | v as the projection writes as planes.
 extern "C" int abx_gemm_planes_ok(long long M) {
-    static const bool off = getenv("ABX_NO_GEMM_AS") != nullptr || getenv("ABX_NO_GEMM_SIDE") != nullptr;
+    static const bool off = abx_env_on("ABX_NO_GEMM_AS") || abx_env_on("ABX_NO_GEMM_SIDE");
     return (!off && (M + 63) / 64 >= 1024) ? 1 : 0;
 }
 
@@ -545,9 +546,10 @@ static int gemm_run(const AbxGemm* gp, hipStream_t st, AbxPlan* plan) {
     if (g.N <= 32) return launch_cfg<128, 32, 32, 32>(g, st, plan);
     if (g.N <= 64) return launch_cfg<128, 64, 32, 64>(g, st, plan);
     if (mt128 * (((long long)g.N + 127) / 128) * g.batch < 512) return launch_cfg<64, 64, 32, 32>(g, st, plan);
-    if (g.tune >> 1) {
+    const int variant = (g.tune & ABX_TUNE_FORCE_MASK) >> ABX_TUNE_FORCE_SHIFT;      // (this family reads its own bits only)
+    if (variant) {
         ABX_REQUIRE(!g.c_transposed && akc && g.sBn == 1, "abx_gemm: tuning variants exist for the plain weight GEMM only");
-        switch (g.tune >> 1) {
+        switch (variant) {
             case 1: return launch_main_variant<16, 2>(g, st, plan);
             case 2: return launch_main_variant<16, 4>(g, st, plan);
             case 3: return launch_cfg<128, 128, 64, 64, 16, 3>(g, st, plan);
@@ -557,7 +559,7 @@ static int gemm_run(const AbxGemm* gp, hipStream_t st, AbxPlan* plan) {
     // 128x192 tiles (96 accumulator registers per lane) when they waste no more columns than 128x128 tiles do: N = 192 (every
     // residual-stream update of the pair stack), 768 (q|k|v|gate, transition hidden), 544 ...
     const long long pad128 = ((g.N + 127) / 128) * 128, pad192 = ((g.N + 191) / 192) * 192;
-    if (pad192 <= pad128 && !(g.tune >> 1)) return launch_cfg<128, 192, 64, 96, 16, 2>(g, st, plan);
+    if (pad192 <= pad128 && !variant) return launch_cfg<128, 192, 64, 96, 16, 2>(g, st, plan);
     return launch_cfg<128, 128, 64, 64>(g, st, plan);
 }
 
@@ -568,7 +570,7 @@ static int gemm_side_run(const AbxGemm* main_gemm, const AbxGemm* side_gemm, hip
     if (int rc = gemm_prepare(main_gemm, g)) return rc;
     if (int rc = gemm_prepare(side_gemm, s2)) return rc;
     int rc = 0;
-    static const bool off = getenv("ABX_NO_GEMM_SIDE") != nullptr;          // (A / B measurements: always the two launches)
+    static const bool off = abx_env_on("ABX_NO_GEMM_SIDE");                 // (A / B measurements: always the two launches)
     if (!off && !abx_gemm_as_dispatch(g, &s2, st, &rc, plan)) return rc;      // A-stationary walk: the side rides in the ragged last N-tile
     // (plane output exists in the A-stationary kernel only: a caller asks for it when the launch qualifies - abx_gemm_planes_ok)
     ABX_REQUIRE(g.c_planes_from == 0, "abx_gemm_side: c_planes_from is served by the A-stationary kernel only (>= 65 536 rows, K = 192, N % 128 == 64, "

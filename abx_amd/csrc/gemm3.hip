@@ -26,370 +26,14 @@
 //      both operands this way).  LDS image [plane][row][32 B], the two 16-byte halves swapped on odd row-octets:
 //      conflict-free ds_read_b128 fragment reads (lane -> row, lane >> 5 -> k half).
 // Requirements (abx_gemm falls back to the exact kernel otherwise): K % 16 == 0, 16-byte aligned operand rows.
-// Epilogue: gemm_epilogue.h (shared with gemm.hip).
+// Epilogue: gemm_epilogue.h (shared with gemm.hip).  Main loop: gemm3_mainloop.h (shared with tails.hip).
 #include "common.h"
 #include "abx_hip.h"
 #include "gemm_epilogue.h"
-#include "rigid_dev.h"
+#include "gemm3_mainloop.h"
+#include "grid_map.h"
 
 namespace {
-
-constexpr int BK = 16;
-#ifndef ABX_SPLIT_MIN_TILES
-#define ABX_SPLIT_MIN_TILES 256     // smaller problems (sequence track, IPA) stay on the exact fp32 kernels
-#endif
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
-// 16 bytes per lane, global -> LDS at (wave-uniform) dst + lane * 16
-__device__ __forceinline__ void glds16(const void* src, char* dst_wave_base) {
-    __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)dst_wave_base, 16, 0, 0);
-}
-
-// A per-lane 32-bit byte offset as the compiler must see it AT the DMA instruction: defined in the same basic block, so that the
-// address is (scalar base) + zext(32-bit VGPR) and the load takes the scalar-base form `global_load_lds v, s[a:a+1]`.  Hoisted out
-// of the k loop the zero-extension becomes a 64-bit VGPR pair and every DMA instruction a v_lshl_add_u64 first (4 VALU instructions
-// and 4 VGPRs per k-step of the 128 x 128 tile).
-__device__ __forceinline__ unsigned vgpr32(unsigned o) {
-    asm volatile("" : "+v"(o));
-    return o;
-}
-
-template <int N> __device__ __forceinline__ void wait_vm_and_barrier() {
-    // own DMA writes for the next tile have landed (the newest N stay in flight), own LDS reads retired, then the block barrier
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
-// byte offset of (plane, row, 16-byte half) in a [2][ROWS][16] 16-bit tile image
-template <int ROWS>
-__device__ __forceinline__ int plane_off(int plane, int row, int half) {
-    return plane * (ROWS * 32) + row * 32 + ((half ^ ((row >> 3) & 1)) << 4);
-}
-
-// DMA source byte offsets (from the operand's batch base) of one wave for a [2][ROWS][16] 16-bit plane image stage: chunk c (1 KB of LDS) = wave * NL + i.
-// Surplus chunks (image not a multiple of 4 KB) and rows past the matrix re-read a valid row; their LDS bytes are never used
-// for valid outputs.
-template <int ROWS, int NL, int NPL = 2>
-__device__ __forceinline__ void plane_sources(long long s_plane, long long s_row, int r0, int R, unsigned (&off)[NL]) {
-    // (the k-tile stride is applied by the caller: one k-tile = 16 consecutive k of every row)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        int o = (wave * NL + i) * 1024 + lane * 16;                 // byte offset in the stage
-        if (o >= NPL * ROWS * 32) o -= NPL * ROWS * 32;             // surplus chunk: duplicate of the image start
-        const int plane = o / (ROWS * 32), rem = o % (ROWS * 32);
-        const int row = rem >> 5, hp = (rem >> 4) & 1;
-        const int half = hp ^ ((row >> 3) & 1);
-        const int gr = min(r0 + row, R - 1);
-        off[i] = (unsigned)((plane * s_plane + (long long)gr * s_row + 8 * half) * 2);
-    }
-}
-
-// Main loop of one output tile: acc += A' B for the operands of `g`; for the inline LayerNorm also the per-row partial sums
-// (ls, lq over this lane's k half, shifted by lshift).  Ends with all DMA drained and a block barrier (the LDS is free again).
-// SWAP: the MFMA operands trade places, acc[i][j] holds the TRANSPOSED 32 x 32 tile (rows = the tile's B rows / output columns, lane =
-// A row): the fused transition consumes it as the A operand of its second GEMM straight from the registers.
-// STATS: accumulate the inline LayerNorm partial sums and set lshift (the per-row shift of the operand, part of the statistics'
-// meaning); a caller that walks the same A rows again passes STATS = false and the lshift of its first walk.
-// AMODE 3: the A operand is resident in LDS (a_lds: BM fp32 rows of a_lds_stride bytes, k-contiguous; written by the caller before
-// the call): no A stage, no A DMA - the fused IPA tail chains its GEMMs this way.
-template <int BM, int BN, int WM, int WN, int AMODE, bool SWAP = false, bool STATS = true, int RING = 2, int JGO = 0>
-__device__ __forceinline__ void gemm3_mainloop(const AbxGemm& g, float* smem, int mt, int nt, int b, f32x16 (&acc)[WM / 32][WN / 32],
-                                               float (&ls)[WM / 32], float (&lq)[WM / 32], float (&lshift)[WM / 32],
-                                               const char* a_lds = nullptr, int a_lds_stride = 0) {
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int WAVES_N = BN / WN;
-    constexpr int A_IMG = AMODE == 3 ? 0 : (AMODE == 2 ? 2 * BM * 32 : BM * 64);   // bytes per A stage (planes: the two pieces a0, a1)
-    constexpr int NLA = AMODE == 3 ? 1 : (A_IMG + 4095) / 4096;                 // DMA instructions per wave per A tile
-    constexpr int A_STAGE = RING == 2 ? A_IMG : (A_IMG + 4095) / 4096 * 4096;
-    constexpr int B_IMG = 2 * BN * 32;
-    constexpr int NLB = (B_IMG + 4095) / 4096;
-    // with counted waits every wave must issue the same number of DMA instructions (stage padded to 4 KB multiples); the
-    // 2-stage protocol waits for everything, so the surplus chunks are simply skipped and the stage is the bare image
-    constexpr int B_STAGE = RING == 2 ? B_IMG : (B_IMG + 4095) / 4096 * 4096;   // (counted waits: the surplus chunks of a padded stage re-read the image start)
-    // RING stages per operand: tile t + RING - 1 is fetched (DMA) while tile t is consumed.  RING = 2 (tile t + 1 waited for at the
-    // end of step t) for the pair-stack GEMMs: with K <= 192 the fixed per-tile latencies (dispatch, first DMA, epilogue) weigh more
-    // than pipeline depth, and the smaller LDS footprint buys a third / fourth resident block per CU (40 KB with 128x128 tiles, 52 KB
-    // with 128x192) that hides them.  RING = 3 where ONE block owns the CU anyway (the IPA tail: 180 k-steps per block and nothing
-    // else to hide a DMA round trip): two tiles in flight, counted waits (vmcnt: results return in issue order, so every wave must
-    // issue the same NI instructions per tile - a stage is then padded to 4 KB and the surplus chunk loads rows nobody reads).
-    constexpr int NI = (AMODE == 3 ? 0 : NLA) + NLB;
-    constexpr int INFLIGHT = (RING - 2) * NI;                  // DMA instructions of this wave allowed to be outstanding at a wait
-
-    char* As = reinterpret_cast<char*>(smem);                 // RING stages
-    char* Bs = As + RING * A_STAGE;                           // RING stages
-    const int m0 = mt * BM, n0 = nt * BN;
-    // (the wave index as a scalar: the LDS destinations of the DMA instructions - m0 - are then SALU arithmetic, not a VALU
-    // computation + v_readfirstlane per instruction)
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int h = lane >> 5;
-
-    // ---- DMA sources: a block-uniform base pointer (advanced per k-tile) plus per-lane 32-bit byte offsets, so the loads
-    // use the scalar-base addressing form and cost no vector address arithmetic in the loop
-    unsigned offsA[NLA], offsB[NLB];
-    // The weight side first: its sources need two shifts, and with two stages its first k-tile is requested here, before the
-    // integer divisions of the A-row maps below - a block's first DMA round trip is exposed (nothing of this block can run
-    // before it lands), so it starts as early as the block knows where to read
-    const char* baseB = reinterpret_cast<const char*>(
-        g.B_split + ((g.batch_inner > 0 && g.A_split) ? (long long)(b / g.batch_inner) * g.sB3b + (long long)(b % g.batch_inner) * g.sB3i
-                                                      : (long long)b * g.sB3b));
-    plane_sources<BN, NLB>(g.sB3p, g.sB3n, n0, g.N, offsB);
-    const long long b_step = g.sB3k * 2;
-    const int nk = g.K / BK;
-    auto issue_b = [&](int tile) {
-        char* dst = Bs + (tile % RING) * B_STAGE + wave * NLB * 1024;
-        const char* src = baseB + tile * b_step;
-#pragma unroll
-        for (int i = 0; i < NLB; ++i)
-            if (RING > 2 || B_IMG % 4096 == 0 || (wave * NLB + i) * 1024 < B_IMG) glds16(src + vgpr32(offsB[i]), dst + i * 1024);
-    };
-    if constexpr (RING == 2) issue_b(0);
-    const char* baseA = nullptr;
-    long long a_step = 0;                                      // bytes per k-tile
-    if constexpr (AMODE == 3) {
-        offsA[0] = 0;
-    } else if constexpr (AMODE == 0) {
-        // offsets are relative to the tile's first row (to the batch base when the rows are pair-transposed)
-        const bool remap = g.a_pair_transpose > 0 || g.a_pair != 0;
-        const long long row0 = remap ? 0 : m0;
-        baseA = reinterpret_cast<const char*>(g.A + (long long)b * g.sAb + row0 * g.sAm);
-#pragma unroll
-        for (int i = 0; i < NLA; ++i) {
-            const int r = (wave * NLA + i) * 16 + (lane >> 2), p = lane & 3;
-            const int kq = p ^ ((r >> 2) & 3);                 // physical 16-byte slot p of row r holds logical k-quad kq
-            const int gri = min(m0 + r, g.M - 1);                    // (32-bit: M < 2^31; 64-bit divisions cost ~80 instructions)
-            long long gr = gri;
-            if (g.a_pair) {
-                // padded pair position (i, j) of the GEMM -> row of the unpadded pair tensor (pad columns re-read column L-1;
-                // their outputs are zeroed by the row scale / never stored)
-                int pi, pj;
-                if (g.c_split_tile) {
-                    pair_tile_decode(gri, g.pair_Lp, pi, pj);
-                    pi = min(pi, g.pair_L - 1);
-                    pj = min(pj, g.pair_L - 1);
-                } else {
-                    pi = gri / g.pair_Lp;
-                    pj = min(gri - pi * g.pair_Lp, g.pair_L - 1);
-                }
-                gr = g.a_pair_transpose > 0 ? (long long)pj * g.pair_L + pi : (long long)pi * g.pair_L + pj;
-            } else if (g.a_pair_transpose > 0) {
-                const int qi = gri / g.a_pair_transpose;
-                gr = (long long)(gri - qi * g.a_pair_transpose) * g.a_pair_transpose + qi;
-            }
-            offsA[i] = (unsigned)(((gr - row0) * g.sAm + kq * 4) * 4);
-        }
-        a_step = BK * 4;
-    } else if constexpr (AMODE == 1) {
-        baseA = reinterpret_cast<const char*>(g.A + (long long)b * g.sAb + m0);
-#pragma unroll
-        for (int i = 0; i < NLA; ++i) {
-            const int kl = (wave * NLA + i) * 2 + (lane >> 5), mq = lane & 31;     // LDS [k][BM]: 2 k-rows per instruction
-            const int gm = min(m0 + mq * 4, g.M - 4) - m0;                         // (M % 4 == 0: checked by the dispatch)
-            offsA[i] = (unsigned)(((long long)kl * g.sAk + gm) * 4);
-        }
-        a_step = (long long)BK * g.sAk * 4;
-    } else {
-        baseA = reinterpret_cast<const char*>(g.A_split + (g.batch_inner > 0 ? (long long)(b / g.batch_inner) * g.sA3b + (long long)(b % g.batch_inner) * g.sA3i
-                                                                                  : (long long)b * g.sA3b));
-        plane_sources<BM, NLA>(g.sA3p, g.sA3m, m0, g.M, offsA);
-        a_step = g.sA3k * 2;
-    }
-
-    auto issue_a = [&](int tile) {          // tile index clamped by the caller
-        if constexpr (AMODE == 3) return;
-        char* dst = As + (tile % RING) * A_STAGE + wave * NLA * 1024;
-        const char* src = baseA + tile * a_step;
-#pragma unroll
-        for (int i = 0; i < NLA; ++i)
-            if (RING > 2 || A_IMG % 4096 == 0 || (wave * NLA + i) * 1024 < A_IMG) glds16(src + vgpr32(offsA[i]), dst + i * 1024);
-    };
-
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    float m2048 = -2048.0f;
-    asm volatile("" : "+v"(m2048));                           // (a VGPR constant of split2h_mix; not rematerialised into an SGPR)
-    const bool relu = g.a_relu != 0;
-    const bool ln_inline = g.ln_csum != nullptr && g.ln_stats == nullptr;
-    f32x2 ls2[TM], lq2[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        ls[i] = lq[i] = 0.f;
-        if constexpr (STATS) lshift[i] = 0.f;
-        ls2[i] = lq2[i] = (f32x2){0.f, 0.f};
-    }
-
-    // prologue
-#pragma unroll
-    for (int r = 0; r < RING - 1; ++r) {
-        issue_a(min(r, nk - 1));
-        if constexpr (RING != 2) issue_b(min(r, nk - 1));
-    }
-    wait_vm_and_barrier<INFLIGHT>();
-
-    // per-lane LDS fragment offsets
-    int offA[TM][(AMODE == 0 || AMODE == 3) ? 2 : 1];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int r = wm * WM + i * 32 + (lane & 31);
-        if constexpr (AMODE == 3) {
-            offA[i][0] = r * a_lds_stride + (2 * h) * 16;
-            offA[i][1] = r * a_lds_stride + (2 * h + 1) * 16;
-        } else if constexpr (AMODE == 0) {
-            const int x = (r >> 2) & 3;
-            offA[i][0] = r * 64 + (((2 * h) ^ x) << 4);
-            offA[i][1] = r * 64 + (((2 * h + 1) ^ x) << 4);
-        } else if constexpr (AMODE == 1) {
-            offA[i][0] = (8 * h) * (BM * 4) + r * 4;
-        } else {
-            offA[i][0] = plane_off<BM>(0, r, h);
-        }
-    }
-    int offB[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) offB[j] = plane_off<BN>(0, wn * WN + j * 32 + (lane & 31), h);
-
-    // a wave whose 32 rows all lie beyond M (the last row tile of a ragged M: e.g. the 4th wave of the third 128-row tile of the
-    // L = 352 contraction) takes part in the DMA and the barriers but skips its B-fragment reads and MFMAs
-    const bool rows_live = m0 + wm * WM < g.M;
-    if (!rows_live) {
-        for (int t = 0; t < nk; ++t) {
-            issue_b(min(t + RING - 1, nk - 1));
-            issue_a(min(t + RING - 1, nk - 1));
-            wait_vm_and_barrier<INFLIGHT>();
-        }
-    } else
-    for (int t = 0; t < nk; ++t) {
-        // next tiles
-        issue_b(min(t + RING - 1, nk - 1));
-        issue_a(min(t + RING - 1, nk - 1));
-        const char* as = AMODE == 3 ? a_lds + t * 64 : As + (t % RING) * A_STAGE;
-        const char* bs = Bs + (t % RING) * B_STAGE;
-        u32x4 a[TM][2];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            if constexpr (AMODE == 2) {
-#pragma unroll
-                for (int p = 0; p < 2; ++p) a[i][p] = *reinterpret_cast<const u32x4*>(as + offA[i][0] + p * (BM * 32));
-            } else {
-                float x[8];
-                if constexpr (AMODE == 0 || AMODE == 3) {
-                    const f32x4 lo = *reinterpret_cast<const f32x4*>(as + offA[i][0]);
-                    const f32x4 hi = *reinterpret_cast<const f32x4*>(as + offA[i][1]);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) { x[c] = lo[c]; x[4 + c] = hi[c]; }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) x[e] = *reinterpret_cast<const float*>(as + offA[i][0] + e * (BM * 4));
-                }
-                if (ln_inline) {
-                    // statistics of the row from this lane's 8 k (the other k half sits in lane ^ 32), shifted by the row's
-                    // first element so that E[x^2] - mean^2 does not cancel when |mean| >> sigma.  Packed math: two elements
-                    // per VALU instruction (even / odd partial sums, folded after the loop)
-                    if (STATS && t == 0) lshift[i] = __shfl(x[0], lane & 31, 64);
-                    const f32x2 sh2 = {lshift[i], lshift[i]};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        f32x2 xp = {x[2 * e], x[2 * e + 1]};
-                        xp -= sh2;
-                        if constexpr (STATS) {
-                            ls2[i] += xp;
-                            lq2[i] = __builtin_elementwise_fma(xp, xp, lq2[i]);
-                        }
-                        x[2 * e] = xp[0];
-                        x[2 * e + 1] = xp[1];
-                    }
-                }
-                if (relu) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) x[e] = fmaxf(x[e], 0.f);
-                }
-                unsigned q0[4], q1[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    split2h_mix(x[2 * e], x[2 * e + 1], m2048, q0[e], q1[e]);
-                }
-                a[i][0] = u32x4{q0[0], q0[1], q0[2], q0[3]};
-                a[i][1] = u32x4{q1[0], q1[1], q1[2], q1[3]};
-            }
-        }
-        // product terms, smallest first (SplitTerms); the B fragments are fetched per group of JG sub-tiles (register budget);
-        // consecutive MFMAs hit different accumulators
-        using T = SplitTerms;
-        constexpr int JG = JGO > 0 ? JGO : (TN > 3 ? (TN % 3 == 0 ? 3 : 2) : TN);
-#pragma unroll
-        for (int j0 = 0; j0 < TN; j0 += JG) {
-            u32x4 bb[JG][3];
-#pragma unroll
-            for (int j = 0; j < JG; ++j)
-#pragma unroll
-                for (int p = 0; p < 2; ++p) bb[j][p] = *reinterpret_cast<const u32x4*>(bs + offB[j0 + j] + p * (BN * 32));
-#pragma unroll
-            for (int j = 0; j < JG; ++j) bb[j][2] = f16x8_lo(bb[j][0]);
-#pragma unroll
-            for (int term = 0; term < T::N; ++term)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < JG; ++j)
-                        acc[i][j0 + j] = SWAP ? mfma_split(bb[j][T::B[term]], a[i][T::A[term]], acc[i][j0 + j])
-                                              : mfma_split(a[i][T::A[term]], bb[j][T::B[term]], acc[i][j0 + j]);
-        }
-        wait_vm_and_barrier<INFLIGHT>();
-    }
-    if constexpr (AMODE != 2) {
-        // the planes hold w * 2^b_exp, the activations went in as x * 2^ABX_F16_A_EXP: exact power-of-two rescale
-        // (plane x plane: the images were written as x 2^-4 and y 2^4, nothing to undo)
-        const float cs = __builtin_ldexpf(1.0f, -ABX_F16_A_EXP - g.b_exp);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] *= cs;
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        ls[i] = ls2[i][0] + ls2[i][1];
-        lq[i] = lq2[i][0] + lq2[i][1];
-    }
-    // drain the (redundant) tail DMA before the epilogue reuses the LDS
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// LayerNorm row statistics of this M-panel -> st_lds [BM][2] (mean - shift, rstd); returns whether the GEMM is LN-folded
-template <int BM, int BN, int WM, int WN, bool EDGE>
-__device__ __forceinline__ bool gemm3_row_stats(const AbxGemm& g, float* st_lds, int mt, int b, const float (&ls)[WM / 32],
-                                                const float (&lq)[WM / 32]) {
-    constexpr int TM = WM / 32, WAVES_N = BN / WN;
-    const int m0 = mt * BM;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N, h = lane >> 5;
-    const bool ln_inline = g.ln_csum != nullptr && g.ln_stats == nullptr;
-    const float* gstats = g.ln_stats ? g.ln_stats + 2 * (long long)b * g.sSb : nullptr;
-    if (gstats) {
-        for (int idx = threadIdx.x; idx < 2 * BM; idx += 256) {
-            const int m = m0 + (idx >> 1);
-            st_lds[idx] = (!EDGE || m < g.M) ? gstats[2 * (long long)m + (idx & 1)] : 0.f;
-        }
-    } else if (ln_inline) {
-        const float invK = 1.0f / (float)g.K;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const float sm = ls[i] + __shfl_xor(ls[i], 32, 64), sq = lq[i] + __shfl_xor(lq[i], 32, 64);
-            if (wn == 0 && h == 0) {                            // the wn waves hold identical copies
-                const int row = wm * WM + i * 32 + lane;
-                const float dm = sm * invK;
-                st_lds[2 * row] = dm;                           // the operand was shifted: only (mean - shift) remains
-                st_lds[2 * row + 1] = 1.0f / sqrtf(fmaxf(sq * invK - dm * dm, 0.f) + g.ln_eps);
-            }
-        }
-    }
-    return gstats != nullptr || ln_inline;
-}
 
 template <int BM, int BN, int WM, int WN, int AMODE, bool EDGE, bool TS, bool OLN = false, bool PROBE = true, int RING = 2, int JGO = 0>
 __device__ __forceinline__ void gemm3_block(const AbxGemm& g, float* smem, int mt, int nt, int b) {
@@ -439,7 +83,7 @@ __device__ __forceinline__ void gemm3_dual_block(const AbxGemm& g, float* smem, 
 // z is walked once instead of twice, the product rows twice as before.  Every accumulator receives the products of the two-tile form
 // in the same order and the gate is the same expression: bit-identical results.  MEASURED SLOWER (10.97 vs 10.30 ms at 100 samples of
 // L = 352, profiles/r06c_kb_dual.txt): 96 + 48 live accumulator registers leave two blocks per CU where the two-tile form runs three;
-// kept behind AbxGemm.tune bit 7 as the record of the experiment and a cross-check (test_gemm_dual_walk_variants_bit_identical).
+// kept behind ABX_TUNE_DUAL_1WALK as the record of the experiment and a cross-check (test_gemm_dual_walk_variants_bit_identical).
 template <bool EDGE>
 __device__ __forceinline__ void gemm3_dual1_block(const AbxGemm& g, float* smem, int mt, int b) {
     constexpr int BM = 128, BN = 192, WM = 32, BH = 96, TH = BH / 32, TN = BN / 32;
@@ -491,9 +135,7 @@ __global__ __launch_bounds__(256, 2) void gemm3_dual1_kernel(const AbxGemm g) {
     constexpr int EPI = 4 * 128 + 4 * 32 * (3 * 32 + 4);
     __shared__ __attribute__((aligned(16))) float smem[OPER > EPI ? OPER : EPI];
     const int ntm = (g.M + 127) / 128;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)ntm), mt = (int)(wgid - (unsigned)b * (unsigned)ntm);
     const ClockProbe probe(g.clock_probe);
     if ((mt + 1) * 128 <= g.M && g.N == 192) gemm3_dual1_block<false>(g, smem, mt, b);
@@ -520,7 +162,7 @@ __global__ __launch_bounds__(256, MINW) void gemm3_kernel(const AbxGemm g) {
     const ClockProbe probe(g.clock_probe);
     constexpr bool PROBE = !(BM == 128 && BN == 128 && MINW >= 4);      // (no register for it at four blocks per CU: gemm_epilogue.h)
 #ifdef ABX_PERSIST
-    if (g.tune & 256) {
+    if (g.tune & ABX_TUNE_PERSIST) {
         // experiment: resident blocks walk the tiles of their XCD's range (slot s takes x0 + s, x0 + s + slots, ...)
         const long long total = (long long)per_batch * g.batch;
         const long long q = total >> 3, r = total & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
@@ -539,12 +181,7 @@ __global__ __launch_bounds__(256, MINW) void gemm3_kernel(const AbxGemm g) {
     }
 #endif
     // (32-bit: the dispatch keeps the grid below 2^31 tiles; a 64-bit division is ~80 instructions in front of the block's first DMA)
-    unsigned wgid = blockIdx.x;
-    if (!(g.tune & 1)) {
-        const unsigned nwg = gridDim.x, bid = blockIdx.x;
-        const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const unsigned wgid = (g.tune & ABX_TUNE_NO_REMAP) ? blockIdx.x : xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)per_batch);
     const int rem = (int)(wgid - (unsigned)b * (unsigned)per_batch);
     const int mt = rem / ntn, nt = rem % ntn;
@@ -564,9 +201,7 @@ __global__ __launch_bounds__(256, 4) void gemm3_side_kernel(const AbxGemm g, con
     __shared__ __attribute__((aligned(16))) float smem[35840 / 4];
     const unsigned ntn = (g.N + BN - 1) / BN, ntm = (g.M + BM - 1) / BM, per_batch = ntn * ntm;
     const unsigned stm = (s2.M + BM - 1) / BM, ts = stm * (unsigned)s2.batch;
-    const unsigned total = gridDim.x, bid = blockIdx.x;
-    const unsigned q = total >> 3, r = total & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned total = gridDim.x, wgid = xcd_contiguous(blockIdx.x, total);
     // slot w is a side tile when floor((w + 1) ts / total) > floor(w ts / total); it is side tile floor(w ts / total)
     const unsigned sw = (unsigned)(((unsigned long long)wgid * ts) / total), sw1 = (unsigned)(((unsigned long long)(wgid + 1) * ts) / total);
     if (sw1 > sw) {
@@ -583,7 +218,7 @@ __global__ __launch_bounds__(256, 4) void gemm3_side_kernel(const AbxGemm g, con
     else gemm3_block<BM, BN, 32, 128, 0, true, false, false, false>(g, smem, mt, nt, b);
 }
 
-// Probe (round 6, AbxGemm.tune bit 9): the skinny N <= 32 projections - HBM streams of 9.5 / 6.3 GB at 4.2 - 4.5 TB/s - with a deeper operand ring
+// Probe (round 6, ABX_TUNE_NARROW_RING_MASK): the skinny N <= 32 projections - HBM streams of 9.5 / 6.3 GB at 4.2 - 4.5 TB/s - with a deeper operand ring
 // (RING k-tiles of A in flight per block instead of one); bit-identical to gemm3_kernel<128, 32, 32, 32, 0, TS, 6>
 template <bool TS, int RING, int MINW>
 __global__ __launch_bounds__(256, MINW) void gemm3_narrow_ring_kernel(const AbxGemm g) {
@@ -592,9 +227,7 @@ __global__ __launch_bounds__(256, MINW) void gemm3_narrow_ring_kernel(const AbxG
     constexpr int EPI = 2 * BM + 4 * 32 * ((TS ? 32 : 32) + 4);
     __shared__ __attribute__((aligned(16))) float smem[OPER > EPI ? OPER : EPI];
     const int ntm = (g.M + BM - 1) / BM;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)ntm), mt = (int)(wgid - (unsigned)b * (unsigned)ntm);
     if ((mt + 1) * BM <= g.M && BN <= g.N) gemm3_block<BM, BN, 32, 32, 0, false, TS, false, true, RING>(g, smem, mt, 0, b);
     else gemm3_block<BM, BN, 32, 32, 0, true, TS, false, true, RING>(g, smem, mt, 0, b);
@@ -608,9 +241,7 @@ __global__ __launch_bounds__(256, MINW) void gemm3_oln_kernel(const AbxGemm g) {
     constexpr int EPI = 2 * BM + 4 * 32 * (TGW * 32 + 4);
     __shared__ __attribute__((aligned(16))) float smem[OPER > EPI ? OPER : EPI];
     const int ntm = (g.M + BM - 1) / BM;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)ntm), mt = (int)(wgid - (unsigned)b * (unsigned)ntm);
     const bool interior = (mt + 1) * BM <= g.M && BN <= g.N;
     if (interior) gemm3_block<BM, BN, WM, WN, 0, false, false, true>(g, smem, mt, 0, b);
@@ -628,9 +259,7 @@ __global__ __launch_bounds__(256, MINW) void gemm3_dual_kernel(const AbxGemm g) 
     constexpr int EPI = 4 * BM + 4 * 32 * (TGW * 32 + 4);
     __shared__ __attribute__((aligned(16))) float smem[OPER > EPI ? OPER : EPI];
     const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + BM - 1) / BM;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int per_batch = ntn * ntm;
     const int b = (int)(wgid / (unsigned)per_batch);
     const int rem = (int)(wgid - (unsigned)b * (unsigned)per_batch);
@@ -784,9 +413,7 @@ __global__ __launch_bounds__(256, MINB) void gemm3_mlp_kernel(const AbxGemm g) {
     constexpr int EPI = 2 * 128 + 4 * 32 * (3 * 32 + 4);
     __shared__ __attribute__((aligned(16))) float smem[OPER > EPI ? OPER : EPI];
     const int ntm = (g.M + 127) / 128;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)ntm), mt = (int)(wgid - (unsigned)b * (unsigned)ntm);
     const ClockProbe probe(g.clock_probe);
     if ((mt + 1) * 128 <= g.M && g.N2 == 192) gemm3_mlp_block<false>(g, smem, mt, b);
@@ -799,9 +426,7 @@ constexpr int MLP3_LDS = 3 * (128 * 64 + 2 * 128 * 32) + 2 * 2 * 192 * 32 + 2 * 
 __global__ __launch_bounds__(256, 2) void gemm3_mlp3_kernel(const AbxGemm g) {
     extern __shared__ __attribute__((aligned(16))) float mlp3_smem[];
     const int ntm = (g.M + 127) / 128;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)ntm), mt = (int)(wgid - (unsigned)b * (unsigned)ntm);
     const ClockProbe probe(g.clock_probe);
     if ((mt + 1) * 128 <= g.M && g.N2 == 192) gemm3_mlp_block<false, 3>(g, mlp3_smem, mt, b);
@@ -972,14 +597,12 @@ __device__ __forceinline__ void gemm3_gtail2w_block(const AbxGemm& g, float* sme
 
 constexpr int GT_LDS = 2 * 128 * 64 + 2 * 2 * 96 * 32 + 2 * 2 * 192 * 32 + 3 * 128 * 64 + 2 * GT_NG * 4;      // 79 360 bytes (two blocks per CU)
 
-// the round-5 form (two walks over the z rows, one per gate chunk of 96): AbxGemm.tune bit 6, kept for A / B runs and as a cross-check
+// the round-5 form (two walks over the z rows, one per gate chunk of 96): ABX_TUNE_GTAIL_2WALK, kept for A / B runs and as a cross-check
 // (test_gemm_gated_tail_walk_variants_bit_identical)
 __global__ __launch_bounds__(256, 2) void gemm3_gtail2w_kernel(const AbxGemm g) {
     extern __shared__ __attribute__((aligned(16))) float gt_smem[];
     const int ntm = (g.M + 127) / 128;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)ntm), mt = (int)(wgid - (unsigned)b * (unsigned)ntm);
     const ClockProbe probe(g.clock_probe);
     if ((mt + 1) * 128 <= g.M && g.N2 == 192) gemm3_gtail2w_block<false>(g, gt_smem, mt, b);
@@ -1136,9 +759,7 @@ __device__ __forceinline__ void gemm3_gtail_block(const AbxGemm& g, float* smem,
 __global__ __launch_bounds__(256, 2) void gemm3_gtail_kernel(const AbxGemm g) {
     extern __shared__ __attribute__((aligned(16))) float gt_smem[];
     const int ntm = (g.M + 127) / 128;
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)ntm), mt = (int)(wgid - (unsigned)b * (unsigned)ntm);
     const ClockProbe probe(g.clock_probe);
     if ((mt + 1) * 128 <= g.M && g.N2 == 192 && g.N == 192) gemm3_gtail_block<false>(g, gt_smem, mt, b);
@@ -1146,333 +767,13 @@ __global__ __launch_bounds__(256, 2) void gemm3_gtail_kernel(const AbxGemm g) {
     probe.finish();
 }
 
-// ---- IPA layer tail (score_network.py:126-163 per layer: the single representation after the attention) in ONE kernel:
-//     s <- LN1(s + feat W_final + b)                                 attention_module.final_proj + attention_layer_norm
-//     s <- LN2(s + relu(relu(s W0 + b0) W2 + b2) W4 + b4)            transition_module.0 / .2 / .4 + transition_layer_norm
-// A block owns 32 rows and all 256 channels: 4 waves x (32 rows x 64 columns), the main loop with swapped MFMA operands (lane = row, 16
-// columns per 32 x 32 tile in registers), so bias / ReLU / residual are lane-local and the LayerNorm statistics need one 32-lane
-// exchange + a 4-wave fold through LDS.  The activations between the GEMMs never leave the CU: each epilogue writes the block's
-// 32 x 256 tile to one of two LDS buffers (1040-byte rows: conflict-free 16-byte fragment reads), which IS the A operand of the next
-// main loop (AMODE 3); only the weight planes stream (DMA, 24 KB per k-tile).  Six launches per layer become one; the arithmetic of a
-// row does not depend on the batch (one instantiation for every size).
-constexpr int IT_C = 256;
-constexpr int IT_ASTR = IT_C * 4 + 16;                                      // bytes per activation row in LDS
-constexpr int IT_RING = 4;
-constexpr int IT_OPER = IT_RING * (4096 + 2 * IT_C * 32);                   // main-loop stages: A 3 x 4 KB (padded) + weights 3 x 16 KB
-constexpr int IT_LDS = IT_OPER + 2 * 32 * IT_ASTR + 2 * 4 * 32 * 4;
-
-__global__ __launch_bounds__(256, 1) void ipa_tail_kernel(const AbxIpaTail a) {
-    constexpr int BM = 32, BN = IT_C, WM = 32, WN = 64, TN = 2;
-    extern __shared__ __attribute__((aligned(16))) float it_smem[];
-    char* lds = reinterpret_cast<char*>(it_smem);
-    char* act[2] = {lds + IT_OPER, lds + IT_OPER + 32 * IT_ASTR};
-    float* red = reinterpret_cast<float*>(lds + IT_OPER + 2 * 32 * IT_ASTR);    // [2][4][32]
-    const int mt = blockIdx.x, m0 = mt * BM;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, row = lane & 31;
-    const int grc = min(m0 + row, a.M - 1);
-    // column of accumulator register r of tile j (swapped operands): wave * 64 + j * 32 + 8 (r >> 2) + 4 h + (r & 3)
-    const int colb = wave * WN + 4 * h;
-
-    AbxGemm g = {};
-    g.M = a.M; g.N = IT_C; g.batch = 1; g.b_f16 = 1;
-    g.sB3k = 2 * IT_C * 16; g.sB3p = IT_C * 16; g.sB3n = 16;
-    f32x16 acc[1][TN];
-    float ls[1], lq[1], lsh[1];
-    float x[TN][16];
-
-    // rows of 4 consecutive channels <-> registers 4 q .. 4 q + 3 of tile j
-    auto for_groups = [&](auto&& fn) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) fn(j, q, colb + j * 32 + 8 * q);
-    };
-    // LayerNorm over the 256 channels of this lane's row (values in x): two passes like torch, gamma / beta applied in place
-    auto layer_norm = [&](const float* gamma, const float* beta) {
-        float sm = 0.f;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sm += x[j][r];
-        sm += __shfl_xor(sm, 32, 64);
-        if (h == 0) red[wave * 32 + row] = sm;
-        __syncthreads();
-        const float mean = (red[row] + red[32 + row] + red[64 + row] + red[96 + row]) * (1.0f / IT_C);
-        float sq = 0.f;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { x[j][r] -= mean; sq = fmaf(x[j][r], x[j][r], sq); }
-        sq += __shfl_xor(sq, 32, 64);
-        if (h == 0) red[128 + wave * 32 + row] = sq;
-        __syncthreads();
-        const float var = (red[128 + row] + red[160 + row] + red[192 + row] + red[224 + row]) * (1.0f / IT_C);
-        const float rstd = 1.0f / sqrtf(var + a.ln_eps);
-        for_groups([&](int j, int q, int c) {
-            const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[j][4 * q + e] = x[j][4 * q + e] * rstd * gm[e] + bt[e];
-        });
-    };
-    auto to_lds = [&](char* buf) {
-        for_groups([&](int j, int q, int c) {
-            *reinterpret_cast<f32x4*>(buf + row * IT_ASTR + c * 4) = (f32x4){x[j][4 * q], x[j][4 * q + 1], x[j][4 * q + 2], x[j][4 * q + 3]};
-        });
-    };
-    auto bias_act = [&](const float* bias, bool relu) {
-        for_groups([&](int j, int q, int c) {
-            const f32x4 bi = *reinterpret_cast<const f32x4*>(bias + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float v = acc[0][j][4 * q + e] + bi[e];
-                x[j][4 * q + e] = relu ? relu_keep_nan(v) : v;
-            }
-        });
-    };
-
-    // ---- 1: s + feat W_final + b -> LN1 -> act[0] (and kept in registers: the residual of the transition)
-    if (a.partial) {
-        // feat W_final comes as n_partial K-slice products of a split-K GEMM launched before (the 132-k-step chain of this block becomes
-        // 12 k-steps of 11 x as many blocks): summed here in slice order, then the bias
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
-        for (int sl = 0; sl < a.n_partial; ++sl) {
-            const float* pp = a.partial + (long long)sl * a.s_partial + (long long)grc * IT_C;
-            for_groups([&](int j, int q, int c) {
-                const f32x4 pv = *reinterpret_cast<const f32x4*>(pp + c);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[0][j][4 * q + e] += pv[e];
-            });
-        }
-    } else {
-        g.A = a.feat; g.sAm = a.s_feat; g.sAk = 1; g.K = a.K1;
-        g.B_split = a.W_final; g.b_exp = a.e_final;
-        gemm3_mainloop<BM, BN, WM, WN, 0, true, false, IT_RING>(g, it_smem, mt, 0, 0, acc, ls, lq, lsh);
-    }
-    bias_act(a.b_final, false);
-    for_groups([&](int j, int q, int c) {
-        const f32x4 rv = *reinterpret_cast<const f32x4*>(a.s + (long long)grc * a.s_s + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[j][4 * q + e] += rv[e];
-    });
-    layer_norm(a.ln1_w, a.ln1_b);
-    float res[TN][16];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) res[j][r] = x[j][r];
-    to_lds(act[0]);
-    __syncthreads();
-    // ---- 2, 3: relu(. W0 + b0) -> act[1], relu(. W2 + b2) -> act[0]
-    g.K = IT_C;
-    g.B_split = a.W_t0; g.b_exp = a.e_t0;
-    gemm3_mainloop<BM, BN, WM, WN, 3, true, false, IT_RING>(g, it_smem, mt, 0, 0, acc, ls, lq, lsh, act[0], IT_ASTR);
-    bias_act(a.b_t0, true);
-    to_lds(act[1]);
-    __syncthreads();
-    g.B_split = a.W_t2; g.b_exp = a.e_t2;
-    gemm3_mainloop<BM, BN, WM, WN, 3, true, false, IT_RING>(g, it_smem, mt, 0, 0, acc, ls, lq, lsh, act[1], IT_ASTR);
-    bias_act(a.b_t2, true);
-    to_lds(act[0]);
-    __syncthreads();
-    // ---- 4: residual + . W4 + b4 -> LN2 -> act[1] -> the rows of s, coalesced
-    g.B_split = a.W_t4; g.b_exp = a.e_t4;
-    gemm3_mainloop<BM, BN, WM, WN, 3, true, false, IT_RING>(g, it_smem, mt, 0, 0, acc, ls, lq, lsh, act[0], IT_ASTR);
-    bias_act(a.b_t4, false);
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) x[j][r] += res[j][r];
-    layer_norm(a.ln2_w, a.ln2_b);
-    if (a.range_flag) {                                         // range safety (AbxGemm.range_flag): a row that left the split range is NaN by now
-        float z = 0.f;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) z = fmaf(x[j][r], 0.f, z);
-        if (__any(z != z) && lane == 0) atomicOr(a.range_flag, a.range_tag);
-    }
-    to_lds(act[1]);
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < BM * (IT_C / 4); idx += 256) {
-        const int r = idx / (IT_C / 4), c4 = idx % (IT_C / 4);
-        if (m0 + r < a.M)
-            *reinterpret_cast<f32x4*>(a.s + (long long)(m0 + r) * a.s_s + c4 * 4) = *reinterpret_cast<const f32x4*>(act[1] + r * IT_ASTR + c4 * 16);
-    }
-    // ---- 5 (optional): affine_update (256 -> 6, fp32 FMA chain in channel order) and the frame update of the block's residues
-    if (a.W_aff) {
-        const int r = threadIdx.x >> 3, o = threadIdx.x & 7;
-        if (o < 6) {
-            const float* y = reinterpret_cast<const float*>(act[1] + r * IT_ASTR);
-            float u = 0.f;
-#pragma unroll 8
-            for (int c = 0; c < IT_C; ++c) u = fmaf(y[c], a.W_aff[c * 6 + o], u);
-            red[r * 8 + o] = u + a.b_aff[o];
-        }
-        __syncthreads();
-        if (threadIdx.x < BM && m0 + threadIdx.x < a.M)
-            rigid_update_row(m0 + threadIdx.x, red + threadIdx.x * 8, a.fixed, a.init_q, a.init_t, a.cur_q, a.cur_t, a.cur_R, a.delta_q, a.pscale);
-    }
-}
-
-// ---- Per-residue heads on the final single representation in ONE kernel: the torsion ResNet (sidechain.py:28-62), the SequenceHead MLP
-// and - on the last pass - the PredictedLDDTHead MLP (head.py:143-226).  Thirteen (eighteen) launches of 352 ... 35 200-row GEMMs and
-// LayerNorms otherwise, each a latency chain of its own at small batches.
-//     t  = relu(s) W_act + b + relu(s0) W_init + b;   t += relu(relu(t) W_r0 + b) W_r1 + b;   t += relu(relu(t) W_r2 + b) W_r3 + b
-//     un = relu(t) W_proj + b                                            (14 columns: the unnormalised torsion sin / cos)
-//     logits = relu(relu(LN_s(s) W_s1 + b) W_s3 + b) W_s5 + b            (20 columns);  pLDDT logits likewise (50 columns)
-// A block owns 32 rows; 4 waves x (32 rows x 32 of the 128 hidden columns), swapped MFMA operands (lane = row), activations in LDS
-// between the GEMMs (AMODE 3 main loops as in ipa_tail_kernel), only the weight planes stream.  The 14 / 20 / 50-column projections
-// run as 128-column GEMMs on zero-padded planes (negligible work; one code path).  Split-f16 arithmetic throughout.
-constexpr int HT_C = 256, HT_H = 128;
-constexpr int HT_ASTR = HT_C * 4 + 16, HT_HSTR = HT_H * 4 + 16;             // bytes per activation row in LDS
-constexpr int HT_RING = 4;
-constexpr int HT_OPER = HT_RING * (2 * HT_H * 32);                           // 4 weight stages of 8 KB
-constexpr int HT_LDS = HT_OPER + 2 * 32 * HT_ASTR + 2 * 32 * HT_HSTR;
-
-__global__ __launch_bounds__(256, 1) void heads_tail_kernel(const AbxHeadsTail a) {
-    constexpr int BM = 32, BN = HT_H, WM = 32, WN = 32;
-    extern __shared__ __attribute__((aligned(16))) float ht_smem[];
-    char* lds = reinterpret_cast<char*>(ht_smem);
-    char* S = lds + HT_OPER;
-    char* S0 = S + 32 * HT_ASTR;                                            // s0, later LN(s)
-    char* T1 = S0 + 32 * HT_ASTR;
-    char* T2 = T1 + 32 * HT_HSTR;
-    const int mt = blockIdx.x, m0 = mt * BM;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, row = lane & 31;
-    const int colb = wave * WN + 4 * h;               // column of accumulator register r (swapped operands): colb + 8 (r >> 2) + (r & 3)
-    const bool row_ok = m0 + row < a.M;
-
-    for (int idx = threadIdx.x; idx < 32 * (HT_C / 4); idx += 256) {
-        const int r = idx / (HT_C / 4), c4 = idx % (HT_C / 4);
-        const long long gr = min(m0 + r, a.M - 1);
-        *reinterpret_cast<f32x4*>(S + r * HT_ASTR + c4 * 16) = *reinterpret_cast<const f32x4*>(a.s + gr * a.s_s + c4 * 4);
-        *reinterpret_cast<f32x4*>(S0 + r * HT_ASTR + c4 * 16) = *reinterpret_cast<const f32x4*>(a.s0 + gr * a.s_s0 + c4 * 4);
-    }
-    __syncthreads();
-
-    AbxGemm g = {};
-    g.M = a.M; g.N = HT_H; g.batch = 1; g.b_f16 = 1;
-    g.sB3k = 2 * HT_H * 16; g.sB3p = HT_H * 16; g.sB3n = 16;
-    f32x16 acc[1][1];
-    float ls[1], lq[1], lsh[1];
-    float x[16], y[16];
-    bool bad = false;
-
-    auto run = [&](const unsigned short* W, int e, int K, const char* abuf, int astr, int a_relu) {
-        g.K = K; g.B_split = W; g.b_exp = e; g.a_relu = a_relu;
-        gemm3_mainloop<BM, BN, WM, WN, 3, true, false, HT_RING>(g, ht_smem, mt, 0, 0, acc, ls, lq, lsh, abuf, astr);
-    };
-    // v = acc + bias (relu: after the Linear); into `dst` (add: on top of what it holds)
-    auto bias_to = [&](const float* bias, bool relu, bool add, float (&dst)[16]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 bi = *reinterpret_cast<const f32x4*>(bias + colb + 8 * q);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = acc[0][0][4 * q + e] + bi[e];
-                if (relu) v = relu_keep_nan(v);
-                dst[4 * q + e] = add ? dst[4 * q + e] + v : v;
-            }
-        }
-    };
-    auto to_lds = [&](char* buf, int stride, const float (&src)[16]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<f32x4*>(buf + row * stride + (colb + 8 * q) * 4) = (f32x4){src[4 * q], src[4 * q + 1], src[4 * q + 2], src[4 * q + 3]};
-    };
-    auto store_cols = [&](float* out, int ncol, const float (&src)[16]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int c = colb + 8 * q + e;
-                if (c < ncol) {
-                    bad |= !(fabsf(src[4 * q + e]) <= 3.0e38f);
-                    if (row_ok) out[(long long)(m0 + row) * ncol + c] = src[4 * q + e];
-                }
-            }
-    };
-    // LayerNorm of the block's rows of s -> S0 (two passes like torch): 8 threads per row, 32 channels each
-    auto layer_norm_s = [&](const float* gamma, const float* beta) {
-        const int r = threadIdx.x >> 3, p = threadIdx.x & 7;
-        const float* src = reinterpret_cast<const float*>(S + r * HT_ASTR) + p * 32;
-        float* dst = reinterpret_cast<float*>(S0 + r * HT_ASTR) + p * 32;
-        float v[32], sm = 0.f;
-#pragma unroll
-        for (int c = 0; c < 32; ++c) { v[c] = src[c]; sm += v[c]; }
-        sm += __shfl_xor(sm, 1, 64); sm += __shfl_xor(sm, 2, 64); sm += __shfl_xor(sm, 4, 64);
-        const float mean = sm * (1.0f / HT_C);
-        float sq = 0.f;
-#pragma unroll
-        for (int c = 0; c < 32; ++c) { v[c] -= mean; sq = fmaf(v[c], v[c], sq); }
-        sq += __shfl_xor(sq, 1, 64); sq += __shfl_xor(sq, 2, 64); sq += __shfl_xor(sq, 4, 64);
-        const float rstd = 1.0f / sqrtf(sq * (1.0f / HT_C) + a.ln_eps);
-#pragma unroll
-        for (int c = 0; c < 32; ++c) dst[c] = v[c] * rstd * gamma[p * 32 + c] + beta[p * 32 + c];
-    };
-    // LayerNorm -> Linear -> ReLU -> Linear -> ReLU -> Linear of one head (S0 holds LN(s) on entry)
-    auto head = [&](const unsigned short* W1, int e1, const float* b1, const unsigned short* W3, int e3, const float* b3,
-                    const unsigned short* W5, int e5, const float* b5, float* out, int ncol) {
-        run(W1, e1, HT_C, S0, HT_ASTR, 0);
-        bias_to(b1, true, false, y);
-        to_lds(T1, HT_HSTR, y);
-        __syncthreads();
-        run(W3, e3, HT_H, T1, HT_HSTR, 0);
-        bias_to(b3, true, false, y);
-        to_lds(T2, HT_HSTR, y);
-        __syncthreads();
-        run(W5, e5, HT_H, T2, HT_HSTR, 0);
-        bias_to(b5, false, false, y);
-        store_cols(out, ncol, y);
-    };
-
-    // ---- torsion module
-    run(a.W_act, a.e_act, HT_C, S, HT_ASTR, 1);
-    bias_to(a.b_act, false, false, x);
-    run(a.W_init, a.e_init, HT_C, S0, HT_ASTR, 1);
-    bias_to(a.b_init, false, true, x);
-    to_lds(T1, HT_HSTR, x);
-    __syncthreads();
-    {
-        const unsigned short* Wr[4] = {a.W_r0, a.W_r1, a.W_r2, a.W_r3};
-        const int er[4] = {a.e_r0, a.e_r1, a.e_r2, a.e_r3};
-        const float* br[4] = {a.b_r0, a.b_r1, a.b_r2, a.b_r3};
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-            run(Wr[2 * blk], er[2 * blk], HT_H, T1, HT_HSTR, 1);
-            bias_to(br[2 * blk], false, false, y);
-            to_lds(T2, HT_HSTR, y);
-            __syncthreads();
-            run(Wr[2 * blk + 1], er[2 * blk + 1], HT_H, T2, HT_HSTR, 1);
-            bias_to(br[2 * blk + 1], false, true, x);
-            to_lds(T1, HT_HSTR, x);
-            __syncthreads();
-        }
-    }
-    run(a.W_proj, a.e_proj, HT_H, T1, HT_HSTR, 1);
-    bias_to(a.b_proj, false, false, y);
-    store_cols(a.un, 14, y);
-    // ---- sequence head, pLDDT head
-    layer_norm_s(a.lns_w, a.lns_b);
-    __syncthreads();
-    head(a.W_s1, a.e_s1, a.b_s1, a.W_s3, a.e_s3, a.b_s3, a.W_s5, a.e_s5, a.b_s5, a.logits, 20);
-    if (a.W_p1) {
-        layer_norm_s(a.lnp_w, a.lnp_b);          // (every read of S0 by the sequence head ended with its first main loop's barrier)
-        __syncthreads();
-        head(a.W_p1, a.e_p1, a.b_p1, a.W_p3, a.e_p3, a.b_p3, a.W_p5, a.e_p5, a.b_p5, a.pl, 50);
-    }
-    if (a.range_flag && __any(bad) && lane == 0) atomicOr(a.range_flag, a.range_tag);
-}
 
 template <int BM, int BN, int WM, int WN, int MINW>
 int launch3(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
     const long long mt = ((long long)g.M + BM - 1) / BM, ntn = ((long long)g.N + BN - 1) / BN;
     dim3 grid((unsigned)(mt * ntn * g.batch), 1, 1), block(256);
 #ifdef ABX_PERSIST
-    if ((g.tune & 256) && grid.x > 256u * MINW) grid.x = 256u * MINW;
+    if ((g.tune & ABX_TUNE_PERSIST) && grid.x > 256u * MINW) grid.x = 256u * MINW;
 #endif
     const int amode = g.A_split ? 2 : (g.sAk == 1 ? 0 : 1);
 #define GEMM3_LAUNCH(AMODE, TS)                                                                                         \
@@ -1566,7 +867,7 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
         }
         const long long mt = ((long long)g.M + 127) / 128;
         const dim3 grid((unsigned)(mt * g.batch)), block(256);
-        if (g.tune & 64)                                                     // tune bit 6: the two-walk form of round 5 (A / B runs, cross-check)
+        if (g.tune & ABX_TUNE_GTAIL_2WALK)                                   // the two-walk form of round 5 (A / B runs, cross-check)
             *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(gated tail, two walks)", &gemm3_gtail2w_kernel, GT_LDS, grid, block, GT_LDS, st, g);
         else
             *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(gated tail)", &gemm3_gtail_kernel, GT1_LDS, grid, block, GT1_LDS, st, g);
@@ -1585,8 +886,8 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
         }
         const long long mt = ((long long)g.M + 127) / 128;
         const dim3 grid((unsigned)(mt * g.batch)), block(256);
-        if ((g.tune >> 5) & 1) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp3_kernel, MLP3_LDS, grid, block, MLP3_LDS, st, g);     // benchmarking
-        else if ((g.tune >> 4) & 1) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp_kernel<1>, 0, grid, block, 0, st, g);         // benchmarking
+        if (g.tune & ABX_TUNE_MLP_RING3) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp3_kernel, MLP3_LDS, grid, block, MLP3_LDS, st, g);     // benchmarking
+        else if (g.tune & ABX_TUNE_MLP_MINB1) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp_kernel<1>, 0, grid, block, 0, st, g);         // benchmarking
         else *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp_kernel<2>, 0, grid, block, 0, st, g);
         return 0;
     }
@@ -1602,23 +903,22 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
         }
         // (128 x 192 tiles - A read and split once per row - need 2 x 96 accumulator registers and spill at 256 VGPRs)
         const long long mt = ((long long)g.M + 127) / 128, ntn = ((long long)g.N + 95) / 96;
-        // Three blocks per CU (142 VGPRs).  tune bit 10: the four-block build (one B sub-tile in flight, 32-column store groups, 128 VGPRs):
+        // Three blocks per CU (142 VGPRs).  ABX_TUNE_DUAL_4BLOCK: the four-block build (one B sub-tile in flight, 32-column store groups, 128 VGPRs):
         // 5 % faster (9.75 vs 10.28 ms at 100 samples), but the accumulator set of the first main loop is parked in scratch across the
         // second and that is + 9 GB of HBM traffic per launch on the counters (43.9 vs 34.8 GB) - measured in profiles/r04l, not the default
-        // tune bit 7 (round 6 probe, 96 < N <= 192): one block per row tile, z walked once (gemm3_dual1_kernel) - bit-identical, but its 96 kept
+        // ABX_TUNE_DUAL_1WALK (round 6 probe, 96 < N <= 192): one block per row tile, z walked once (gemm3_dual1_kernel) - bit-identical, but its 96 kept
         // gate registers + 48 accumulators leave two blocks per CU instead of three (256 VGPRs, 7 spilled): 10.97 vs 10.30 ms at 100 samples
         // (profiles/r06c_kb_dual.txt); NOT the default
         const dim3 grid((unsigned)(mt * ntn * g.batch)), block(256);
-        if (g.N > 96 && g.N <= 192 && (g.tune & 128)) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", &gemm3_dual1_kernel, 0, dim3((unsigned)(mt * g.batch)), block, 0, st, g);
-        else if (g.tune & 1024) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", (gemm3_dual_kernel<128, 96, 32, 96, 4>), 0, grid, block, 0, st, g);
+        if (g.N > 96 && g.N <= 192 && (g.tune & ABX_TUNE_DUAL_1WALK)) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", &gemm3_dual1_kernel, 0, dim3((unsigned)(mt * g.batch)), block, 0, st, g);
+        else if (g.tune & ABX_TUNE_DUAL_4BLOCK) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", (gemm3_dual_kernel<128, 96, 32, 96, 4>), 0, grid, block, 0, st, g);
         else *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", (gemm3_dual_kernel<128, 96, 32, 96, 3>), 0, grid, block, 0, st, g);
         return 0;
     }
     if (narrow) {
         const long long mt = ((long long)g.M + 127) / 128;
         dim3 grid((unsigned)(mt * g.batch), 1, 1), block(256);
-        if ((g.tune >> 9) & 3) {                                     // probe: deeper ring (1: 3 stages at 4 blocks per CU, 2: 4 stages at 3)
-            const int v = (g.tune >> 9) & 3;
+        if (const int v = (g.tune & ABX_TUNE_NARROW_RING_MASK) >> ABX_TUNE_NARROW_RING_SHIFT) {      // probe: deeper ring (1: 3 stages at 4 blocks per CU, 2: 4 stages at 3)
             const char* what = "abx_gemm(narrow, ring)";
             if (g.c_transposed && v == 1) *rc = ABX_LAUNCH_LIT(plan, what, (gemm3_narrow_ring_kernel<true, 3, 4>), 0, grid, block, 0, st, g);
             else if (g.c_transposed) *rc = ABX_LAUNCH_LIT(plan, what, (gemm3_narrow_ring_kernel<true, 4, 3>), 0, grid, block, 0, st, g);
@@ -1631,7 +931,7 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
         return 0;
     }
     const long long pad128 = ((g.N + 127) / 128) * 128, pad192 = ((g.N + 191) / 192) * 192;
-    const int force = (g.tune >> 1) & 7;                       // 1: 128x128, 2: 128x192 (benchmarking)
+    const int force = (g.tune & ABX_TUNE_FORCE_MASK) >> ABX_TUNE_FORCE_SHIFT;      // 1: 128x128, 2: 128x192 (benchmarking)
     // (the plane x plane contraction at L = 352 pads to 384 either way: the wide tile measured 10 % faster)
     const bool wide = g.glu ? false : force ? force == 2 : (g.A_split ? pad192 <= pad128 : (pad192 <= pad128 && g.N % 128 != 0));
     // waves are stacked along M (4 x 1): every wave owns 32 rows and the full tile width, so each A row is read from LDS and
@@ -1684,54 +984,4 @@ extern "C" int abx_split_weights_f16(const float* w, long long s_n, long long s_
     hipLaunchKernelGGL(split_weights_f16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, s_n, s_k, N, K, Kp,
                        ldexpf(1.0f, scale_exp), out);
     return abx_check_launch("abx_split_weights_f16");
-}
-
-extern "C" int abx_ipa_tail(const AbxIpaTail* ap, hipStream_t st) {
-    ABX_REQUIRE(ap != nullptr, "abx_ipa_tail: null descriptor");
-    const AbxIpaTail a = *ap;
-    auto al16 = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    ABX_REQUIRE(a.M > 0 && a.C == IT_C, "abx_ipa_tail: M > 0, C == 256");
-    ABX_REQUIRE(al16(a.s) && a.s_s % 4 == 0 && a.s_s >= IT_C, "abx_ipa_tail: s must be 16-byte aligned rows");
-    if (a.partial) {
-        ABX_REQUIRE(al16(a.partial) && a.n_partial > 0 && a.s_partial >= (long long)a.M * IT_C && a.s_partial % 4 == 0,
-                    "abx_ipa_tail: partial = n_partial K-slice products (M, 256) of feat W_final, s_partial floats apart");
-    } else {
-        ABX_REQUIRE(a.K1 > 0 && a.K1 % 16 == 0, "abx_ipa_tail: K1 % 16 == 0");
-        ABX_REQUIRE(al16(a.feat) && a.s_feat % 4 == 0 && a.s_feat >= a.K1, "abx_ipa_tail: feat must be 16-byte aligned rows");
-        ABX_REQUIRE(32LL * a.s_feat < (1LL << 28), "abx_ipa_tail: feature rows too long");
-        ABX_REQUIRE(al16(a.W_final), "abx_ipa_tail: weight planes (abx_split_weights_f16)");
-    }
-    ABX_REQUIRE(al16(a.W_t0) && al16(a.W_t2) && al16(a.W_t4), "abx_ipa_tail: weight planes (abx_split_weights_f16)");
-    ABX_REQUIRE(al16(a.b_final) && al16(a.b_t0) && al16(a.b_t2) && al16(a.b_t4) && al16(a.ln1_w) && al16(a.ln1_b) && al16(a.ln2_w) && al16(a.ln2_b),
-                "abx_ipa_tail: biases and LayerNorm parameters ([256], 16-byte aligned)");
-    for (int e : {a.e_final, a.e_t0, a.e_t2, a.e_t4}) ABX_REQUIRE(e >= -100 && e <= 100, "abx_ipa_tail: weight exponent out of range");
-    ABX_REQUIRE(!a.W_aff || (a.b_aff && a.fixed && a.init_q && a.init_t && a.cur_q && a.cur_t && a.cur_R && a.delta_q && a.pscale != 0.f),
-                "abx_ipa_tail: the affine / frame update needs all of its operands");
-    if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&ipa_tail_kernel), IT_LDS, "abx_ipa_tail")) return rc;
-    hipLaunchKernelGGL(ipa_tail_kernel, dim3((unsigned)((a.M + 31) / 32)), dim3(256), IT_LDS, st, a);
-    return abx_check_launch("abx_ipa_tail");
-}
-
-extern "C" int abx_heads_tail(const AbxHeadsTail* ap, hipStream_t st) {
-    ABX_REQUIRE(ap != nullptr, "abx_heads_tail: null descriptor");
-    const AbxHeadsTail a = *ap;
-    auto al16 = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    ABX_REQUIRE(a.M > 0 && al16(a.s) && al16(a.s0) && a.s_s % 4 == 0 && a.s_s0 % 4 == 0 && a.s_s >= HT_C && a.s_s0 >= HT_C,
-                "abx_heads_tail: s / s0 are (M, 256) fp32 rows, 16-byte aligned");
-    ABX_REQUIRE(a.un && a.logits, "abx_heads_tail: un (M, 14) and logits (M, 20) outputs");
-    const unsigned short* Ws[] = {a.W_act, a.W_init, a.W_r0, a.W_r1, a.W_r2, a.W_r3, a.W_proj, a.W_s1, a.W_s3, a.W_s5};
-    const float* bs[] = {a.b_act, a.b_init, a.b_r0, a.b_r1, a.b_r2, a.b_r3, a.b_proj, a.b_s1, a.b_s3, a.b_s5};
-    for (int i = 0; i < 10; ++i)
-        ABX_REQUIRE(al16(Ws[i]) && al16(bs[i]), "abx_heads_tail: weight planes (abx_split_weights_f16, 128 columns) and [128] biases, 16-byte aligned");
-    for (int e : {a.e_act, a.e_init, a.e_r0, a.e_r1, a.e_r2, a.e_r3, a.e_proj, a.e_s1, a.e_s3, a.e_s5})
-        ABX_REQUIRE(e >= -100 && e <= 100, "abx_heads_tail: weight exponent out of range");
-    ABX_REQUIRE(al16(a.lns_w) && al16(a.lns_b), "abx_heads_tail: LayerNorm parameters of the sequence head ([256])");
-    if (a.W_p1) {
-        ABX_REQUIRE(al16(a.W_p1) && al16(a.W_p3) && al16(a.W_p5) && al16(a.b_p1) && al16(a.b_p3) && al16(a.b_p5) && al16(a.lnp_w) && al16(a.lnp_b) && a.pl,
-                    "abx_heads_tail: the pLDDT head needs all of its operands");
-        for (int e : {a.e_p1, a.e_p3, a.e_p5}) ABX_REQUIRE(e >= -100 && e <= 100, "abx_heads_tail: weight exponent out of range");
-    }
-    if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(&heads_tail_kernel), HT_LDS, "abx_heads_tail")) return rc;
-    hipLaunchKernelGGL(heads_tail_kernel, dim3((unsigned)((a.M + 31) / 32)), dim3(256), HT_LDS, st, a);
-    return abx_check_launch("abx_heads_tail");
 }

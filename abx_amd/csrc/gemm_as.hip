@@ -22,17 +22,14 @@
 // 75 KB of LDS, two blocks per CU: one block's prologue and its last, un-overlapped epilogue run under the other block's walk.
 // The arithmetic of every output element is that of gemm3_kernel (same pieces, same three product terms per k-step in the same
 // order, same statistics code in the same order): results are bit-identical to the tile kernels.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
 #include "abx_hip.h"
+#include "split_dev.h"
+#include "grid_map.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
 constexpr int AS_BM = 64, AS_BN = 128, AS_NK = 12, AS_RING = 3;
 constexpr int AS_KT = 4096;                              // bytes of one k-tile of the A image: fp32 [64][16] or pieces [2][64][16]
@@ -44,49 +41,7 @@ constexpr int AS_OFF_ST = AS_OFF_RING + AS_RING * AS_STAGE;         // [4][64]: 
 constexpr int AS_OFF_CONST = AS_OFF_ST + 4 * 64 * 4;                // [2 tiles][csum 128 | bias 128]: column constants of a tile
 constexpr int AS_LDS = AS_OFF_CONST + 2 * 1024;                     // 76 800 = 60 granules of 1 280 (two blocks per CU: <= 81 920)
 
-__device__ __forceinline__ void as_glds16(const void* src, char* dst_wave_base) {
-    __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)dst_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ unsigned as_vgpr32(unsigned o) {
-    asm volatile("" : "+v"(o));
-    return o;
-}
-template <int I> using IC = std::integral_constant<int, I>;
-template <int I0, int I1, class F> __device__ __forceinline__ void as_static_for(F&& f) {
-    if constexpr (I0 < I1) {
-        f(IC<I0>{});
-        as_static_for<I0 + 1, I1>(f);
-    }
-}
-
-// byte offset of (plane, row, 16-byte half) in a [2][ROWS][16] 16-bit tile image (the layout of gemm3.hip: conflict-free 16-byte
-// fragment reads with lane -> row, lane >> 5 -> k half)
-template <int ROWS> __device__ __forceinline__ int as_plane_off(int plane, int row, int half) {
-    return plane * (ROWS * 32) + row * 32 + ((half ^ ((row >> 3) & 1)) << 4);
-}
-
 // ---- the A image ------------------------------------------------------------------------------------------------------------------------
-// source row of GEMM row gri (the row maps of gemm3_mainloop: padded pair positions, (8 i x 16 k) block order, pair transposition)
-__device__ __forceinline__ long long as_a_row(const AbxGemm& g, int gri) {
-    long long gr = gri;
-    if (g.a_pair) {
-        int pi, pj;
-        if (g.c_split_tile) {
-            pair_tile_decode(gri, g.pair_Lp, pi, pj);
-            pi = min(pi, g.pair_L - 1);
-            pj = min(pj, g.pair_L - 1);
-        } else {
-            pi = gri / g.pair_Lp;
-            pj = min(gri - pi * g.pair_Lp, g.pair_L - 1);
-        }
-        gr = g.a_pair_transpose > 0 ? (long long)pj * g.pair_L + pi : (long long)pi * g.pair_L + pj;
-    } else if (g.a_pair_transpose > 0) {
-        const int qi = gri / g.a_pair_transpose;
-        gr = (long long)(gri - qi * g.a_pair_transpose) * g.a_pair_transpose + qi;
-    }
-    return gr;
-}
-
 // The burst of a column-0 wave (wm, 0): its 32 rows x 192 fp32, 24 DMA instructions in k-tile order (two per k-tile: rows 0 - 15 and
 // 16 - 31 of the half).  Landing image of a (k-tile, half): [32 rows][4 slots of 16 bytes], slot p of row r holds the k-quad
 // p ^ ((r >> 2) & 3) (conflict-free 16-byte reads of a row's two k halves by the 32 x 2 lanes of the splitting wave).
@@ -100,14 +55,14 @@ __device__ __forceinline__ void as_issue_a(const AbxGemm& g, char* lds, int m0, 
     for (int i = 0; i < 2; ++i) {
         const int r = 16 * i + (lane >> 2), p = lane & 3;
         const int kq = p ^ ((r >> 2) & 3);
-        const long long gr = as_a_row(g, min(m0 + wm * 32 + r, g.M - 1));
+        const long long gr = pair_a_row(g, min(m0 + wm * 32 + r, g.M - 1));
         offA[i] = (unsigned)(((gr - row0) * g.sAm + kq * 4) * 4);
     }
     char* dst = lds + wm * AS_HALF;
 #pragma unroll
     for (int kt = 0; kt < AS_NK; ++kt)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) as_glds16(baseA + kt * 64 + as_vgpr32(offA[i]), dst + kt * AS_KT + i * 1024);
+        for (int i = 0; i < 2; ++i) glds16(baseA + kt * 64 + vgpr32(offA[i]), dst + kt * AS_KT + i * 1024);
 }
 
 // statistics + split of ONE (k-tile, row half) by the wave that fetched it: lane = (row, k half) exactly as a fragment lane of the tile
@@ -123,7 +78,7 @@ __device__ __forceinline__ void as_conv_init(AsConv& c, const AbxGemm& g) {
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, x = (r >> 2) & 3;
     c.rd0 = r * 64 + (((2 * h) ^ x) << 4);
     c.rd1 = r * 64 + (((2 * h + 1) ^ x) << 4);
-    c.wr = as_plane_off<32>(0, r, h);
+    c.wr = plane_off<32>(0, r, h);
     c.lshift = 0.f;
     c.ls2 = c.lq2 = (f32x2){0.f, 0.f};
     c.m2048 = -2048.0f;
@@ -181,32 +136,6 @@ __device__ __forceinline__ void as_conv_finish(const AsConv& c, float* st, int w
     }
 }
 
-// 4 x 4 transpose inside every lane quad: lane q of a quad holds x[0 .. 3] = rows 0 .. 3 of column q and receives o[0 .. 3] = columns
-// 0 .. 3 of row q.  Two exchange stages (lane ^ 1, lane ^ 2), each ONE v_cndmask_b32 with a DPP quad_perm source per value (the select
-// and the cross-lane move in one instruction; vcc = the lanes that keep their own value): 8 VALU instructions instead of the 24 the
-// compiler makes of update_dpp + select (a zeroed destination, the move, the select).  The leading s_nop covers the two wait states
-// between the VALU write of x and its DPP read; inside the statement every DPP source is written >= 2 instructions earlier.
-__device__ __forceinline__ void as_quad_transpose(const float (&x)[4], float (&o)[4]) {
-    float a0, a1, a2, a3;
-    asm volatile(
-        "s_nop 1\n\t"
-        "s_mov_b32 vcc_lo, 0x55555555\n\ts_mov_b32 vcc_hi, 0x55555555\n\t"                                    // even lanes keep rows 0, 2
-        "v_cndmask_b32_dpp %4, %9, %8, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"               // a0 = even ? x0 : x1 of lane ^ 1
-        "v_cndmask_b32_dpp %6, %11, %10, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"             // a2 = even ? x2 : x3 of lane ^ 1
-        "s_mov_b32 vcc_lo, 0xaaaaaaaa\n\ts_mov_b32 vcc_hi, 0xaaaaaaaa\n\t"                                    // odd lanes keep rows 1, 3
-        "v_cndmask_b32_dpp %5, %8, %9, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"               // a1 = odd ? x1 : x0 of lane ^ 1
-        "v_cndmask_b32_dpp %7, %10, %11, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"             // a3 = odd ? x3 : x2 of lane ^ 1
-        "s_mov_b32 vcc_lo, 0x33333333\n\ts_mov_b32 vcc_hi, 0x33333333\n\t"                                    // lanes 0, 1 of a quad
-        "v_cndmask_b32_dpp %0, %6, %4, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"               // o0 = low ? a0 : a2 of lane ^ 2
-        "v_cndmask_b32_dpp %1, %7, %5, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"               // o1 = low ? a1 : a3 of lane ^ 2
-        "s_mov_b32 vcc_lo, 0xcccccccc\n\ts_mov_b32 vcc_hi, 0xcccccccc\n\t"                                    // lanes 2, 3 of a quad
-        "v_cndmask_b32_dpp %2, %4, %6, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"               // o2 = high ? a2 : a0 of lane ^ 2
-        "v_cndmask_b32_dpp %3, %5, %7, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"                     // o3 = high ? a3 : a1 of lane ^ 2
-        : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3)
-        : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3])
-        : "vcc");
-}
-
 // ---- operations a COLUMN-1 wave queues behind the weight DMA of a k-step (for its counted waits) -------------------------------------
 // Per tile: two more DMA instructions at k-step 0 (the tile's column constants); NST stores at each of the k-steps [S0, S0 + NSL) of
 // every tile but the first (the slices of the previous tile's epilogue).  S0 + NSL <= 10: the steps 10, 11 of a tile carry nothing, so
@@ -242,7 +171,6 @@ __device__ __forceinline__ void as_rendezvous_free(u32x4 (&fa)[2], u32x4 (&fb)[2
                  :
                  : "memory");
 }
-template <int N> __device__ __forceinline__ void as_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // ---- the block ------------------------------------------------------------------------------------------------------------------------
 // EPI_PLAIN: C[m][n] = rstd (acc - dmean csum[n]) + bias[n] (the folded LayerNorm; the dispatch admits alpha == 1, no activation), 16-byte
@@ -261,7 +189,7 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
     const int wm = wave >> 1, wn = wave & 1, h = lane >> 5;
     const int m0 = mt * AS_BM;
     float* st = reinterpret_cast<float*>(lds + AS_OFF_ST);       // [4][64]: mean - shift | rstd | row scale | row valid
-    // ABL (probe builds, -DABX_AS_ABLATE + tune bits 12 - 13): 1 = no slice stores, 2 = no MFMA, 3 = half of the weight DMA inside the walk
+    // ABL (probe builds, -DABX_AS_ABLATE + ABX_TUNE_ABLATE_MASK): 1 = no slice stores, 2 = no MFMA, 3 = half of the weight DMA inside the walk
     using Sched = typename std::conditional<EPI == AS_EPI_PLAIN, AsSched<2, 8, (ABL == 1 ? 0 : (PL ? 2 : 1)), (ABL == 3 ? 2 : 4)>, AsSched<6, 2, (ABL == 1 ? 0 : 2), (ABL == 3 ? 2 : 4)>>::type;
 
     // ---- weight operand: fetched by the column-1 waves, wave (wm, 1) = plane wm of a stage (four 1 KB chunks of 32 rows)
@@ -292,15 +220,15 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
         const int t = min(tile, ntiles - 1);                    // (tiles beyond the walk re-request the last one: uniform instruction counts)
         const char* src = bbase + kt * bkstep + (long long)t * tile_step;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) as_glds16(src + i * chunk_step + as_vgpr32(off0), dst + i * 1024);
+        for (int i = 0; i < 2; ++i) glds16(src + i * chunk_step + vgpr32(off0), dst + i * 1024);
         if (half_only) return;
         if (t == ntiles - 1) {
             const char* srcU = bbaseS + kt * bkstepS;
 #pragma unroll
-            for (int i = 2; i < 4; ++i) as_glds16(srcU + as_vgpr32(offU[i - 2]), dst + i * 1024);
+            for (int i = 2; i < 4; ++i) glds16(srcU + vgpr32(offU[i - 2]), dst + i * 1024);
         } else {
 #pragma unroll
-            for (int i = 2; i < 4; ++i) as_glds16(src + i * chunk_step + as_vgpr32(off0), dst + i * 1024);
+            for (int i = 2; i < 4; ++i) glds16(src + i * chunk_step + vgpr32(off0), dst + i * 1024);
         }
     };
     // column constants of a tile -> LDS [slot = tile & 1][csum 128 | bias 128] by DMA (4 bytes per lane: wave (0, 1) the column sums,
@@ -331,7 +259,7 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
         t_issued = __builtin_amdgcn_s_memtime();
 #endif
         as_conv_init(cv, g);
-        as_wait_vm<20>();                                       // k-tiles 0, 1 of the burst (its first four instructions) have landed
+        wait_vm<20>();                                       // k-tiles 0, 1 of the burst (its first four instructions) have landed
 #ifdef ABX_AS_STAMP
         as_t_landed = __builtin_amdgcn_s_memtime();
 #endif
@@ -350,7 +278,7 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
             st[128 + lane] = (ok && g.rowscale) ? g.rowscale[(long long)b * g.sRSb + (long long)pi * g.pair_Lp + pj] : (ok ? 1.f : 0.f);
             st[192 + lane] = ok ? 1.f : 0.f;
         }
-        as_wait_vm<8>();                                        // stage 0 has landed
+        wait_vm<8>();                                        // stage 0 has landed
     }
     __syncthreads();
 
@@ -361,8 +289,8 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
     bool bad = false;
 
     // ---- fragment addressing
-    const int offAf = wm * AS_HALF + as_plane_off<32>(0, lane & 31, h);                     // + kt * AS_KT + p * 1024
-    const int offBf = AS_OFF_RING + as_plane_off<AS_BN>(0, wn * 64 + (lane & 31), h);       // + slot * AS_STAGE + p * 4096 + j * 1024
+    const int offAf = wm * AS_HALF + plane_off<32>(0, lane & 31, h);                     // + kt * AS_KT + p * 1024
+    const int offBf = AS_OFF_RING + plane_off<AS_BN>(0, wn * 64 + (lane & 31), h);       // + slot * AS_STAGE + p * 4096 + j * 1024
     u32x4 fa[2][2], fb[2][2][2];                                // [set][piece], [set][sub-tile][plane]
     auto read_frags = [&](int set, int kt, int slot) __attribute__((always_inline)) {
 #pragma unroll
@@ -410,7 +338,7 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
         }
         // (one class test per slice: a NaN / inf among the four makes their sum NaN / inf - the kernel is instruction-issue bound)
         bad |= __builtin_amdgcn_classf((x[0] + x[1]) + (x[2] + x[3]), 0x207);
-        as_quad_transpose(x, o);
+        quad_transpose(x, o);
         const int m = m0 + wm * 32 + 8 * rq + 4 * h + (lane & 3);
         const int n = tile_p * AS_BN + wn * 64 + j * 32 + ((lane & 31) >> 2) * 4;
         if constexpr (PL) {
@@ -576,7 +504,7 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
         } else if constexpr (first && kt < AS_NK - 2) {
             // first tile, column 0: statistics + split of the k-tile two steps ahead (its fragments are read one step ahead, behind
             // the next rendezvous); this wave's vector-memory queue holds nothing but the burst
-            as_wait_vm<2 * (AS_NK - 3 - kt)>();
+            wait_vm<2 * (AS_NK - 3 - kt)>();
             as_conv_ktile<false>(cv, a_half + (kt + 2) * AS_KT);
             if constexpr (kt == AS_NK - 3) as_conv_finish(cv, st, wm, g.ln_eps, cs);
         }
@@ -627,10 +555,10 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
 #endif
     read_frags(0, 0, 0);                                        // (pieces of k-tile 0 written, weight stage 0 landed: the barrier above)
     auto walk = [&](auto role_) __attribute__((always_inline)) {
-        as_static_for<0, AS_NK>([&](auto kt_) { step(0, kt_, IC<1>{}, role_); });
+        static_for<0, AS_NK>([&](auto kt_) { step(0, kt_, IC<1>{}, role_); });
         rotate(0);
         for (int tile = 1; tile < ntiles; ++tile) {
-            as_static_for<0, AS_NK>([&](auto kt_) { step(tile, kt_, IC<0>{}, role_); });
+            static_for<0, AS_NK>([&](auto kt_) { step(tile, kt_, IC<0>{}, role_); });
             rotate(tile);
         }
 #ifdef ABX_AS_STAMP
@@ -642,10 +570,10 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
         if (SIDE && role == 1) side_store();
         else if (SIDE || !ragged || role == 0) {                // (the idle wave column of a ragged last tile stores nothing)
             read_consts();
-            if constexpr (EPI == AS_EPI_PLAIN) as_static_for<0, 8>([&](auto q_) { plain_slice(q_); });
+            if constexpr (EPI == AS_EPI_PLAIN) static_for<0, 8>([&](auto q_) { plain_slice(q_); });
             else {
-                as_static_for<0, 4>([&](auto q_) { glu_value(q_); });
-                as_static_for<0, 2>([&](auto q_) { glu_round(q_); });
+                static_for<0, 4>([&](auto q_) { glu_value(q_); });
+                static_for<0, 2>([&](auto q_) { glu_round(q_); });
             }
         }
     };
@@ -675,9 +603,7 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(const AbxGemm g, const 
     const ClockProbe probe(g.clock_probe);
     const unsigned ntm = (unsigned)((g.M + AS_BM - 1) / AS_BM);
     // XCD-aware remap (gemm3_kernel): every XCD gets a contiguous range of row tiles
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / ntm), mt = (int)(wgid - (unsigned)b * ntm);
     bool edge = (mt + 1) * AS_BM > g.M;
     if (EPI == AS_EPI_GLU) edge = edge || (g.pair_L & 7) != 0 || (g.c_split_L & 15) != 0;     // padded pair rows: predicated stores
@@ -741,7 +667,7 @@ __device__ __forceinline__ void ad_issue_z(const AbxGemm& g, char* lds, int m0, 
 #pragma unroll
     for (int kt = 0; kt < AD_NK2; ++kt)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) as_glds16(baseA + kt * 64 + as_vgpr32(offA[i]), dst + kt * AS_KT + i * 1024);
+        for (int i = 0; i < 2; ++i) glds16(baseA + kt * 64 + vgpr32(offA[i]), dst + kt * AS_KT + i * 1024);
 }
 
 // statistics + split of one (k-tile, row half) of the channel-major product: landing image [16 k][32 rows] fp32
@@ -795,11 +721,11 @@ __device__ __forceinline__ void as_dual_block(const AbxGemm& g, char* lds, int m
         if constexpr (s < AD_NK2) {
             const char* src = wbase2 + s * wk2;
 #pragma unroll
-            for (int i = 0; i < 6; ++i) as_glds16(src + i * wchunk2 + as_vgpr32(woff2), dst + i * 1024);
+            for (int i = 0; i < 6; ++i) glds16(src + i * wchunk2 + vgpr32(woff2), dst + i * 1024);
         } else {
             const char* src = wbase1 + (s - AD_NK2) * wk1;
 #pragma unroll
-            for (int i = 0; i < 6; ++i) as_glds16(src + i * wchunk1 + as_vgpr32(woff1), dst + i * 1024);
+            for (int i = 0; i < 6; ++i) glds16(src + i * wchunk1 + vgpr32(woff1), dst + i * 1024);
         }
     };
 
@@ -817,7 +743,7 @@ __device__ __forceinline__ void as_dual_block(const AbxGemm& g, char* lds, int m
         char* dst = lds + (AD_P0 + kt) * AS_KT + wm * AS_HALF;
         const char* src = pbase + kt * pk;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) as_glds16(src + as_vgpr32(poff[i]), dst + i * 1024);
+        for (int i = 0; i < 2; ++i) glds16(src + vgpr32(poff[i]), dst + i * 1024);
     };
 
     // ---- prologue.  Column 0: the z burst, statistics + split of its first two k-tiles.  Column 1: column constants, two weight stages
@@ -831,7 +757,7 @@ __device__ __forceinline__ void as_dual_block(const AbxGemm& g, char* lds, int m
         cz.ln = true;
         cz.relu = false;
         cp = cz;
-        as_wait_vm<20>();
+        wait_vm<20>();
         as_conv_ktile<true>(cz, a_half);
         as_conv_ktile<false>(cz, a_half + AS_KT);
     } else {
@@ -846,13 +772,13 @@ __device__ __forceinline__ void as_dual_block(const AbxGemm& g, char* lds, int m
             }
         issue_w(IC<0>{});
         issue_w(IC<1>{});
-        as_wait_vm<6>();                                        // the constants and stage 0 have landed
+        wait_vm<6>();                                        // the constants and stage 0 have landed
     }
     __syncthreads();
 
     // ---- fragments
-    const int offAf = wm * AS_HALF + as_plane_off<32>(0, lane & 31, h);                       // + kt * AS_KT + p * 1024
-    const int offBf = as_plane_off<AD_BN>(0, wn * 96 + (lane & 31), h);                       // + ad_wslot + p * AD_PLANE + j * 1024
+    const int offAf = wm * AS_HALF + plane_off<32>(0, lane & 31, h);                       // + kt * AS_KT + p * 1024
+    const int offBf = plane_off<AD_BN>(0, wn * 96 + (lane & 31), h);                       // + ad_wslot + p * AD_PLANE + j * 1024
     u32x4 fa[2][2], fb[2][3][2];
     auto read_frags = [&](int set, int kt, int wslot) __attribute__((always_inline)) {
 #pragma unroll
@@ -925,15 +851,15 @@ __device__ __forceinline__ void as_dual_block(const AbxGemm& g, char* lds, int m
             constexpr int np = s < AD_P0 ? 0 : (s - AD_P0 + 1 < AD_NK1 ? s - AD_P0 + 1 : AD_NK1);      // product k-tiles requested so far
             if constexpr (s >= AD_P0 && s < AD_P0 + AD_NK1) issue_p(s - AD_P0);       // (the fragments of z k-tile s are in registers: its slot is free)
             if constexpr (s < AD_NK2 - 2) {
-                as_wait_vm<(24 - 2 * (s + 3)) + 2 * np>();
+                wait_vm<(24 - 2 * (s + 3)) + 2 * np>();
                 as_conv_ktile<false>(cz, a_half + (s + 2) * AS_KT);
                 if constexpr (s == AD_NK2 - 3) as_conv_finish(cz, st, wm, g.ln_eps, cs2);
             } else if constexpr (s < AD_NK2) {                  // steps 10, 11: the product k-tiles 0, 1
-                as_wait_vm<2 * (np - 1 - (s - 10))>();
+                wait_vm<2 * (np - 1 - (s - 10))>();
                 ad_conv_ptile<s == 10>(cp, a_half + (AD_P0 + s - 10) * AS_KT);
             } else if constexpr (s - AD_NK2 + 2 < AD_NK1) {     // output step t: the product k-tile t + 2
                 constexpr int kp = s - AD_NK2 + 2;
-                as_wait_vm<2 * (AD_NK1 - 1 - kp)>();
+                wait_vm<2 * (AD_NK1 - 1 - kp)>();
                 ad_conv_ptile<false>(cp, a_half + (AD_P0 + kp) * AS_KT);
                 if constexpr (kp == AD_NK1 - 1) as_conv_finish(cp, st + 128, wm, g.ln_eps, cs1, 1.0f / (float)(AD_NK1 * 16));
             }
@@ -975,7 +901,7 @@ __device__ __forceinline__ void as_dual_block(const AbxGemm& g, char* lds, int m
     };
 
     read_frags(0, 0, ad_wslot(0));
-    auto walk = [&](auto role_) __attribute__((always_inline)) { as_static_for<0, AD_NS>([&](auto s_) { step(s_, role_); }); };
+    auto walk = [&](auto role_) __attribute__((always_inline)) { static_for<0, AD_NS>([&](auto s_) { step(s_, role_); }); };
     if (wn == 0) walk(IC<0>{});
     else walk(IC<1>{});
 
@@ -998,7 +924,7 @@ __device__ __forceinline__ void as_dual_block(const AbxGemm& g, char* lds, int m
                 v = v + bias1;
                 x[c] = v * gatev[j][4 * rq + c];
             }
-            as_quad_transpose(x, o);
+            quad_transpose(x, o);
             f32x4 ov;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -1016,9 +942,7 @@ __global__ __launch_bounds__(256, 2) void gemm_as_dual_kernel(const AbxGemm g) {
     char* lds = reinterpret_cast<char*>(as_smem);
     const ClockProbe probe(g.clock_probe);
     const unsigned ntm = (unsigned)((g.M + AS_BM - 1) / AS_BM);
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / ntm), mt = (int)(wgid - (unsigned)b * ntm);
     if ((mt + 1) * AS_BM > g.M) as_dual_block<true>(g, lds, mt, b);
     else as_dual_block<false>(g, lds, mt, b);
@@ -1027,10 +951,7 @@ __global__ __launch_bounds__(256, 2) void gemm_as_dual_kernel(const AbxGemm g) {
 
 // The dual descriptor of the TriangleMultiplication tail -> gemm_as_dual_kernel.  Returns 1 when the tile kernel (gemm3_dual_kernel) keeps it.
 int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan) {
-    static const bool off = [] {
-        const char* e = getenv("ABX_NO_DUAL_AS");               // (A / B measurements: the tile kernel everywhere)
-        return e != nullptr && !(e[0] == '0' && e[1] == 0);
-    }();
+    static const bool off = abx_env_on("ABX_NO_DUAL_AS");       // (A / B measurements: the tile kernel everywhere)
     if (off) return 1;
     if (g.exact == 1 || g.K != AD_NK1 * 16 || g.K2 != AD_NK2 * 16 || g.N != AD_BN) return 1;
     if (!g.A || g.A_split || g.sAm != 1 || g.M % 4 != 0 || g.M < 4 || !g.B_split || !g.B2_split || !g.b_f16) return 1;
@@ -1059,8 +980,8 @@ int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan) {
     const long long ntm = ((long long)g.M + AS_BM - 1) / AS_BM;
     if (ntm * g.batch >= (1LL << 31)) return 1;
     // the launch-size rule of the walk below (and its INVARIANT: bit-identical to the tile kernel, test_gpu_tri_mul_tail_as.py);
-    // tune bit 14 forces the kernel on an eligible shape of any size
-    if (!(g.tune & 16384) && ntm * g.batch < 1024) return 1;
+    // ABX_TUNE_AS_DUAL forces the kernel on an eligible shape of any size
+    if (!(g.tune & ABX_TUNE_AS_DUAL) && ntm * g.batch < 1024) return 1;
     *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(as, dual)", &gemm_as_dual_kernel, AD_LDS, dim3((unsigned)(ntm * g.batch)), dim3(256), AD_LDS, st, g);
     return 0;
 }
@@ -1070,8 +991,8 @@ int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan) {
 // Called by abx_gemm / abx_gemm_side (gemm.hip) with validated descriptors (vector flags filled).  side == nullptr: no side GEMM.
 // Returns 1 when the problem is not served here (the caller goes on to the tile kernels of gemm3.hip).
 int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, int* rc, AbxPlan* plan) {
-    static const bool off = getenv("ABX_NO_GEMM_AS") != nullptr;          // (A / B measurements: always the tile kernels)
-    if (off || (g.tune & 2048)) return 1;                       // tune bit 11: the tile kernels for this call
+    static const bool off = abx_env_on("ABX_NO_GEMM_AS");       // (A / B measurements: always the tile kernels)
+    if (off || (g.tune & ABX_TUNE_TILE_ONLY)) return 1;
     if (g.A2) return side ? 1 : as_dual_dispatch(g, st, rc, plan);    // the TriangleMultiplication tail
     if (g.exact == 1 || !g.B_split || !g.b_f16 || g.A_split || !g.A || g.sAk != 1 || g.K != AS_NK * 16) return 1;
     if (g.A2 || g.out_ln_w || g.mlp || g.ln_stats || g.gate || g.resid || g.batch_inner || !g.ln_csum || !g.bias) return 1;
@@ -1118,7 +1039,7 @@ int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, 
     ABX_LAUNCH(plan, ("gemm_as_kernel<%d, %s, %d, %s>", EPI, ABX_BOOL(SIDE), ABL, ABX_BOOL(PL)), "abx_gemm(as)", (gemm_as_kernel<EPI, SIDE, ABL, PL>), \
                AS_LDS, grid, block, AS_LDS, st, g, side ? *side : none)
 #ifdef ABX_AS_ABLATE
-    const int abl = (g.tune >> 12) & 3;
+    const int abl = (g.tune & ABX_TUNE_ABLATE_MASK) >> ABX_TUNE_ABLATE_SHIFT;
     if (abl == 1) *rc = glu ? AS_LAUNCH(AS_EPI_GLU, false, 1, false) : side ? AS_LAUNCH(AS_EPI_PLAIN, true, 1, false) : AS_LAUNCH(AS_EPI_PLAIN, false, 1, false);
     else if (abl == 2) *rc = glu ? AS_LAUNCH(AS_EPI_GLU, false, 2, false) : side ? AS_LAUNCH(AS_EPI_PLAIN, true, 2, false) : AS_LAUNCH(AS_EPI_PLAIN, false, 2, false);
     else if (abl == 3) *rc = glu ? AS_LAUNCH(AS_EPI_GLU, false, 3, false) : side ? AS_LAUNCH(AS_EPI_PLAIN, true, 3, false) : AS_LAUNCH(AS_EPI_PLAIN, false, 3, false);

@@ -16,40 +16,14 @@
 // Mathematically the reference's expression regrouped: sum_k (l r) W1 + sum_k (l - r) W2 = l . (diag(r) W1 + W2) - r . W2.
 #include "common.h"
 #include "abx_hip.h"
+#include "split_dev.h"
+#include "grid_map.h"
 
 namespace {
 
 constexpr int OPM_C = 64, OPM_N = 192, OPM_KT = OPM_C / 16;
 constexpr int OPM_IMG = 2 * OPM_N * 32;                     // one k-tile of the U image: [2 planes][192 columns][16 k] float16 = 12 288 bytes
 constexpr int OPM_LDS = OPM_KT * OPM_IMG + OPM_N * 4 + OPM_C * 4;      // U image 49 152 + c_i 768 + r_i 256
-
-// byte offset of (plane, row, 16-byte half) in a [2][ROWS][16] 16-bit tile image (the layout of gemm3.hip: conflict-free 16-byte fragment reads)
-__device__ __forceinline__ int opm_plane_off(int plane, int row, int half) {
-    return plane * (OPM_N * 32) + row * 32 + ((half ^ ((row >> 3) & 1)) << 4);
-}
-
-// 4 x 4 transpose inside every lane quad (gemm_as.hip as_quad_transpose): lane q of a quad holds x[0 .. 3] = rows 0 .. 3 of column q and receives
-// o[0 .. 3] = columns 0 .. 3 of row q
-__device__ __forceinline__ void opm_quad_transpose(const float (&x)[4], float (&o)[4]) {
-    float a0, a1, a2, a3;
-    asm volatile(
-        "s_nop 1\n\t"
-        "s_mov_b32 vcc_lo, 0x55555555\n\ts_mov_b32 vcc_hi, 0x55555555\n\t"
-        "v_cndmask_b32_dpp %4, %9, %8, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %6, %11, %10, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b32 vcc_lo, 0xaaaaaaaa\n\ts_mov_b32 vcc_hi, 0xaaaaaaaa\n\t"
-        "v_cndmask_b32_dpp %5, %8, %9, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %7, %10, %11, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b32 vcc_lo, 0x33333333\n\ts_mov_b32 vcc_hi, 0x33333333\n\t"
-        "v_cndmask_b32_dpp %0, %6, %4, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %1, %7, %5, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b32 vcc_lo, 0xcccccccc\n\ts_mov_b32 vcc_hi, 0xcccccccc\n\t"
-        "v_cndmask_b32_dpp %2, %4, %6, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %3, %5, %7, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
-        : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3)
-        : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3])
-        : "vcc");
-}
 
 __global__ __launch_bounds__(256, 3) void opm_out_kernel(const float* __restrict__ lr, long long ld, const float* __restrict__ Wt,
                                                          const float* __restrict__ bias, float* __restrict__ z, int B, int L,
@@ -60,9 +34,7 @@ __global__ __launch_bounds__(256, 3) void opm_out_kernel(const float* __restrict
     float* rs = cs + OPM_N;                                                 // [64]   r_i
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5;
     // XCD-aware remap: every XCD gets a contiguous range of (b, i) rows, so the (L, 64) table of a sample is fetched into one L2
-    const unsigned nwg = gridDim.x, bid = blockIdx.x;
-    const unsigned q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    const unsigned wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)L), i = (int)(wgid - (unsigned)b * (unsigned)L);
     const float* lrb = lr + (long long)b * L * ld;
 
@@ -78,7 +50,7 @@ __global__ __launch_bounds__(256, 3) void opm_out_kernel(const float* __restrict
         unsigned p0[4], p1[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) split2b(u[2 * e], u[2 * e + 1], p0[e], p1[e]);
-        char* d = Us + kt * OPM_IMG + opm_plane_off(0, n, hh);
+        char* d = Us + kt * OPM_IMG + plane_off<OPM_N>(0, n, hh);
         *reinterpret_cast<u32x4*>(d) = u32x4{p0[0], p0[1], p0[2], p0[3]};
         *reinterpret_cast<u32x4*>(d + OPM_N * 32) = u32x4{p1[0], p1[1], p1[2], p1[3]};
     }
@@ -132,7 +104,7 @@ __global__ __launch_bounds__(256, 3) void opm_out_kernel(const float* __restrict
                 for (int t = 0; t < 3; ++t)
 #pragma unroll
                     for (int p = 0; p < 2; ++p)
-                        fb[t][p] = *reinterpret_cast<const u32x4*>(Us + kt * OPM_IMG + opm_plane_off(p, half * 96 + t * 32 + (lane & 31), h));
+                        fb[t][p] = *reinterpret_cast<const u32x4*>(Us + kt * OPM_IMG + plane_off<OPM_N>(p, half * 96 + t * 32 + (lane & 31), h));
                 // a1 p2, a0 p1, a0 p0 (smallest first), consecutive MFMAs on different accumulators
 #pragma unroll
                 for (int t = 0; t < 3; ++t) acc[t] = mfma_split(fa[kt][1], f16x8_lo(fb[t][0]), acc[t]);
@@ -151,7 +123,7 @@ __global__ __launch_bounds__(256, 3) void opm_out_kernel(const float* __restrict
                     float x[4], o[4];
 #pragma unroll
                     for (int c = 0; c < 4; ++c) x[c] = acc[t][4 * rq + c] + cn;
-                    opm_quad_transpose(x, o);
+                    quad_transpose(x, o);
                     const int jr = j0 + 8 * rq + 4 * h + (lane & 3);
                     if (jr < L) {
                         float* zp = zrow0 + (long long)jr * OPM_N + n4;

@@ -20,8 +20,8 @@ from abx_amd import residue_constants as rc
 # round-6 experiment, OFF unless ABX_ASSEMBLE_BIAS is set: abx_assemble_pair_bias (assembly + the sequence attention's pair bias in one pass) is correct
 # and SLOWER than the two launches (7.14 vs 5.99 ms at 100 samples: its fragment-layout loads and stores touch 32 cache lines per instruction,
 # profiles/r06q_kb_assemble_bias.txt)
-_NO_ASSEMBLE_BIAS = not bool(__import__('os').environ.get('ABX_ASSEMBLE_BIAS'))
-_NO_OPM_FUSED = bool(__import__('os').environ.get('ABX_NO_OPM_FUSED'))      # (A / B runs: the feature tensor + GEMM form of rounds 1 - 5)
+_NO_ASSEMBLE_BIAS = not ops.env_on('ABX_ASSEMBLE_BIAS')
+_NO_OPM_FUSED = ops.env_on('ABX_NO_OPM_FUSED')      # (A / B runs: the feature tensor + GEMM form of rounds 1 - 5)
 P_SEQF = 'impl.seqformer.'
 P_BLK = 'impl.seqformer.seqformer.blocks.0.'
 P_IPA = 'impl.diffusion_module.ScoreNetwork.'
@@ -263,10 +263,10 @@ class Engine:
         # op-group entry points of the C ABI (abx_tri_mul_fwd / abx_tri_attn_block_fwd / abx_transition_fwd, csrc/blocks.hip) - the same
         # kernels in the same order as the descriptor-level path below, which stays as the per-kernel view (bench.py's op profile, the
         # exact-arithmetic tri-mul)
-        self.block_api = not bool(__import__('os').environ.get('ABX_NO_BLOCK_API'))
+        self.block_api = not ops.env_on('ABX_NO_BLOCK_API')
         self._blk_ws = {}
         # True: torsion ResNet + sequence / pLDDT head MLPs of a pass in one launch (abx_heads_tail) instead of 13 - 18 small ones
-        self.fused_heads = not bool(__import__('os').environ.get('ABX_NO_FUSED_HEADS'))
+        self.fused_heads = not ops.env_on('ABX_NO_FUSED_HEADS')
         # K-slices of the IPA final_proj GEMM in front of abx_ipa_tail (0: the tail walks K itself)
         self.ipa_splitk = int(__import__('os').environ.get('ABX_IPA_SPLITK', '11'))
         c = cfg_model.embeddings_and_seqformer

@@ -2,6 +2,7 @@
 stream only; every function launches HIP kernels from libabx_hip.so and raises if the library is unavailable."""
 import ctypes as C
 import math
+import os
 
 import torch
 
@@ -26,7 +27,13 @@ def _f32(t):
     return t
 
 
-GEMM_TUNE = int(__import__('os').environ.get('ABX_GEMM_TUNE', '0'))      # kernel-variant selector (benchmarking only: AbxGemm.tune of every descriptor-level launch)
+def env_on(name):
+    """The one rule for the on / off environment switches, the library's abx_env_on (csrc/capi.hip): ON when the variable is set, not empty
+    and not "0"."""
+    return os.environ.get(name, '') not in ('', '0')
+
+
+GEMM_TUNE = int(os.environ.get('ABX_GEMM_TUNE', '0'))      # kernel-variant selector (benchmarking only: AbxGemm.tune of every descriptor-level launch)
 
 # ---- range safety of the split-f16 kernels (include/abx_hip.h, AbxGemm.range_flag) ----------------------------------------------
 # Every split-f16 launch made through this module carries the address of one device word per GPU and a bit that names its call-site
@@ -35,7 +42,7 @@ GEMM_TUNE = int(__import__('os').environ.get('ABX_GEMM_TUNE', '0'))      # kerne
 # kernels when it is set, so the range contract of the fast path never reaches a caller as a wrong or non-finite result.
 RANGE_TAGS = {'gemm': 1, 'contraction': 2, 'plane_projection': 4, 'tri_mul_tail': 8, 'pair_transition': 16, 'ipa_pair_init': 32,
               'tri_attn': 64, 'ipa_tail': 128, 'heads_tail': 256, 'gemm_late': 512}     # gemm / gemm_late: the plain GEMMs in front of / behind the pair stack
-RANGE_CHECK = not bool(__import__('os').environ.get('ABX_NO_RANGE_CHECK'))     # (A / B measurements of the probe's cost)
+RANGE_CHECK = not env_on('ABX_NO_RANGE_CHECK')     # (A / B measurements of the probe's cost)
 _range_words = {}
 
 
@@ -637,7 +644,7 @@ def tri_attn_kernel_name(L, exact=None, bias_vec=True, rowfused=None):
 TRI_BIAS_LOG2 = float(__import__('numpy').float32(1.4426950408889634) * __import__('numpy').float32(128.0))
 
 
-KV_PLANES = bool(__import__('os').environ.get('ABX_KV_PLANES'))       # round-6 experiment, off by default (measured slower: profiles/r06h_kb_kvplanes.txt)
+KV_PLANES = env_on('ABX_KV_PLANES')       # round-6 experiment, off by default (measured slower: profiles/r06h_kb_kvplanes.txt)
 
 
 def kv_planes_ok(M):

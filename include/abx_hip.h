@@ -162,13 +162,27 @@ typedef struct AbxGemm {
                                                       independent of the batch size fix the arithmetic per op with 1 or 2 */
     /* float16 weight planes: see "Split-f16 operands" above.  b_exp / b2_exp: exponents of B_split / B2_split (|.| <= 100) */
     int b_f16, b_exp, b2_exp;
-    int tune;                                      /* 0 = library default; kernel-variant selector for benchmarking.  Bit 11 (2048): the tile
-                                                      kernels of gemm3.hip for this call, never an A-stationary kernel of gemm_as.hip.
-                                                      Bit 14 (16384): the dual descriptor of the TriangleMultiplication tail (A2, K = 128
-                                                      channel-major, K2 = 192, N = 192, out of place) takes gemm_as_dual_kernel also below its
-                                                      launch-size threshold of 1 024 blocks of 64 rows (tests; the results are bit-identical to
-                                                      the tile kernel's either way).  Environment: ABX_NO_DUAL_AS set and not "0" keeps
-                                                      gemm3_dual_kernel for every dual descriptor of the process (A / B measurements) */
+    /* tune: 0 = library default.  A kernel-variant selector for A / B measurements and for the tests that cross-check two variants bit for
+     * bit; every variant computes the same values.  Each kernel family reads its own bits only, so a value set for one family changes no
+     * other launch.  Constants: ABX_TUNE_* below the struct.
+     *   bit 0      NO_REMAP       workgroups keep the launch order (no XCD-contiguous remap, csrc/grid_map.h): gemm_kernel, gemm3_kernel
+     *   bits 1-3   FORCE          tile kernels of gemm3.hip: 1 = 128 x 128 tiles, 2 = 128 x 192; exact fp32 kernels of gemm.hip: variant
+     *                             1 = BK 16 at two blocks per CU, 2 = at four, 3 = 128 x 128 at three (plain weight GEMM only)
+     *   bit 4      MLP_MINB1      fused transition: gemm3_mlp_kernel<1> (one block per CU: what the second resident block is worth)
+     *   bit 5      MLP_RING3      fused transition: gemm3_mlp3_kernel (three-stage ring for its first GEMM)
+     *   bit 6      GTAIL_2WALK    gated attention tail: the two-walk form gemm3_gtail2w_kernel
+     *   bit 7      DUAL_1WALK     dual GEMM, 96 < N <= 192: gemm3_dual1_kernel (one block per row tile, z walked once)
+     *   bit 8      PERSIST        gemm3_kernel: resident blocks walk the tiles of their XCD's range (-DABX_PERSIST builds only)
+     *   bits 9-10  NARROW_RING    skinny N <= 32 projections: gemm3_narrow_ring_kernel, 1 = 3 stages at 4 blocks per CU, 2 = 4 stages at 3
+     *   bit 11     TILE_ONLY      the tile kernels of gemm3.hip for this call, never an A-stationary kernel of gemm_as.hip
+     *   bits 12-13 ABLATE         gemm_as_kernel: 1 = no slice stores, 2 = no MFMA, 3 = half of the weight DMA (-DABX_AS_ABLATE builds only)
+     *   bit 14     AS_DUAL        the dual descriptor of the TriangleMultiplication tail (A2, K = 128 channel-major, K2 = 192, N = 192, out
+     *                             of place) takes gemm_as_dual_kernel also below its launch-size threshold of 1 024 blocks of 64 rows
+     *                             (tests; the results are bit-identical to the tile kernel's either way)
+     *   bit 15     DUAL_4BLOCK    dual GEMM: gemm3_dual_kernel<128, 96, 32, 96, 4> (four blocks per CU instead of three)
+     * Environment: ABX_NO_DUAL_AS set, not empty and not "0" keeps gemm3_dual_kernel for every dual descriptor of the process (A / B
+     * measurements); the on / off switches all read that way */
+    int tune;
     int c_planes_from, c_planes_group;             /* plain store, c_planes_from > 0: the output columns n >= c_planes_from leave as the B-side
                                                       OPERAND IMAGE of a following split-f16 product instead of fp32 - two float16 planes of
                                                       16 x value (p0 = f16(x'), p1 = f16(x' - p0): the same 4 bytes per element) in groups of
@@ -190,6 +204,23 @@ typedef struct AbxGemm {
     int a_vec_ok, b_vec_ok, fast_ok;               /* filled by the library */
     int c_vec_ok, g_vec_ok, r_vec_ok, rs_vec_ok;   /* filled by the library (16-byte epilogue accesses possible) */
 } AbxGemm;
+
+/* AbxGemm.tune: the table at the field says what each selects */
+#define ABX_TUNE_NO_REMAP 1
+#define ABX_TUNE_FORCE_SHIFT 1
+#define ABX_TUNE_FORCE_MASK (7 << ABX_TUNE_FORCE_SHIFT)
+#define ABX_TUNE_MLP_MINB1 16
+#define ABX_TUNE_MLP_RING3 32
+#define ABX_TUNE_GTAIL_2WALK 64
+#define ABX_TUNE_DUAL_1WALK 128
+#define ABX_TUNE_PERSIST 256
+#define ABX_TUNE_NARROW_RING_SHIFT 9
+#define ABX_TUNE_NARROW_RING_MASK (3 << ABX_TUNE_NARROW_RING_SHIFT)
+#define ABX_TUNE_TILE_ONLY 2048
+#define ABX_TUNE_ABLATE_SHIFT 12
+#define ABX_TUNE_ABLATE_MASK (3 << ABX_TUNE_ABLATE_SHIFT)
+#define ABX_TUNE_AS_DUAL 16384
+#define ABX_TUNE_DUAL_4BLOCK 32768
 int abx_gemm(const AbxGemm* desc, hipStream_t stream);
 /* Two GEMMs over the SAME rows in one launch: `main_gemm` a plain-store split-f16 problem with N % 128 == 0 (k-contiguous fp32 A), `side_gemm` a
  * skinny (N <= 32) transposed-store projection - TriangleAttention's q | k | v | gate projection and its pair bias, which both read

@@ -98,9 +98,9 @@ def test_rejected_descriptor_returns_the_code_of_the_mode_check():
     assert _plan(g) == (rc, '') and b'mutually exclusive' in lib.abx_last_error_string()
 
 
-def _child(case, switch):
-    """The name of `case` in a fresh process that has `switch` set and nothing else changed."""
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), case], env=dict(os.environ, **{switch: '1'}), capture_output=True,
+def _child(case, switch, value='1'):
+    """The name of `case` in a fresh process that has `switch` set to `value` and nothing else changed."""
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), case], env=dict(os.environ, **{switch: value}), capture_output=True,
                          text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     return out.stdout.strip().splitlines()[-1]
@@ -110,6 +110,11 @@ def test_abx_no_gemm_as_switches_the_name_too():
     from abx_amd import ops
     assert ops.gemm_as_kernel_name(_ln_gemm(ROWS, 768)) == 'gemm_as_kernel<0, false, 0, false>'
     assert _child('as_plain', 'ABX_NO_GEMM_AS') == 'None'
+
+
+def test_abx_no_gemm_as_set_to_0_is_off():
+    """One rule for the on / off switches (abx_env_on): set, not empty and not "0"."""
+    assert _child('as_plain', 'ABX_NO_GEMM_AS', '0') == 'gemm_as_kernel<0, false, 0, false>'
 
 
 def test_abx_no_dual_as_switches_the_name_too():

@@ -1,6 +1,6 @@
 """Registers / scratch / LDS / occupancy per kernel of one HIP source, from the compiler's own remarks.
 
-    python tools/kernel_resources.py abx_amd/csrc/gemm3.hip [filter] [-DNAME ...]
+    python tools/kernel_resources.py abx_amd/csrc/gemm3.hip [filter] [-DNAME ...]        (tails.hip, gemm_as.hip, ...: one source per call)
 
 Runs `hipcc -c -Rpass-analysis=kernel-resource-usage` (gfx950, the Makefile's flags) and prints one line per kernel:
 VGPRs, AGPRs, SGPRs, spills, scratch bytes per lane, waves per SIMD, static LDS.  No GPU needed.

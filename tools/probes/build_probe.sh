@@ -9,7 +9,7 @@ mkdir -p $ROOT/tools/probes/bin /tmp/abx_probe_build
 make -C $CS -j8 > /dev/null
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I$CS -I$ROOT/include "$@" -c $CS/$src -o /tmp/abx_probe_build/${name}.o
 objs=""
-for f in capi gemm gemm3 gemm_as attention ipa embed geometry diffuser guidance blocks; do
+for f in capi gemm gemm3 tails gemm_as attention ipa embed geometry diffuser guidance blocks; do
   if [ "$f.hip" == "$src" ]; then objs="$objs /tmp/abx_probe_build/${name}.o"; else objs="$objs $CS/build/$f.o"; fi
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 $objs -o $ROOT/tools/probes/bin/libabx_hip_${name}.so
