@@ -357,6 +357,22 @@ class AbxDevelopabilityArgs(C.Structure):
     ]
 
 
+SHAPE_COLS = 11           # ABX_SHAPE_COLS
+
+
+class AbxShapeArgs(C.Structure):
+    _fields_ = _STRUCTURE_FIELDS + [
+        ('region', c_f),
+        ('radius', c_f),
+        ('sphere', c_f), ('P', I),
+        ('points', c_f),
+        ('probe', C.c_double), ('trim', C.c_double), ('weight', C.c_double),
+        ('out', c_f), ('out_stride', LL),
+        ('max_dots', I), ('j_chunk', I),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -433,6 +449,8 @@ _PROTOS = {
     'abx_polar_scores': (I, [C.POINTER(AbxPolarArgs), c_f, _S]),
     'abx_developability_scores_workspace_bytes': (LL, [I, I]),
     'abx_developability_scores': (I, [C.POINTER(AbxDevelopabilityArgs), c_f, _S]),
+    'abx_shape_scores_workspace_bytes': (LL, [I, I, I, I]),
+    'abx_shape_scores': (I, [C.POINTER(AbxShapeArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

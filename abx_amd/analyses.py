@@ -1,6 +1,6 @@
-"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES (or, the later ones, in EXTENSIONS) beside
-the writers of its tables, and RowLayout, the columns of the row table that a set-level run gathers.  design.main walks ANALYSES +
-EXTENSIONS in their order for the option checks, the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and
+"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES (or, the later ones, in EXTENSIONS and LATER)
+beside the writers of its tables, and RowLayout, the columns of the row table that a set-level run gathers.  design.main walks ANALYSES +
+EXTENSIONS + LATER in their order for the option checks, the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and
 zero-row blocks come from the same declarations), the set-level rows and the files of rank 0: the next analysis is one more entry here
 and nothing in main."""
 import functools
@@ -11,7 +11,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import accuracy, confidence, developability, ensemble, interface, metrics, polar, relax
+from . import accuracy, confidence, developability, ensemble, interface, metrics, polar, relax, shape
 from .io import index_to_str_seq
 
 F64 = torch.float64
@@ -100,11 +100,11 @@ RELAX = Analysis('relax', 'relaxer', lambda batch, a, *_: relax.ViolationRelaxer
 
 
 def _write_with_wild_deltas(kind, out_dir, cname, wild, rows, relaxed):
-    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence, developability): the `wild` line, then (sample
+    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence, developability, shape): the `wild` line, then (sample
     id, values) per sample; values = the module's <KIND>_COLUMNS row and, when relaxed, the row of the relaxed structure.  After the
     columns: delta_<column> = row minus wild for the module's DELTA_COLUMNS.  wild None: every sample has a wild row of its own, the
     last columns of its values, and the `wild` line is their mean."""
-    mod = {'interface': interface, 'polar': polar, 'confidence': confidence, 'developability': developability}[kind]
+    mod = {'interface': interface, 'polar': polar, 'confidence': confidence, 'developability': developability, 'shape': shape}[kind]
     columns, fmt = getattr(mod, f'{kind.upper()}_COLUMNS'), getattr(mod, f'format_{kind}')
     N = len(columns)
     wilds = [wild if wild is not None else v[len(v) - N:] for _, v in rows]
@@ -213,10 +213,10 @@ def _polar_build(batch, a, model, cfg, scorers):
 
 
 def _shared_wild_points(scorers):
-    """--polar or --developability with --interface: the (1, L, 14, 2) point counts of the wild type that interface.wild() fills and
-    polar.wild() / developability.wild() read instead of running the surface kernel again, kept with the scorers of the batch; None
-    without --interface or without either of the two."""
-    users = [scorers[k] for k in ('polar', 'developability') if k in scorers]
+    """--polar, --developability or --shape with --interface: the (1, L, 14, 2) point counts of the wild type that interface.wild() fills
+    and polar.wild() / developability.wild() / shape.wild() read instead of running the surface kernel again, kept with the scorers of the
+    batch; None without --interface or without any of the three."""
+    users = [scorers[k] for k in ('polar', 'developability', 'shape') if k in scorers]
     if users and 'interface' in scorers and 'wild_points' not in scorers:
         scorers['wild_points'] = users[0].new_points(1)
     return scorers.get('wild_points')
@@ -293,10 +293,37 @@ DEVELOPABILITY = _wild_table('developability', developability.DEVELOPABILITY_COL
 EXTENSIONS = (DEVELOPABILITY,)
 
 
+# --shape: the shape complementarity Sc of the interface.  Its dots are the sphere points of the interface analysis, so it is coupled to
+# --interface exactly as --polar is (the three places named there).  A row of -1 says that a dot list outgrew --shape_max_dots: no
+# table is written with such a row.
+SHAPE_CHECKS = [(lambda a: not a.shape_trim >= 0 or not a.shape_weight >= 0 or not a.shape_max_dots >= 1,
+                 '--shape_trim must be >= 0, --shape_weight >= 0, --shape_max_dots >= 1'),
+                (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')]
+
+
+def _write_shape(out_dir, cname, wild, rows, relaxed):
+    """_write_with_wild_deltas('shape', ...); a row of -1 (its dot count is negative) ends the run by the name of the option to raise."""
+    N = len(shape.SHAPE_COLUMNS)
+    written = [wild] + [v[:N] for _, v in rows] + ([v[N:2 * N] for _, v in rows] if relaxed else [])
+    if any(r[6] < 0 for r in written):
+        raise SystemExit(f'--shape: a dot list of {cname} outgrew --shape_max_dots (a row of -1): raise --shape_max_dots')
+    return _write_with_wild_deltas('shape', out_dir, cname, wild, rows, relaxed)
+
+
+SHAPE = _wild_table('shape', shape.SHAPE_COLUMNS, _write_shape,
+                    lambda batch, a, model, cfg, scorers: shape.ShapeScorer(batch, trim=a.shape_trim, weight=a.shape_weight, n_points=a.interface_points,
+                                                                            probe=a.interface_probe, max_dots=a.shape_max_dots,
+                                                                            interface=scorers.get('interface')),
+                    lambda last, scorers: scorers['shape'].wild(points=_shared_wild_points(scorers)), SHAPE_CHECKS)
+
+# The analyses added after EXTENSIONS was pinned in its turn: walked after both
+LATER = (SHAPE,)
+
+
 def check_options(a, set_level):
     """The analyses that the parsed options `a` switch on, in order, after their option checks.  set_level: the run gathers rows."""
     active = []
-    for an in ANALYSES + EXTENSIONS:
+    for an in ANALYSES + EXTENSIONS + LATER:
         if getattr(a, an.flag):
             for bad, text in an.checks:
                 if bad(a):

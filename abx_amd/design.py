@@ -33,14 +33,15 @@ field (sampler.gather_results) for `<output_dir>/<complex>_designs.tsv`, written
 The per-design analyses run on the GPU without a host synchronisation in the sampling loop; abx_amd.analyses states each of them once.
 --score: per-CDR RMSD / AAR, violation and clash counts as further columns of <complex>_designs.tsv; in trajectory mode also
 <complex>_trajectory_scores.tsv.  --relax: rigid-body + chi minimisation of the violation energy of the designed residues;
-<name>_relaxed.pdb beside every design, <complex>_relax.tsv, and _relaxed columns in the five tables that follow, each with a `wild`
+<name>_relaxed.pdb beside every design, <complex>_relax.tsv, and _relaxed columns in the six tables that follow, each with a `wild`
 line for the input complex and one line per sample.  --interface: buried surface, interface residues and contacts,
 <complex>_interface.tsv.  --confidence: the distogram head of the last network call against the emitted structure,
 <complex>_confidence.tsv (--confidence_planes: also <complex>_confidence_contacts.npy).  --accuracy: lDDT, TM-score / GDT / RMSD and
 Fnat against the input structure, <complex>_accuracy.tsv (--accuracy_rows: also <complex>_accuracy_rows.npy).  --polar: hydrogen bonds,
 salt bridges and unsatisfied polar atoms across the interface, <complex>_polar.tsv (--polar_rows: also <complex>_polar_rows.npy).
 --developability: spatial aggregation propensity, chain charges and sequence liabilities of the free antibody,
-<complex>_developability.tsv (--developability_rows: also <complex>_developability_rows.npy).
+<complex>_developability.tsv (--developability_rows: also <complex>_developability_rows.npy).  --shape: the shape complementarity Sc
+of the interface (Lawrence & Colman), both directions, the designed residues' share, gaps and dot counts, <complex>_shape.tsv.
 --ensemble: the designs of a complex compared with each other, Daura clusters and their centres, <complex>_ensemble.tsv
 (--ensemble_matrix: also <complex>_ensemble_rmsd.npy).  No flag changes a file that another one writes; the _rows / _planes tables need
 the sample-sharded schedule (--shard_samples).
@@ -56,7 +57,7 @@ import torch
 
 from . import analyses, features, sampler, synthetic
 from .analyses import (_write_accuracy, _write_confidence, _write_designs, _write_ensemble, _write_interface, _write_polar,      # noqa: F401
-                       _write_relax, _write_trajectory_scores, _write_developability)                 # (the table writers, under the names the host tests call)
+                       _write_relax, _write_trajectory_scores, _write_developability, _write_shape)                 # (the table writers, under the names the host tests call)
 from .config import default_config, load_config
 from .diffuser.full_diffuser import FullDiffuser
 from .io import TrajectoryWriter, index_to_str_seq
@@ -208,6 +209,15 @@ def build_parser():
                     'exposed residue, in [0, 1]')
     ap.add_argument('--developability_rows', action='store_true', help='--developability: also write <complex>_developability_rows.npy, '
                     '(N, L, 4) float64 per residue: mean SAP of its atoms, relative side-chain area, liability bit mask, charge')
+    ap.add_argument('--shape', action='store_true', help='shape complementarity of every design on the GPU (abx_shape_scores): the Sc statistic '
+                    'of Lawrence & Colman on the contact surface of antibody and antigen, both directions, the dots of the designed residues, '
+                    'gaps and dot counts, and their difference to the input complex; writes <complex>_shape.tsv.  The dots are the sphere '
+                    'points of --interface_points: Sc rises with them (512 for values comparable with the literature)')
+    ap.add_argument('--shape_trim', type=float, default=1.5, help='--shape: width of the peripheral band of the buried surface that is dropped '
+                    '(Angstrom, >= 0)')
+    ap.add_argument('--shape_weight', type=float, default=0.5, help='--shape: weight of the squared distance in exp(-w d^2) (1 / square Angstrom, >= 0)')
+    ap.add_argument('--shape_max_dots', type=int, default=8192, help='--shape: capacity of each dot list of a structure; the run ends by this '
+                    'name when an interface outgrows it')
     ap.add_argument('--ensemble', action='store_true', help='compare the designs of a complex with each other on the GPU (abx_ensemble_pairs, '
                     'abx_ensemble_cluster): pairwise RMSD of the designed residues, Daura clusters and their centres; writes <complex>_ensemble.tsv')
     ap.add_argument('--ensemble_cutoff', type=float, default=1.0, help='--ensemble: neighbour distance of the clusters (Angstrom)')

@@ -7,7 +7,7 @@ import os
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxShapeArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1359,6 +1359,42 @@ def developability_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, c
     _side_output(a, 'rows', rows, torch.float64, (B, L, 4))
     ws = torch.empty(max(int(lib.abx_developability_scores_workspace_bytes(B, L)), 16), dtype=torch.uint8, device=dev)
     check(lib.abx_developability_scores(C.byref(a), _p(ws), _stream()), 'abx_developability_scores')
+    return out
+
+
+def shape_workspace_bytes(B, L, P, max_dots):
+    """Bytes of the workspace of shape_scores (abx_shape_scores_workspace_bytes)."""
+    return int(_lib.load().abx_shape_scores_workspace_bytes(int(B), int(L), int(P), int(max_dots)))
+
+
+def shape_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, points, Lab=None, region=None, mask=None, res_mask=None, probe=1.4,
+                 trim=1.5, weight=0.5, max_dots=8192, out=None, j_chunk=0, workspace=None):
+    """Shape complementarity of B structures of one complex (abx_shape_scores; columns: abx_amd.shape.SHAPE_COLUMNS): the Sc statistic of
+    Lawrence & Colman between the rows < Lab and the rows >= Lab on the contact surface of both partners.
+    atom14, seq, the complex, sphere, region, mask, res_mask, probe as for interface_scores; points (B,L,14,2) int32 contiguous, the
+    acc_alone / acc_cplx that interface_scores returned for the SAME structures with this sphere and probe.  trim: width of the peripheral
+    band (Angstrom); weight: of the squared distance in the exponent; max_dots: capacity of each dot list of a structure (a structure
+    beyond it, or one whose dots disagree with `points`, gets a row of -1); j_chunk: dots per LDS chunk of the match (0: the default).
+    out: (B, 11) float64 with unit column stride and any row stride, or None; workspace: a uint8 tensor of at least
+    shape_workspace_bytes(B, L, P, max_dots) bytes, or None (allocated here).  Five launches, no synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = gt_seq.shape[-1]
+    assert sphere.dtype == torch.float64 and sphere.dim() == 2 and sphere.shape[1] == 3 and sphere.is_contiguous() and sphere.device == dev, \
+        'sphere: (P,3) float64 on the device of atom14'
+    a = AbxShapeArgs()
+    B, _, _, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region)
+    a.sphere, a.P = _p(sphere), int(sphere.shape[0])
+    assert points is not None, 'points: the (B,L,14,2) int32 counts of interface_scores'
+    _side_output(a, 'points', points, torch.int32, (B, L, 14, 2))
+    a.probe, a.trim, a.weight, a.max_dots, a.j_chunk = float(probe), float(trim), float(weight), int(max_dots), int(j_chunk)
+    out = _out_rows(a, out, B, _lib.SHAPE_COLS, dev)
+    need = int(lib.abx_shape_scores_workspace_bytes(B, L, a.P, a.max_dots))
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
+        f'workspace: at least {need} uint8 on the device of atom14'
+    check(lib.abx_shape_scores(C.byref(a), _p(workspace), _stream()), 'abx_shape_scores')
     return out
 
 

@@ -24,7 +24,7 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None, developability=None):
+              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None, developability=None, shape=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -67,7 +67,11 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     chain charges and sequence liabilities of the free antibody - with a relaxer 'developability_relaxed', and with
     `developability.want_rows` 'developability_rows' (B, L, 4) float64 of the designs.  It shares the point counts of `interface` like
     `polar`: with all three the surface kernel still runs once per structure set.  Three launches per table, outside any captured step,
-    no host synchronisation."""
+    no host synchronisation.
+    shape: None (the records have exactly today's keys and bits), or an abx_amd.shape.ShapeScorer of the complex: the LAST record gets
+    'shape' (B, len(shape.SHAPE_COLUMNS)) float64 - the shape complementarity Sc of the interface, both directions, the designed
+    residues' dots, the gaps and the dot counts - and with a relaxer 'shape_relaxed'.  It shares the point counts of `interface` like
+    `polar` and `developability`.  Five launches per table, outside any captured step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -138,7 +142,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 if scorer is not None:
                     traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
                 if k == len(steps) - 1:
-                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability)
+                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability, shape)
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)
@@ -160,7 +164,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     return traj
 
 
-def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None):
+def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None, shape=None):
     """What the analyses of sample_fn add to the LAST record, from the model's output `out` of the call that made it and its per-residue
     pLDDT, each on the design and, with a relaxer, on the relaxed structure.  Launches only, no host synchronisation."""
     x, seq, B = rec['atom14_results'], rec['seq'], rec['seq'].shape[0]
@@ -170,7 +174,7 @@ def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accu
             rec['scores_relaxed'] = scorer.score(rec['atom14_relaxed'], seq)
     pts = pts_relaxed = None                                    # point counts of the interface call, when a later scorer shares it
     if interface is not None:
-        sharing = [sc for sc in (polar, developability) if sc is not None and sc.interface is interface]
+        sharing = [sc for sc in (polar, developability, shape) if sc is not None and sc.interface is interface]
         if sharing:
             pts = sharing[0].new_points(B)
             pts_relaxed = sharing[0].new_points(B) if relaxer is not None else None
@@ -192,6 +196,11 @@ def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accu
         rec['developability'] = developability.score(x, seq, points=pts if shared else None, rows=rec.get('developability_rows'))
         if relaxer is not None:
             rec['developability_relaxed'] = developability.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
+    if shape is not None:
+        shared = shape.interface is interface
+        rec['shape'] = shape.score(x, seq, points=pts if shared else None)
+        if relaxer is not None:
+            rec['shape_relaxed'] = shape.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
     if confidence is not None:
         pair = out['representations']['pair']                   # of the call just made: nothing between it and here runs the network
         got = confidence.score(pair, x, seq, planes=bool(confidence.want_planes))

@@ -1106,6 +1106,68 @@ long long abx_developability_scores_workspace_bytes(int B, int L);
 int abx_developability_scores(const AbxDevelopabilityArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Shape complementarity of designs: the Sc statistic of Lawrence & Colman (1993), upstream's sc_value of InterfaceAnalyzerMover, on the
+ * CONTACT part of the molecular (Connolly) surface of each separated partner.  One row of ABX_SHAPE_COLS float64 values per structure of
+ * a batch of B designs of ONE complex (abx_amd.shape.SHAPE_COLUMNS).  No re-entrant (toroidal / concave) patches, no hydrogens; the
+ * antigen is the featurised patch; the value rises with the dot density P.
+ * Structure, sides, atoms and radii exactly as for abx_interface_scores: pred_* / gt_* / pred_mask / res_mask / region, side A = rows
+ * < Lab, side B = rows >= Lab, the atoms are the existing atom14 slots with a positive radius, sphere = P unit vectors (float64), probe.
+ * points: (B, L, 14, 2) int32, REQUIRED: the output of abx_interface_scores for the same structures, sphere and probe.  It names the
+ * atoms that are processed - those with acc_alone > acc_cplx - and fixes every list size and offset before a dot is generated.
+ * DOTS.  A dot is (atom a, point p).  Its surface point is s = c_a + R_a u_p with R_a = (double)r_a + probe, computed as for the interface
+ * (px = xa + R_a * ux: multiply, then add); an atom b occludes s iff (dx*dx + dy*dy) + dz*dz < R_b * R_b, dx = px - (double)x_b.  The dot
+ * is ON THE SURFACE of its side iff no other atom of its own side occludes s, BURIED iff in addition an atom of the other side occludes
+ * s, OPEN iff on the surface and not buried.  Its position is m = c_a + r_a u_p: mx = (double)x_a + (double)r_a * ux (multiply, then
+ * add, no contraction); its normal is u_p.
+ * LISTS of side X, in (row, slot, p) ascending order: I_X = its buried dots; E_X = the open dots of those atoms of X that own at least one
+ * buried dot.  |I_X| = sum of (acc_alone - acc_cplx), |E_X| = sum of acc_cplx over the processed atoms of X.
+ * TRIMMING (Lawrence & Colman's peripheral band): a dot i of I_X is kept iff no e of E_X has (dx*dx + dy*dy) + dz*dz < trim * trim,
+ * dx = mx_i - mx_e.  trim = 0 keeps every dot.  T_X = the kept dots, in order.
+ * MATCH: for i in T_X, j = the dot of T_Y (the other side) with the smallest d2 = (dx*dx + dy*dy) + dz*dz, dx = mx_i - mx_j; ties go to the
+ * lowest list index.  S_i = -((ux_i*ux_j + uy_i*uy_j) + uz_i*uz_j) * exp(-(weight * d2)).
+ * MEDIAN of n values sorted ascending: v[(n-1)/2] for odd n, (v[n/2-1] + v[n/2]) * 0.5 for even n, 0 for n = 0 or an empty T_Y.
+ *   0 sc                  (column 1 + column 2) * 0.5        6 n_dots_antibody     |T_A|
+ *   1 sc_antibody         median S over T_A                  7 n_dots_antigen      |T_B|
+ *   2 sc_antigen          median S over T_B                  8 n_dots_region       dots of T_A in rows with region != 0
+ *   3 sc_region           median S over the dots of T_A      9 n_trimmed_antibody  |I_A| - |T_A|
+ *                         in rows with region != 0          10 n_trimmed_antigen   |I_B| - |T_B|
+ *   4 gap_antibody        sqrt(median d2 over T_A)
+ *   5 gap_antigen         sqrt(median d2 over T_B)
+ * CAPACITY.  max_dots: the capacity of each of the four lists (I_A, I_B, E_A, E_B) of a structure.  A structure whose sizes from
+ * `points` exceed it gets a row of eleven -1; so does a structure with an atom whose recomputed counts disagree with `points`
+ * (or whose `points` name an atom that does not exist, or hold counts outside 0 <= acc_cplx <= acc_alone <= P).  The dot kernel never
+ * writes past the segment `points` promised.
+ * Five launches: (1) one workgroup per structure: atom table, interface atoms, prefix sums of their dot counts in atom order; (2) one
+ * wave per interface atom, the atom table in LDS (L <= 541), the point test of the interface kernel, the dots to their segments by
+ * ballot prefix sums; (3) one workgroup per (side, structure): trimming, E through LDS in chunks, the kept dots compacted in place;
+ * (4) grid (at most 8 workgroups walking tiles of 256 kept dots, side, structure): one thread per dot, the other side's kept dots through
+ * LDS in chunks of j_chunk (0: the default of 1024; 1..1024 otherwise - it exists so that a test can force ragged chunks); (5) one
+ * workgroup per structure: the medians by radix select, the row.  Integer LDS atomics only, no global atomics, no allocation, no
+ * synchronisation: a structure's row depends on nothing but its own inputs.  The caller allocates the workspace
+ * (abx_shape_scores_workspace_bytes: per structure 64 + 504 L + 144 max_dots bytes, rounded up to 16). */
+#define ABX_SHAPE_COLS 11
+typedef struct AbxShapeArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const unsigned char* region;                    /* optional (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs */
+    const double* sphere; int P;                    /* (P,3) unit vectors, 1 <= P <= 1024 */
+    const int* points;                              /* (B,L,14,2) of abx_interface_scores for these structures, sphere and probe */
+    double probe;                                   /* probe radius (1.4), Angstrom */
+    double trim;                                    /* width of the peripheral band (1.5), Angstrom, >= 0 */
+    double weight;                                  /* of d2 in the exponent (0.5), 1 / square Angstrom, >= 0 */
+    double* out; long long out_stride;
+    int max_dots;                                   /* capacity of each dot list of a structure (8192), 1..1048576 */
+    int j_chunk;                                    /* 0: the default */
+    int B, L, Lab;
+} AbxShapeArgs;
+long long abx_shape_scores_workspace_bytes(int B, int L, int P, int max_dots);
+int abx_shape_scores(const AbxShapeArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
