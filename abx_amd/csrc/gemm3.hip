@@ -812,7 +812,9 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
     // HBM streams of the A operand, served by a 128 x 32 tile of the same DMA pipeline (7 blocks per CU keep the stream fed)
     const bool narrow = g.B_split && g.N <= 32 && !g.A_split && g.sAk == 1 && !g.glu && !g.C_split && !g.A2 && !g.out_ln_w &&
                         g.a_pair_transpose <= 0 && g.pair_Lp == 0;
-    if (!g.B_split || g.K % 16 != 0 || (g.N <= 64 && !narrow)) return 1;
+    // (N <= 64 with weight planes goes to the exact kernel; a plane x plane product has no fp32 operands to fall back on and stays here at
+    // any N: the tri-mul contraction of a complex of exactly 64 residues is M = N = 64)
+    if (!g.B_split || g.K % 16 != 0 || (g.N <= 64 && !narrow && !g.A_split)) return 1;
     if ((g.A_split != nullptr) == (g.b_f16 != 0) || !exp_ok(g.b_exp) || !exp_ok(g.b2_exp)) {
         abx_set_error("abx_gemm: B_split must be float16 weight planes (abx_split_weights_f16, b_f16 = 1, |b_exp| <= 100) with an fp32 A "
                       "and activation images (b_f16 = 0) with A_split");

@@ -754,6 +754,31 @@ def test_any_length_takes_the_plane_path_vs_oracle(gpu_model, params, cfg, oracl
     close(f['trans_score'], fr['trans_score'], 3e-4, 1e-4, 'trans_score')
 
 
+def test_complex_of_exactly_64_residues_vs_oracle(gpu_model, params, cfg, oracle_diffuser):
+    """L = 64 is the first length of the split-f16 arithmetic class (ops.gemm_mode), and its tri-mul contraction is the one plane x plane
+    product with N = 64: the dispatch of csrc/gemm3.hip used to turn every N <= 64 away to the exact kernel, which a product of operand
+    images cannot take, and a network call on such a complex failed.  One full call, 2 samples with a masked tail, HIP vs oracle."""
+    from oracle import abx_oracle as O
+    from abx_amd import sampler, ops
+    model, D = gpu_model
+    w, B = dict(L_heavy=28, L_light=24, L_antigen=12, cdr=(16, 23)), 2
+    assert w['L_heavy'] + w['L_light'] + w['L_antigen'] == 64 and ops.gemm_mode(64) == 2
+    b = _synthetic_batch(D, w, B=B, n_masked_tail=2)
+    t_ = torch.full((B,), 0.4040404040404041, dtype=torch.float64, device=DEV)
+    b = sampler.set_t_feats(b, D, t_, torch.ones(B, device=DEV))
+    cpu = _cpu_copy(b)
+    model.max_chunk = None
+    ret = model(b)
+    torch.cuda.synchronize()
+    ref = O.score_network(params, cpu, cfg, oracle_diffuser)
+    f, fr = ret['heads']['folding'], ref['heads']['folding']
+    assert torch.equal(ret['heads']['sequence_module']['seq_0'].cpu(), ref['heads']['sequence_module']['seq_0'])
+    close(ret['representations']['pair'], ref['representations']['pair'], 3e-4, 1e-4, 'pair')
+    close(f['rigids'], fr['rigids'], 1e-4, 1e-4, 'rigids')
+    close(f['final_atom14_positions'], fr['final_atom14_positions'], 1e-3, 1e-4, 'atom14')
+    close(ret['heads']['sequence_module']['logits'], ref['heads']['sequence_module']['logits'], 3e-4, 1e-4, 'logits')
+
+
 @pytest.mark.parametrize('name,B,chunk', [('6ct7like', 100, 40), ('6qd7like', 32, 32)])
 def test_real_complex_lengths_full_batch(gpu_model, params, cfg, oracle_diffuser, name, B, chunk):
     """BASELINE configs 2 and 5 at their real (cropped) lengths, L = 230 x 100 samples and L = 261 x 32 samples of one complex:
