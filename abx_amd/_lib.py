@@ -373,6 +373,29 @@ class AbxShapeArgs(C.Structure):
     ]
 
 
+PATCH_COLS = 18           # ABX_PATCH_COLS
+
+
+class AbxPatchArgs(C.Structure):
+    _fields_ = _STRUCTURE_FIELDS + [
+        ('region', c_f),
+        ('radius', c_f),
+        ('points', c_f),
+        ('chain_id', c_f),
+        ('cdr_def', c_f),
+        ('h', c_f), ('h_max', C.c_double),
+        ('q10', c_f), ('q_max', I),
+        ('table', c_f),
+        ('a', c_f), ('ref', c_f),
+        ('cutoff2', C.c_double), ('vicinity2', C.c_double), ('salt2', C.c_double),
+        ('exposed', C.c_double),
+        ('out', c_f), ('out_stride', LL),
+        ('rows', c_f),
+        ('gly', I),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -451,6 +474,8 @@ _PROTOS = {
     'abx_developability_scores': (I, [C.POINTER(AbxDevelopabilityArgs), c_f, _S]),
     'abx_shape_scores_workspace_bytes': (LL, [I, I, I, I]),
     'abx_shape_scores': (I, [C.POINTER(AbxShapeArgs), c_f, _S]),
+    'abx_patch_scores_workspace_bytes': (LL, [I, I, I]),
+    'abx_patch_scores': (I, [C.POINTER(AbxPatchArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

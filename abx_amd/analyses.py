@@ -1,6 +1,6 @@
-"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES (or, the later ones, in EXTENSIONS and LATER)
-beside the writers of its tables, and RowLayout, the columns of the row table that a set-level run gathers.  design.main walks ANALYSES +
-EXTENSIONS + LATER in their order for the option checks, the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and
+"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES (or, the later ones, in EXTENSIONS, LATER and
+FURTHER) beside the writers of its tables, and RowLayout, the columns of the row table that a set-level run gathers.  design.main walks
+ANALYSES + EXTENSIONS + LATER + FURTHER in their order for the option checks, the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and
 zero-row blocks come from the same declarations), the set-level rows and the files of rank 0: the next analysis is one more entry here
 and nothing in main."""
 import functools
@@ -11,7 +11,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import accuracy, confidence, developability, ensemble, interface, metrics, polar, relax, shape
+from . import accuracy, confidence, developability, ensemble, interface, metrics, patches, polar, relax, shape
 from .io import index_to_str_seq
 
 F64 = torch.float64
@@ -100,11 +100,11 @@ RELAX = Analysis('relax', 'relaxer', lambda batch, a, *_: relax.ViolationRelaxer
 
 
 def _write_with_wild_deltas(kind, out_dir, cname, wild, rows, relaxed):
-    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence, developability, shape): the `wild` line, then (sample
+    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence, developability, shape, patches): the `wild` line, then (sample
     id, values) per sample; values = the module's <KIND>_COLUMNS row and, when relaxed, the row of the relaxed structure.  After the
     columns: delta_<column> = row minus wild for the module's DELTA_COLUMNS.  wild None: every sample has a wild row of its own, the
     last columns of its values, and the `wild` line is their mean."""
-    mod = {'interface': interface, 'polar': polar, 'confidence': confidence, 'developability': developability, 'shape': shape}[kind]
+    mod = {'interface': interface, 'polar': polar, 'confidence': confidence, 'developability': developability, 'shape': shape, 'patches': patches}[kind]
     columns, fmt = getattr(mod, f'{kind.upper()}_COLUMNS'), getattr(mod, f'format_{kind}')
     N = len(columns)
     wilds = [wild if wild is not None else v[len(v) - N:] for _, v in rows]
@@ -213,10 +213,10 @@ def _polar_build(batch, a, model, cfg, scorers):
 
 
 def _shared_wild_points(scorers):
-    """--polar, --developability or --shape with --interface: the (1, L, 14, 2) point counts of the wild type that interface.wild() fills
-    and polar.wild() / developability.wild() / shape.wild() read instead of running the surface kernel again, kept with the scorers of the
-    batch; None without --interface or without any of the three."""
-    users = [scorers[k] for k in ('polar', 'developability', 'shape') if k in scorers]
+    """--polar, --developability, --shape or --patches with --interface: the (1, L, 14, 2) point counts of the wild type that
+    interface.wild() fills and polar.wild() / developability.wild() / shape.wild() / patches.wild() read instead of running the surface
+    kernel again, kept with the scorers of the batch; None without --interface or without any of the four."""
+    users = [scorers[k] for k in ('polar', 'developability', 'shape', 'patches') if k in scorers]
     if users and 'interface' in scorers and 'wild_points' not in scorers:
         scorers['wild_points'] = users[0].new_points(1)
     return scorers.get('wild_points')
@@ -320,10 +320,36 @@ SHAPE = _wild_table('shape', shape.SHAPE_COLUMNS, _write_shape,
 LATER = (SHAPE,)
 
 
+# --patches: the patches of surface hydrophobicity and of charge around the CDRs, the charge symmetry of the Fv and the charge pairing
+# across the interface.  Its exposure comes from the point counts of the interface analysis, so it is coupled to --interface exactly as
+# --polar is (the three places named there).
+PATCHES_CHECKS = [(lambda a: not a.patches_cutoff > 0 or not a.patches_vicinity > 0 or not a.patches_salt > 0 or not 0.0 <= a.patches_exposed <= 1.0,
+                   '--patches_cutoff, --patches_vicinity and --patches_salt must be > 0, --patches_exposed in [0, 1]'),
+                  (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')]
+
+
+def _patches_build(batch, a, model, cfg, scorers):
+    pat = patches.PatchScorer(batch, cutoff=a.patches_cutoff, vicinity=a.patches_vicinity, salt=a.patches_salt, exposed=a.patches_exposed,
+                              n_points=a.interface_points, probe=a.interface_probe, interface=scorers.get('interface'))
+    pat.want_rows = a.patches_rows
+    return pat
+
+
+_write_patches = functools.partial(_write_with_wild_deltas, 'patches')
+PATCHES = _wild_table('patches', patches.PATCHES_COLUMNS, _write_patches, _patches_build,
+                      lambda last, scorers: scorers['patches'].wild(points=_shared_wild_points(scorers)), PATCHES_CHECKS,
+                      Extra('patches_rows', Field('patches_rows', F64, ('L', 4), False), lambda last: last['patches_rows'], lambda t: t.cpu().numpy()))
+
+# The analyses added since LATER was pinned, walked after the three tuples before it.  The NEXT analysis is appended HERE: a test asserts
+# that its own flag is in FURTHER and that ANALYSES, EXTENSIONS and LATER come first, never the contents of FURTHER, so no fifth tuple
+# is needed.
+FURTHER = (PATCHES,)
+
+
 def check_options(a, set_level):
     """The analyses that the parsed options `a` switch on, in order, after their option checks.  set_level: the run gathers rows."""
     active = []
-    for an in ANALYSES + EXTENSIONS + LATER:
+    for an in ANALYSES + EXTENSIONS + LATER + FURTHER:
         if getattr(a, an.flag):
             for bad, text in an.checks:
                 if bad(a):

@@ -42,6 +42,8 @@ salt bridges and unsatisfied polar atoms across the interface, <complex>_polar.t
 --developability: spatial aggregation propensity, chain charges and sequence liabilities of the free antibody,
 <complex>_developability.tsv (--developability_rows: also <complex>_developability_rows.npy).  --shape: the shape complementarity Sc
 of the interface (Lawrence & Colman), both directions, the designed residues' share, gaps and dot counts, <complex>_shape.tsv.
+--patches: the patches of surface hydrophobicity and of charge around the CDRs of the free antibody (TAP's PSH / PPC / PNC), its charge
+symmetry and the charge pairing across the interface, <complex>_patches.tsv (--patches_rows: also <complex>_patches_rows.npy).
 --ensemble: the designs of a complex compared with each other, Daura clusters and their centres, <complex>_ensemble.tsv
 (--ensemble_matrix: also <complex>_ensemble_rmsd.npy).  No flag changes a file that another one writes; the _rows / _planes tables need
 the sample-sharded schedule (--shard_samples).
@@ -57,7 +59,7 @@ import torch
 
 from . import analyses, features, sampler, synthetic
 from .analyses import (_write_accuracy, _write_confidence, _write_designs, _write_ensemble, _write_interface, _write_polar,      # noqa: F401
-                       _write_relax, _write_trajectory_scores, _write_developability, _write_shape)                 # (the table writers, under the names the host tests call)
+                       _write_relax, _write_trajectory_scores, _write_developability, _write_shape, _write_patches)                 # (the table writers, under the names the host tests call)
 from .config import default_config, load_config
 from .diffuser.full_diffuser import FullDiffuser
 from .io import TrajectoryWriter, index_to_str_seq
@@ -218,6 +220,21 @@ def build_parser():
     ap.add_argument('--shape_weight', type=float, default=0.5, help='--shape: weight of the squared distance in exp(-w d^2) (1 / square Angstrom, >= 0)')
     ap.add_argument('--shape_max_dots', type=int, default=8192, help='--shape: capacity of each dot list of a structure; the run ends by this '
                     'name when an interface outgrows it')
+    ap.add_argument('--patches', action='store_true', help='surface patches of every design on the GPU (abx_patch_scores): patches of surface '
+                    'hydrophobicity and of positive / negative charge over the exposed residues near the CDRs of the free antibody (PSH, PPC, '
+                    'PNC of the Therapeutic Antibody Profiler), its Fv charge symmetry, like and opposite charges facing each other across the '
+                    'interface, and their difference to the input complex; writes <complex>_patches.tsv')
+    ap.add_argument('--patches_cutoff', type=float, default=7.5, help='--patches: closest heavy-atom distance of a patch pair and of a cross '
+                    'pair (Angstrom, > 0)')
+    ap.add_argument('--patches_vicinity', type=float, default=4.0, help='--patches: closest heavy-atom distance to an exposed CDR residue that '
+                    'puts an exposed residue into the CDR vicinity (Angstrom, > 0)')
+    ap.add_argument('--patches_salt', type=float, default=3.2, help='--patches: cation-anion distance of a salt bridge within the antibody; a '
+                    'salt-bridged residue takes the hydrophobicity of Gly (Angstrom, > 0)')
+    ap.add_argument('--patches_exposed', type=float, default=0.075, help='--patches: smallest relative side-chain area of an exposed residue, '
+                    'in [0, 1]')
+    ap.add_argument('--patches_rows', action='store_true', help='--patches: also write <complex>_patches_rows.npy, (N, L, 4) float64 per '
+                    'residue: its share of PSH, of PPC or PNC, of attract minus repel across the interface, and its flags (1 present, 2 exposed, '
+                    '4 CDR seed, 8 vicinity, 16 salt-bridged, 32 region)')
     ap.add_argument('--ensemble', action='store_true', help='compare the designs of a complex with each other on the GPU (abx_ensemble_pairs, '
                     'abx_ensemble_cluster): pairwise RMSD of the designed residues, Daura clusters and their centres; writes <complex>_ensemble.tsv')
     ap.add_argument('--ensemble_cutoff', type=float, default=1.0, help='--ensemble: neighbour distance of the clusters (Angstrom)')

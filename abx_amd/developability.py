@@ -3,9 +3,9 @@ to a binder before it is taken forward, on the FREE antibody (rows < Lab; the an
 surface with the antigen taken away): spatial aggregation propensity (SAP, Chennamsetty et al. 2009, with the per-residue grouping
 multiplied out into per-atom weights), the net charge of the heavy and the light chain and their product, and the sequence liabilities
 (N-glycosylation, deamidation, isomerisation, fragmentation, oxidation, free cysteines) of residues whose side chain is exposed.
-Not covered: no pI, no patch metrics (PSH / PPC / PNC), no hydrogens; His carries no charge.  The reference side-chain area is that of
-the ISOLATED residue, somewhat larger than Ala-X-Ala tripeptide values: compare designs with the `wild` line, not with literature
-thresholds.
+Not covered: no pI, no patch metrics (PSH / PPC / PNC: abx_amd.patches), no hydrogens; His carries no charge.  The reference side-chain
+area is that of the ISOLATED residue, somewhat larger than Ala-X-Ala tripeptide values: compare designs with the `wild` line, not with
+literature thresholds.
 
 Every decision is exact: float64 from the float32 coordinates in a fixed IEEE operation order, fixed-point integer weights, int64 sums
 (include/abx_hip.h, AbxDevelopabilityArgs): the row of the device (`DevelopabilityScorer`, abx_developability_scores,

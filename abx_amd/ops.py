@@ -7,7 +7,7 @@ import os
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxShapeArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxShapeArgs, AbxPatchArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1395,6 +1395,56 @@ def shape_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, points, Lab=
     assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
         f'workspace: at least {need} uint8 on the device of atom14'
     check(lib.abx_shape_scores(C.byref(a), _p(workspace), _stream()), 'abx_shape_scores')
+    return out
+
+
+def patch_workspace_bytes(B, L, Lab):
+    """Bytes of the workspace of patch_scores (abx_patch_scores_workspace_bytes)."""
+    return int(_lib.load().abx_patch_scores_workspace_bytes(int(B), int(L), int(Lab)))
+
+
+def patch_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, cdr_def, tables, points, Lab=None, region=None, mask=None,
+                 res_mask=None, cutoff=7.5, vicinity=4.0, salt=3.2, exposed=0.075, h_max=None, q_max=None, gly=7, out=None, rows=None,
+                 workspace=None):
+    """Surface patches of B structures of one complex (abx_patch_scores; columns: abx_amd.patches.PATCHES_COLUMNS): patches of surface
+    hydrophobicity and of positive / negative charge around the CDRs of the free antibody, its charge symmetry, and the charge pairing
+    across the interface.
+    atom14, seq, the complex, region, mask, res_mask as for interface_scores; chain_id, cdr_def (L) int32 as for design_scores; tables =
+    (h (21) float64, q10 (21) int32, a (21,14) float64, ref (21) float64, roles (21,14) int32) on the device (abx_amd.patches.
+    kyte_doolittle / charge_table, abx_amd.developability.weight_table for the surface's points and probe, abx_amd.polar.polar_table);
+    h_max / q_max: the largest |h| / |q10| (None: read from the tables, one host synchronisation each); gly: the residue type whose h a
+    salt-bridged row takes; points (B,L,14,2) int32 contiguous, the acc_alone / acc_cplx that interface_scores returned for the SAME
+    structures.  cutoff, vicinity, salt: closest heavy-atom distances (Angstrom); exposed: smallest relative side-chain area of an
+    exposed residue.
+    out: (B, 18) float64 with unit column stride and any row stride, or None; rows: (B,L,4) float64 contiguous to receive
+    abx_amd.patches.ROW_COLUMNS of every row, or None; workspace: a uint8 tensor of at least patch_workspace_bytes(B, L, Lab) bytes, or
+    None (allocated here).  Three launches, no synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = gt_seq.shape[-1]
+    h, q10, ar, ref, roles = tables
+    assert h.dtype == torch.float64 and tuple(h.shape) == (21,) and q10.dtype == torch.int32 and tuple(q10.shape) == (21,) and \
+        ar.dtype == torch.float64 and tuple(ar.shape) == (21, 14) and ref.dtype == torch.float64 and tuple(ref.shape) == (21,) and \
+        roles.dtype == torch.int32 and tuple(roles.shape) == (21, 14) and all(t.is_contiguous() and t.device == dev for t in tables), \
+        'tables: h (21) float64, q10 (21) int32, a (21,14) float64, ref (21) float64, roles (21,14) int32 on the device of atom14'
+    a = AbxPatchArgs()
+    B, _, Lab, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region, extra=(chain_id, cdr_def))
+    a.chain_id, a.cdr_def = own(chain_id, torch.int32), own(cdr_def, torch.int32)
+    a.h, a.q10, a.a, a.ref, a.table = _p(h), _p(q10), _p(ar), _p(ref), _p(roles)
+    a.h_max = float(h.abs().max()) if h_max is None else float(h_max)
+    a.q_max = int(q10.abs().max()) if q_max is None else int(q_max)
+    assert points is not None, 'points: the (B,L,14,2) int32 counts of interface_scores'
+    _side_output(a, 'points', points, torch.int32, (B, L, 14, 2))
+    a.cutoff2, a.vicinity2, a.salt2 = float(cutoff) * float(cutoff), float(vicinity) * float(vicinity), float(salt) * float(salt)
+    a.exposed, a.gly = float(exposed), int(gly)
+    out = _out_rows(a, out, B, _lib.PATCH_COLS, dev)
+    _side_output(a, 'rows', rows, torch.float64, (B, L, 4))
+    need = int(lib.abx_patch_scores_workspace_bytes(B, L, Lab))
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
+        f'workspace: at least {need} uint8 on the device of atom14'
+    check(lib.abx_patch_scores(C.byref(a), _p(workspace), _stream()), 'abx_patch_scores')
     return out
 
 

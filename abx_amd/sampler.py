@@ -24,7 +24,8 @@ def set_t_feats(feats, diffuser, t, ones):
 
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
-              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None, developability=None, shape=None):
+              scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None, developability=None, shape=None,
+              patches=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -71,7 +72,12 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     shape: None (the records have exactly today's keys and bits), or an abx_amd.shape.ShapeScorer of the complex: the LAST record gets
     'shape' (B, len(shape.SHAPE_COLUMNS)) float64 - the shape complementarity Sc of the interface, both directions, the designed
     residues' dots, the gaps and the dot counts - and with a relaxer 'shape_relaxed'.  It shares the point counts of `interface` like
-    `polar` and `developability`.  Five launches per table, outside any captured step, no host synchronisation."""
+    `polar` and `developability`.  Five launches per table, outside any captured step, no host synchronisation.
+    patches: None (the records have exactly today's keys and bits), or an abx_amd.patches.PatchScorer of the complex: the LAST record
+    gets 'patches' (B, len(patches.PATCHES_COLUMNS)) float64 - the patches of surface hydrophobicity and charge around the CDRs of the
+    free antibody, its charge symmetry, the charge pairing across the interface - with a relaxer 'patches_relaxed', and with
+    `patches.want_rows` 'patches_rows' (B, L, 4) float64 of the designs.  It shares the point counts of `interface` like `polar`,
+    `developability` and `shape`.  Three launches per table, outside any captured step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -142,7 +148,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 if scorer is not None:
                     traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
                 if k == len(steps) - 1:
-                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability, shape)
+                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability, shape, patches)
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)
@@ -164,7 +170,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     return traj
 
 
-def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None, shape=None):
+def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None, shape=None, patches=None):
     """What the analyses of sample_fn add to the LAST record, from the model's output `out` of the call that made it and its per-residue
     pLDDT, each on the design and, with a relaxer, on the relaxed structure.  Launches only, no host synchronisation."""
     x, seq, B = rec['atom14_results'], rec['seq'], rec['seq'].shape[0]
@@ -174,7 +180,7 @@ def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accu
             rec['scores_relaxed'] = scorer.score(rec['atom14_relaxed'], seq)
     pts = pts_relaxed = None                                    # point counts of the interface call, when a later scorer shares it
     if interface is not None:
-        sharing = [sc for sc in (polar, developability, shape) if sc is not None and sc.interface is interface]
+        sharing = [sc for sc in (polar, developability, shape, patches) if sc is not None and sc.interface is interface]
         if sharing:
             pts = sharing[0].new_points(B)
             pts_relaxed = sharing[0].new_points(B) if relaxer is not None else None
@@ -201,6 +207,13 @@ def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accu
         rec['shape'] = shape.score(x, seq, points=pts if shared else None)
         if relaxer is not None:
             rec['shape_relaxed'] = shape.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
+    if patches is not None:
+        shared = patches.interface is interface
+        if patches.want_rows:
+            rec['patches_rows'] = patches.new_rows(B)
+        rec['patches'] = patches.score(x, seq, points=pts if shared else None, rows=rec.get('patches_rows'))
+        if relaxer is not None:
+            rec['patches_relaxed'] = patches.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
     if confidence is not None:
         pair = out['representations']['pair']                   # of the call just made: nothing between it and here runs the network
         got = confidence.score(pair, x, seq, planes=bool(confidence.want_planes))

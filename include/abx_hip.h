@@ -1168,6 +1168,81 @@ long long abx_shape_scores_workspace_bytes(int B, int L, int P, int max_dots);
 int abx_shape_scores(const AbxShapeArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Surface patches of designs: three of the five numbers of the Therapeutic Antibody Profiler (Raybould et al. 2019) - the patches of
+ * surface hydrophobicity (PSH), of positive (PPC) and of negative charge (PNC) - with its Fv charge symmetry parameter (SFvCSP) and its
+ * CDR length on the FREE antibody (rows < Lab), and the charge pairing ACROSS the interface out to the same cutoff.  One row of
+ * ABX_PATCH_COLS float64 values per structure of a batch of B designs of ONE complex (abx_amd.patches.PATCHES_COLUMNS).  Not the TAP
+ * server's numbers: the exposure reference is the isolated-residue area of abx_developability_scores, the CDRs are cdr_def as given (no
+ * +-2 anchors), no hydrogens, no pI.
+ * The structure and the complex are given as for abx_developability_scores (pred_* rows < Lpred, residue types of rows < Lab from
+ * pred_seq, clamped to 0..20; pred_mask / res_mask optional; region (L) bytes shared by the batch, optional; chain_id, cdr_def (L)).
+ * points: (B, L, 14, 2) int32, the output of abx_interface_scores for the same structures; only acc_alone (points[..., 0]) is read.
+ * COUNTED ATOMS: the slots of ANY row that exist and have radius > 0.  A row is PRESENT if it has a counted atom.  Coordinates must be
+ * finite.  Float32 coordinates are converted to float64; no operation is fused.
+ * Tables of the caller: h [21] doubles, the hydrophobicity of a residue type (abx_amd.patches.kyte_doolittle: 1..2, X = 0) and h_max,
+ * the largest |h|; q10 [21] int32, its charge in tenths (abx_amd.patches.charge_table: K, R +10, D, E -10, H +1) and q_max, the largest
+ * |q10|; table [21][14] int32, the role bits of abx_polar_scores, of which ABX_POLAR_CATION and ABX_POLAR_ANION are read; a [21][14]
+ * and ref [21] doubles as for abx_developability_scores; gly: the residue type whose h a salt-bridged row takes.
+ *   1. EXPOSED row i < Lab: present, ref[type] > 0 and rel >= exposed * ref[type], rel as for abx_developability_scores (a type without
+ *      a reference area - Gly, X - is never exposed).
+ *   2. D2[i][j], i < Lab, j < L, j != i: the minimum over the counted atoms a of i and b of j of (dx*dx + dy*dy) + dz*dz,
+ *      dx = (double)x_b - (double)x_a (likewise y, z); +inf if either row has none.  S2[i][j]: the same minimum over the atom pairs of
+ *      which one has the CATION bit and the other the ANION bit.  Both are symmetric bit for bit.
+ *   3. SALT-BRIDGED row i < Lab: some j < Lab, j != i, has S2[i][j] <= salt2.
+ *   4. SEED: exposed and cdr_def in {1, 3, 5, 8, 10, 12}.  VICINITY: exposed, and a seed or with D2[i][s] <= vicinity2 to a seed s != i.
+ *   5. h_eff = h[gly] for a salt-bridged row, h[type] otherwise.  Q = (double)q10[type] / 10.0.
+ *   6. Over the pairs i < j < Lab, both in the vicinity, D2 <= cutoff2:  r2 = max(D2, 1.0) (two coincident atoms keep the term bounded);
+ *      psh_q += llrint(2^30 * ((h_eff_i * h_eff_j) / r2));  c = llrint(2^30 * (fabs(Q_i * Q_j) / r2));  ppc_q += c if both q10 > 0,
+ *      pnc_q += c if both q10 < 0.  The *_region sums take the pairs with region[i] | region[j].
+ *   7. sfvcsp = (double)(sum of q10 over the exposed rows with chain_id == chain_id[0]  x  sum over the other exposed rows) / 100.0.
+ *   8. Over the pairs i < Lab <= j, both present, q10_i * q10_j != 0, D2 <= cutoff2 (no exposure rule): the same c; opposite signs go
+ *      to cross_attract, equal signs to cross_repel; the *_region sums take the pairs with region[i].
+ *   0 psh         psh_q / 2^30              7 cross_attract          11 n_cdr           present rows < Lab with a CDR code
+ *   1 ppc         ppc_q / 2^30              8 cross_repel            12 n_exposed       exposed rows
+ *   2 pnc         pnc_q / 2^30              9 cross_attract_region   13 n_vicinity      rows in the vicinity
+ *   3 sfvcsp                               10 cross_repel_region     14 n_pairs         pairs of 6
+ *   4 psh_region, 5 ppc_region, 6 pnc_region                         15 n_salt          salt-bridged rows in the vicinity
+ *                                                                    16 n_cross, 17 n_cross_region   pairs of 8
+ * rows: optional (B, L, 4) doubles per row: the sum of its psh terms / 2^30, of its ppc or pnc terms / 2^30 (a row has one sign), its
+ * cross_attract minus its cross_repel terms / 2^30 (antigen rows too), and its flags: 1 present, 2 exposed, 4 seed, 8 vicinity,
+ * 16 salt-bridged, 32 region (0 for an absent row).
+ * Bounds: a term is at most 2^30 h_max^2 (2^32 with the shipped table), a cross term at most 2^30 (q_max / 10)^2, over at most Lab^2 / 2
+ * and Lab (L - Lab) pairs: with L <= 2048 every sum stays below 2^53 and its division by 2^30 is exact.  A problem with
+ * 2^30 h_max^2 Lab^2 or 2^30 (q_max / 10)^2 Lab L >= 2^62 could leave int64 and is an argument error, as is L > 2048 (the row tables
+ * of the last kernel live in LDS).
+ * Three launches: (1) one workgroup per structure: type, presence, exposure, seed and region of every row, its counted atoms compacted
+ * to the front of its 14 float4 (x, y, z, role bits) in the workspace; (2) grid (tile of 256 j-rows, tile of 16 i-rows, structure): one
+ * lane per j-row with its atoms in registers as float64, the atoms of the i-rows broadcast from LDS; D2 to a (Lab, L) float64 plane of
+ * the workspace, the salt bit of a j-row against the tile to a byte; (3) one workgroup per structure: salt-bridged rows, vicinity, the
+ * terms, the row.  Integer LDS atomics only, no global atomics, no allocation, no synchronisation: a structure's row depends on nothing
+ * but its own inputs.  The caller allocates the workspace (abx_patch_scores_workspace_bytes). */
+#define ABX_PATCH_COLS 18
+typedef struct AbxPatchArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const unsigned char* region;                    /* optional (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs */
+    const int* points;                              /* (B,L,14,2) of abx_interface_scores */
+    const int* chain_id;                            /* (L) */
+    const int* cdr_def;                             /* (L) */
+    const double* h; double h_max;                  /* [21] hydrophobicity of a residue type, the largest |h| */
+    const int* q10; int q_max;                      /* [21] charge of a residue type in tenths, the largest |q10| */
+    const int* table;                               /* [21][14] role bits of abx_polar_scores */
+    const double* a; const double* ref;             /* [21][14] area of a sphere point, [21] reference side-chain areas */
+    double cutoff2, vicinity2, salt2;               /* squared distances of a pair (56.25), of the vicinity (16.0), of a salt bridge (10.24) */
+    double exposed;                                 /* smallest relative side-chain area of an exposed residue (0.075), in [0, 1] */
+    double* out; long long out_stride;
+    double* rows;                                   /* optional (B,L,4) */
+    int gly;                                        /* the residue type whose h a salt-bridged row takes */
+    int B, L, Lab;
+} AbxPatchArgs;
+long long abx_patch_scores_workspace_bytes(int B, int L, int Lab);
+int abx_patch_scores(const AbxPatchArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
