@@ -421,6 +421,7 @@ _PROTOS = {
     'abx_tri_attn_plan': (I, [C.POINTER(AbxTriAttn), I, C.c_char_p, I]),
     'abx_tri_attn_rowfused_fwd': (I, [C.POINTER(AbxTriAttn), c_f, LL, LL, LL, C.POINTER(AbxTriRowPack), I, _S]),
     'abx_seq_attn_fwd': (I, [c_f, c_f, c_f, c_f, c_f, I, I, I, I, F, _S]),
+    'abx_seq_attn_plan': (I, [I, C.c_char_p, I, C.POINTER(C.c_int)]),
     'abx_ipa_pack': (I, [c_f, c_f, c_f, c_f, c_f, c_f, I, I, F, _S]),
     'abx_ipa_attn': (I, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, I, I, _S]),
     'abx_debug_poison_lds': (I, [C.c_uint, _S]),

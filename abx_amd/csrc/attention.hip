@@ -1891,8 +1891,10 @@ static int tri_attn_run(const AbxTriAttn* ap, hipStream_t st, AbxPlan* plan) {
 
 extern "C" int abx_tri_attn_fwd(const AbxTriAttn* ap, hipStream_t st) { return tri_attn_run(ap, st, nullptr); }
 
-extern "C" int abx_seq_attn_fwd(const float* qkv, const float* bias, const float* keymask, const float* gate, float* out,
-                                int B, int L, int H, int D, float scale, hipStream_t st) {
+// abx_seq_attn_fwd (plan == nullptr) / abx_seq_attn_plan: the kernel is launched or named where it is chosen; qblk_out (nullable) receives
+// the query rows per workgroup of that launch
+static int seq_attn_run(const float* qkv, const float* bias, const float* keymask, const float* gate, float* out, int B, int L, int H, int D,
+                        float scale, hipStream_t st, AbxPlan* plan, int* qblk_out) {
     ABX_REQUIRE(qkv && bias && out && B > 0 && L > 0 && H > 0, "abx_seq_attn_fwd: bad args");
     ABX_REQUIRE(D == 17, "abx_seq_attn_fwd: head dim must be 17 (544 / 32)");
     ABX_REQUIRE(H <= 65535 && B <= 65535, "abx_seq_attn_fwd: grid too large");
@@ -1905,19 +1907,34 @@ extern "C" int abx_seq_attn_fwd(const float* qkv, const float* bias, const float
     const int qblk = (((L + nb - 1) / nb) + 3) / 4 * 4;
     const size_t lds = ((size_t)2 * L * 20 + (size_t)(nt / 64) * 4 * nkt * 64) * sizeof(float);
     ABX_REQUIRE(lds <= 160 * 1024, "abx_seq_attn_fwd: L too large for the LDS-resident K / V (L <= 716)");
+    if (qblk_out) *qblk_out = qblk;
     const dim3 grid((L + qblk - 1) / qblk, H, B), block(nt);
-    auto launch = [&](auto kern, int) -> int {
-        if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, "abx_seq_attn_fwd")) return rc;
-        hipLaunchKernelGGL(kern, grid, block, lds, st, qkv, bias, keymask, gate, out, L, H, scale, qblk);
-        return abx_check_launch("abx_seq_attn_fwd");
-    };
+#define SEQ_LAUNCH(NK, NT)                                                                                                                      \
+    ABX_LAUNCH_LIT(plan, "abx_seq_attn_fwd", (&seq_attn2_kernel<NK, NT>), 160 * 1024, grid, block, lds, st, qkv, bias, keymask, gate, out, L, H, \
+                   scale, qblk)
     switch (nkt) {
-        case 2: return launch(&seq_attn2_kernel<2, 1024>, 0);
-        case 4: return launch(&seq_attn2_kernel<4, 1024>, 1);
-        case 6: return launch(&seq_attn2_kernel<6, 1024>, 2);
-        case 8: return launch(&seq_attn2_kernel<8, 512>, 3);
-        default: return launch(&seq_attn2_kernel<12, 256>, 4);
+        case 2: return SEQ_LAUNCH(2, 1024);
+        case 4: return SEQ_LAUNCH(4, 1024);
+        case 6: return SEQ_LAUNCH(6, 1024);
+        case 8: return SEQ_LAUNCH(8, 512);
+        default: return SEQ_LAUNCH(12, 256);
     }
+#undef SEQ_LAUNCH
+}
+
+extern "C" int abx_seq_attn_fwd(const float* qkv, const float* bias, const float* keymask, const float* gate, float* out,
+                                int B, int L, int H, int D, float scale, hipStream_t st) {
+    return seq_attn_run(qkv, bias, keymask, gate, out, B, L, H, D, scale, st, nullptr, nullptr);
+}
+
+extern "C" int abx_seq_attn_plan(int L, char* name, int cap, int* qblk) {
+    ABX_REQUIRE(name && cap > 0, "abx_seq_attn_plan: no room for the name");
+    AbxPlan plan = {};
+    // one sample of the model's 32 heads x 17 channels on stand-in operands that pass the null checks - an address is looked at, never followed
+    alignas(16) static float stand_in[4] = {};
+    if (int rc = seq_attn_run(stand_in, stand_in, nullptr, nullptr, stand_in, 1, L, 32, 17, 0.f, nullptr, &plan, qblk)) return rc;
+    snprintf(name, (size_t)cap, "%s", plan.name);
+    return ABX_OK;
 }
 
 // ---- row-fused triangle attention: pack, switch, entry ------------------------------------------------------------------------------

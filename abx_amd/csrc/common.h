@@ -31,9 +31,9 @@ bool abx_env_on(const char* name);
         }                                 \
     } while (0)
 
-// ---- one launch path for the GEMM and triangle-attention dispatchers -----------------------------------------------------------
-// The dispatchers take a nullable plan.  Null: they launch.  Non-null (abx_gemm_plan / abx_tri_attn_plan): the branch that would launch
-// writes its kernel's name instead and returns 0 - no HIP runtime call, no operand dereferenced, so it runs without a GPU.  The name
+// ---- one launch path for the GEMM and attention dispatchers -------------------------------------------------------------------------
+// The dispatchers take a nullable plan.  Null: they launch.  Non-null (abx_gemm_plan / abx_tri_attn_plan / abx_seq_attn_plan): the branch that would
+// launch writes its kernel's name instead and returns 0 - no HIP runtime call, no operand dereferenced, so it runs without a GPU.  The name
 // stands at the launch (ABX_LAUNCH), printed from the template arguments of that very instantiation: there is no second selection.
 struct AbxPlan { char name[128]; };
 #define ABX_BOOL(b) ((b) ? "true" : "false")

@@ -94,7 +94,7 @@ GEMM_EXACT = False   # True: every GEMM on the exact fp32 MFMA kernel (v_mfma_f3
 
 
 def _plan_name(fn, *args):
-    """(return code, kernel name) of abx_gemm_plan / abx_tri_attn_plan: the library's own dispatch run up to the launch.  Needs no GPU."""
+    """(return code, kernel name) of abx_gemm_plan / abx_tri_attn_plan / abx_seq_attn_plan: the library's own dispatch run up to the launch.  Needs no GPU."""
     buf = C.create_string_buffer(128)
     rc = fn(*args, buf, len(buf))
     return rc, buf.value.decode()
@@ -705,6 +705,16 @@ def tri_attn(qkvg, biasT, keymask, out, B, L, per_row, H=4, D=48, bias_is_qk=Fal
         return out
     check(lib.abx_tri_attn_fwd(C.byref(a), _stream()), 'abx_tri_attn_fwd')
     return out
+
+
+def seq_attn_kernel_name(L, with_qblk=False):
+    """Name of the seq_attn2_kernel instantiation abx_seq_attn_fwd launches for a complex of length L - the library's answer
+    (abx_seq_attn_plan: the dispatch of csrc/attention.hip itself, run up to the launch; needs no GPU).  with_qblk: (name, query rows per
+    workgroup) - the queries are split over ceil(L / qblk) workgroups per (sample, head).  A length the entry point refuses raises as it does."""
+    qblk = C.c_int(0)
+    rc, name = _plan_name(lambda b, n: _lib.load().abx_seq_attn_plan(int(L), b, n, C.byref(qblk)))
+    check(rc, 'abx_seq_attn_plan')
+    return (name, int(qblk.value)) if with_qblk else name
 
 
 def seq_attn(qkv, biasT, keymask, gate, out, B, L, H=32, D=17):

@@ -400,6 +400,10 @@ int abx_tri_attn_plan(const AbxTriAttn* desc, int rowfused, char* name, int cap)
  * out [B*L][H*D] = softmax(...) v * sigmoid(gate).  D <= 32. */
 int abx_seq_attn_fwd(const float* qkv, const float* bias, const float* keymask, const float* gate, float* out, int B, int L,
                      int H, int D, float scale, hipStream_t stream);
+/* diagnostics: the name of the kernel instantiation abx_seq_attn_fwd launches for one sample of length L (32 heads of 17 channels), written
+ * to name[cap], and - qblk not null - the query rows per workgroup of that launch (the grid's x extent is ceil(L / *qblk)).  A length the
+ * entry point refuses returns the same negative code and message.  No HIP runtime call, no operand dereferenced (see abx_gemm_plan). */
+int abx_seq_attn_plan(int L, char* name, int cap, int* qblk);
 
 /* Invariant Point Attention core (folding.py:47-132).  abx_ipa_pack turns the fused projection rows
  * [q_scalar 192 | kv_scalar 384 | q_point_local 144 | kv_point_local 432] into global-frame packs

@@ -855,9 +855,11 @@ def test_heads_tail(ops, M, with_plddt):
 
 @pytest.mark.parametrize('L', [52, 131, 230, 402, 600])
 def test_seq_attn(ops, L):
-    """L = 52: one key per lane slot, partial; 131: three key slots (4-slot instantiation), one query block; 230: two query
-    blocks of 128; 402: three query blocks, 7 key slots (8-slot instantiation); 600: the 12-slot / 4-wave instantiation, two query blocks.  One sample has every key
-    masked but two."""
+    """The instantiation follows ceil(L / 64) keys per lane; the queries of a (sample, head) stay in ONE workgroup up to L = 512 and are
+    split over ceil(L / 512) beyond, in blocks rounded up to 4 rows (abx_seq_attn_fwd; ops.seq_attn_kernel_name gives both).  L = 52: one
+    partial key slot (2-slot instantiation); 131: three key slots and 230: four (4-slot instantiation); 402: 7 key slots (8-slot instantiation,
+    8 waves); all of these one workgroup per head; 600: 10 key slots (the 12-slot / 4-wave instantiation), two workgroups of 300 queries.
+    The 6-slot instantiation, the exact multiples and the limits are in tests/test_gpu_node_attn.py.  One sample has every key masked but two."""
     from oracle import abx_oracle as O
     B, H, D = 2, 32, 17
     qkv = torch.randn(B, L, H, 3 * D, generator=g(34))

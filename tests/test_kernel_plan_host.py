@@ -1,5 +1,5 @@
-"""Kernel names come from the library's own dispatch (abx_gemm_plan / abx_tri_attn_plan: the dispatchers of csrc/gemm.hip, gemm3.hip,
-gemm_as.hip and attention.hip run up to the launch and name the kernel there).  Descriptors on placeholder addresses, literal names; no GPU.
+"""Kernel names come from the library's own dispatch (abx_gemm_plan / abx_tri_attn_plan / abx_seq_attn_plan: the dispatchers of csrc/gemm.hip,
+gemm3.hip, gemm_as.hip and attention.hip run up to the launch and name the kernel there).  Descriptors on placeholder addresses, literal names; no GPU.
 Run as a script with a case name, this file prints that case's name: the environment-switch tests start it as a fresh child process,
 because the library reads its switches once."""
 import ctypes
@@ -86,6 +86,28 @@ def test_triangle_attention():
     assert ops.tri_attn_kernel_name(97, exact=False, rowfused=False) == 'tri_attn8_kernel<128, 768, true>'
     assert ops.tri_attn_kernel_name(352, exact=True) == 'tri_attn_kernel'
     assert ops.tri_attn_kernel_name(352, exact=False, rowfused=True) == 'tri_attn8_rowfused_kernel'
+
+
+def test_sequence_attention():
+    import pytest
+    from abx_amd import ops, _lib
+    # keys per lane 2, 4, 6, 8, 12 by ceil(L / 64), on 1024, 1024, 1024, 512, 256 threads; both sides of every threshold
+    for L, name in ((1, '2, 1024'), (128, '2, 1024'), (129, '4, 1024'), (256, '4, 1024'), (257, '6, 1024'), (352, '6, 1024'), (384, '6, 1024'),
+                    (385, '8, 512'), (512, '8, 512'), (513, '12, 256'), (716, '12, 256')):
+        assert ops.seq_attn_kernel_name(L) == f'seq_attn2_kernel<{name}>', L
+    # the queries of a (sample, head) go to one workgroup up to L = 512, to ceil(L / 512) beyond; rows per workgroup rounded up to 4
+    assert [ops.seq_attn_kernel_name(L, with_qblk=True)[1] for L in (1, 5, 352, 512, 513, 716)] == [4, 8, 352, 512, 260, 360]
+    # a refused length: the code and message of the entry point, no name
+    lib = _lib.load()
+    for L in (717, 768, 800, 0):
+        buf, qblk = ctypes.create_string_buffer(64), ctypes.c_int(-1)
+        assert lib.abx_seq_attn_plan(L, buf, len(buf), ctypes.byref(qblk)) < 0 and buf.value == b'' and qblk.value == -1
+        assert (b'L <= 716' if L else b'bad args') in lib.abx_last_error_string()
+        with pytest.raises(_lib.AbxHipError):
+            ops.seq_attn_kernel_name(L)
+    assert lib.abx_seq_attn_plan(64, None, 0, None) < 0 and b'abx_seq_attn_plan' in lib.abx_last_error_string()
+    buf = ctypes.create_string_buffer(64)
+    assert lib.abx_seq_attn_plan(64, buf, len(buf), None) == 0 and buf.value == b'seq_attn2_kernel<2, 1024>'
 
 
 def test_rejected_descriptor_returns_the_code_of_the_mode_check():
