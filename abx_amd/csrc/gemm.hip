@@ -81,7 +81,8 @@ struct TileLoader {
     }
 
     // LayerNorm statistics of the A rows, accumulated from the operand registers while they wait for their LDS slot
-    // (inline-LN mode).  KC: slot i = one row, sums of (x - shift[i]); RC: slots 0..3 = the four rows of this lane's float4.
+    // (inline-LN mode), as sums of (x - shift).  KC: slot i = one row, shift[i]; RC: slots 0..3 = the four rows of this lane's float4,
+    // shift[0..3], and slot i of the loader is one k-row (predicated: a k-row past K holds zeros, not x).
     __device__ __forceinline__ void stats_accum(float* __restrict__ s, float* __restrict__ q, const float* __restrict__ shift,
                                                 int k0, int K) const {
         const int tid = threadIdx.x;
@@ -99,19 +100,21 @@ struct TileLoader {
                             q[i] = fmaf(d, d, q[i]);
                         }
                     }
-                } else {
+                } else if (!EDGE || k0 + idx / (BMN / 4) < K) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
-                        s[c] += v[i][c];
-                        q[c] = fmaf(v[i][c], v[i][c], q[c]);
+                        const float d = v[i][c] - shift[c];
+                        s[c] += d;
+                        q[c] = fmaf(d, d, q[c]);
                     }
                 }
             }
         }
     }
 
-    // shift (KC, inline LayerNorm): the row's first element is subtracted from the operand so that the folded LayerNorm
-    // rstd * (acc - (mean - shift) * csum) has no mean >> sigma cancellation
+    // shift (inline LayerNorm; KC: shift[i] is the row's, RC: shift[0..3] are the four rows'): the row's first element is subtracted
+    // from the operand so that the folded LayerNorm rstd * (acc - (mean - shift) * csum) has no mean >> sigma cancellation.  (A k-row
+    // past K then holds -shift instead of 0: its B row is 0.)
     __device__ __forceinline__ void store(float* __restrict__ lds, bool relu, const float* __restrict__ shift = nullptr) const {
         const int tid = threadIdx.x;
 #pragma unroll
@@ -119,9 +122,9 @@ struct TileLoader {
             const int idx = tid + i * 256;
             if (NVEC % 256 == 0 || idx < NVEC) {
                 f32x4 r = v[i];
-                if (KC && shift) {
+                if (shift) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) r[c] -= shift[i];
+                    for (int c = 0; c < 4; ++c) r[c] -= shift[KC ? i : c];
                 }
                 if (relu) {
 #pragma unroll
@@ -178,10 +181,22 @@ __device__ __forceinline__ void gemm_block(const AbxGemm& g, float* smem, int mt
         if (AKC) {      // shift = first element of the row (held by the kq == 0 lane of the quad): kills the E[x^2]-mean^2 cancellation
 #pragma unroll
             for (int i = 0; i < TileLoader<BM, BK, AKC, EDGE>::NV; ++i) lshift[i] = __shfl(la.v[i][0], lane & ~3, 64);
+        } else {        // m-contiguous A: the k = 0 elements of this lane's four rows (the float4 the tid / (BM / 4) == 0 lanes hold: an L1 hit)
+            const int mn = m0 + (threadIdx.x % (BM / 4)) * 4;
+            const float* p = Ab + mn;
+            if (!EDGE || (a_vec && mn + 3 < g.M)) {
+                const f32x4 r = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) lshift[c] = r[c];
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (mn + c < g.M) lshift[c] = p[c];
+            }
         }
         la.stats_accum(ls, lq, lshift, 0, g.K);
     }
-    const float* shp = (ln_inline && AKC) ? lshift : nullptr;
+    const float* shp = ln_inline ? lshift : nullptr;
     la.store(As, relu, shp);
     lb.store(Bs, false);
     __syncthreads();
@@ -262,9 +277,9 @@ __device__ __forceinline__ void gemm_block(const AbxGemm& g, float* smem, int mt
                     sm += red[(kg2 * BM + r) * 2];
                     sq += red[(kg2 * BM + r) * 2 + 1];
                 }
-                const float mean = sm * invK;
-                st_lds[2 * r] = mean;
-                st_lds[2 * r + 1] = 1.0f / sqrtf(fmaxf(sq * invK - mean * mean, 0.f) + g.ln_eps);
+                const float dm = sm * invK;
+                st_lds[2 * r] = dm;                             // the operand was shifted: only (mean - shift) remains
+                st_lds[2 * r + 1] = 1.0f / sqrtf(fmaxf(sq * invK - dm * dm, 0.f) + g.ln_eps);
             }
             __syncthreads();
         }

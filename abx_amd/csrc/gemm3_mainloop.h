@@ -117,7 +117,11 @@ __device__ __forceinline__ void gemm3_mainloop(const AbxGemm& g, float* smem, in
         baseA = reinterpret_cast<const char*>(g.A + (long long)b * g.sAb + m0);
 #pragma unroll
         for (int i = 0; i < NLA; ++i) {
-            const int kl = (wave * NLA + i) * 2 + (lane >> 5), mq = lane & 31;     // LDS [k][BM]: 2 k-rows per instruction
+            // LDS [k][BM]: a k-row is BM / 4 lanes of 16 bytes, so one instruction (64 lanes) brings 256 / BM k-rows: 2 of the 128-row
+            // tile, 4 of the 64-row tile
+            constexpr int LPR = BM / 4, KPI = 64 / LPR, LPR_LOG = BM == 128 ? 5 : 4;
+            static_assert(LPR == 1 << LPR_LOG, "row-contiguous A: 128- or 64-row tiles");
+            const int kl = (wave * NLA + i) * KPI + (lane >> LPR_LOG), mq = lane & (LPR - 1);
             const int gm = min(m0 + mq * 4, g.M - 4) - m0;                         // (M % 4 == 0: checked by the dispatch)
             offsA[i] = (unsigned)(((long long)kl * g.sAk + gm) * 4);
         }

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import load_npz, tt
+from gemm_cases import _host_planes, _planes_to_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -112,27 +113,6 @@ def test_gemm_ln_gate_resid_rowscale(ops):
     check(o128, ref128, 2e-6, 'layernorm K=128 vector kernel')
     ops.layernorm(xv, g128.to(DEV), b128.to(DEV), out=xv)
     check(xv, ref128 - r128.double(), 2e-6, 'layernorm K=128 in place')
-
-
-def _host_planes(x, a_side):
-    """fp32 tensor (..., rows, K) -> int16 k-tiled f16 operand image (..., K/16, 2, rows, 16) of the plane x plane contraction
-    (include/abx_hip.h): A side x' = x / 16, (a0, (x' - a0) 2^11); B side x' = 16 x, (p0, x' - p0); RNE pieces."""
-    xs = x / 16 if a_side else x * 16
-    p0 = xs.half()
-    r = xs - p0.float()
-    p1 = (r * 2048).half() if a_side else r.half()
-    pl = torch.stack([p0.view(torch.int16), p1.view(torch.int16)], dim=-3)                            # (..., 2, rows, K)
-    rows, K = x.shape[-2:]
-    assert K % 16 == 0
-    pl = pl.reshape(*x.shape[:-2], 2, rows, K // 16, 16)
-    return pl.movedim(-2, -4).contiguous()                                                           # (..., K/16, 2, rows, 16)
-
-
-def _planes_to_f64(pl, a_side):
-    """value of an operand image: (..., K/16, 2, rows, 16) int16 -> float64 (..., rows, K)."""
-    h = pl.view(torch.float16).double()
-    f = (h.select(-3, 0) + h.select(-3, 1) / 2048) * 16 if a_side else (h.select(-3, 0) + h.select(-3, 1)) / 16   # (..., K/16, rows, 16)
-    return f.movedim(-3, -2).reshape(*f.shape[:-3], f.shape[-2], -1)
 
 
 def test_gemm_split_f16_weight_image(ops):

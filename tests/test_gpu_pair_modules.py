@@ -49,7 +49,9 @@ after abx_tri_mul_workspace_init (and without it when ceil4(L) % 16 == 0: what m
 bits, and a sample of the attention block does not depend on its batch.
 
 Out of scope: the exact-route triangle multiplication has no op-group entry point; the L = 56 and 72 network tests of
-tests/test_gpu_model.py cover it.  Range-contract cases exist per kernel; every input here stays inside the split range.
+tests/test_gpu_model.py cover it, and at the kernel level the m-contiguous LayerNorm cases of tests/test_gpu_gemm_cases.py do (family
+'x-ln': K = 128 rows of mean 0, 3 and 30 sigma on the exact fp32 kernels - the tail's own operand).  Range-contract cases exist per kernel;
+every input here stays inside the split range.
 Needs an MI355X: `pytest -m gpu`."""
 import pytest
 import torch
