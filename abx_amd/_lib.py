@@ -396,6 +396,25 @@ class AbxPatchArgs(C.Structure):
     ]
 
 
+TORSION_COLS = 25         # ABX_TORSION_COLS
+TORSION_MAX_LAB = 800     # ABX_TORSION_MAX_LAB
+_PAIR = C.c_double * 2    # a (cos, sin) pair
+
+
+class AbxTorsionArgs(C.Structure):
+    _fields_ = _STRUCTURE_FIELDS + [
+        ('region', c_f),
+        ('radius', c_f),
+        ('chain_id', c_f), ('residx', c_f),
+        ('chi_atoms', c_f), ('chi_pi', c_f),
+        ('cis', _PAIR), ('trans', _PAIR), ('o', _PAIR), ('a_mid', _PAIR), ('a_half', _PAIR), ('g_half', _PAIR), ('chi_tol', _PAIR),
+        ('out', c_f), ('out_stride', LL),
+        ('rows', c_f), ('classes', c_f),
+        ('gly', I), ('pro', I),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -477,6 +496,8 @@ _PROTOS = {
     'abx_shape_scores': (I, [C.POINTER(AbxShapeArgs), c_f, _S]),
     'abx_patch_scores_workspace_bytes': (LL, [I, I, I]),
     'abx_patch_scores': (I, [C.POINTER(AbxPatchArgs), c_f, _S]),
+    'abx_torsion_scores_workspace_bytes': (LL, [I, I]),
+    'abx_torsion_scores': (I, [C.POINTER(AbxTorsionArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

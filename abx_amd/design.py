@@ -44,6 +44,9 @@ salt bridges and unsatisfied polar atoms across the interface, <complex>_polar.t
 of the interface (Lawrence & Colman), both directions, the designed residues' share, gaps and dot counts, <complex>_shape.tsv.
 --patches: the patches of surface hydrophobicity and of charge around the CDRs of the free antibody (TAP's PSH / PPC / PNC), its charge
 symmetry and the charge pairing across the interface, <complex>_patches.tsv (--patches_rows: also <complex>_patches_rows.npy).
+--torsions: cis and twisted peptides, residues with phi >= 0, the ABEGO classes of the designed residues and the chi1 / chi1+2 recovery
+against the input structure, <complex>_torsions.tsv with the ABEGO string as its last column (--torsions_rows: also
+<complex>_torsions_rows.npy).
 --ensemble: the designs of a complex compared with each other, Daura clusters and their centres, <complex>_ensemble.tsv
 (--ensemble_matrix: also <complex>_ensemble_rmsd.npy).  No flag changes a file that another one writes; the _rows / _planes tables need
 the sample-sharded schedule (--shard_samples).
@@ -59,7 +62,7 @@ import torch
 
 from . import analyses, features, sampler, synthetic
 from .analyses import (_write_accuracy, _write_confidence, _write_designs, _write_ensemble, _write_interface, _write_polar,      # noqa: F401
-                       _write_relax, _write_trajectory_scores, _write_developability, _write_shape, _write_patches)                 # (the table writers, under the names the host tests call)
+                       _write_relax, _write_trajectory_scores, _write_developability, _write_shape, _write_patches, _write_torsions)                 # (the table writers, under the names the host tests call)
 from .config import default_config, load_config
 from .diffuser.full_diffuser import FullDiffuser
 from .io import TrajectoryWriter, index_to_str_seq
@@ -235,6 +238,15 @@ def build_parser():
     ap.add_argument('--patches_rows', action='store_true', help='--patches: also write <complex>_patches_rows.npy, (N, L, 4) float64 per '
                     'residue: its share of PSH, of PPC or PNC, of attract minus repel across the interface, and its flags (1 present, 2 exposed, '
                     '4 CDR seed, 8 vicinity, 16 salt-bridged, 32 region)')
+    ap.add_argument('--torsions', action='store_true', help='torsion analysis of every design on the GPU (abx_torsion_scores): cis and twisted '
+                    'peptides, residues other than Gly with phi >= 0, the ABEGO classes of the designed residues and their agreement with the input '
+                    'structure, the distance of phi / psi / omega to it, the chi1 and chi1+2 recovery, and their difference to the input complex; '
+                    'writes <complex>_torsions.tsv, whose last column is the ABEGO string of the designed residues')
+    ap.add_argument('--torsions_chi_tol', type=float, default=40.0, help='--torsions: largest |delta chi| of a recovered chi angle (degrees, in '
+                    '(0, 180])')
+    ap.add_argument('--torsions_rows', action='store_true', help='--torsions: also write <complex>_torsions_rows.npy, (N, Lab, 8) float64 per '
+                    'antibody residue: phi, psi, omega of the preceding link, chi1..chi4 in degrees (nan: undefined) and its flags (bits 0-2 the '
+                    'ABEGO code 1 A, 2 B, 3 G, 4 E, 5 O; 8 cis, 16 twisted, 32 phi >= 0 and not Gly, 64 region, 128 chi1 compared, 256 chi1 ok)')
     ap.add_argument('--ensemble', action='store_true', help='compare the designs of a complex with each other on the GPU (abx_ensemble_pairs, '
                     'abx_ensemble_cluster): pairwise RMSD of the designed residues, Daura clusters and their centres; writes <complex>_ensemble.tsv')
     ap.add_argument('--ensemble_cutoff', type=float, default=1.0, help='--ensemble: neighbour distance of the clusters (Angstrom)')

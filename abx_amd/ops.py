@@ -7,7 +7,7 @@ import os
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxShapeArgs, AbxPatchArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxShapeArgs, AbxPatchArgs, AbxTorsionArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1455,6 +1455,50 @@ def patch_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, cdr_def, t
     assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
         f'workspace: at least {need} uint8 on the device of atom14'
     check(lib.abx_patch_scores(C.byref(a), _p(workspace), _stream()), 'abx_patch_scores')
+    return out
+
+
+def torsion_workspace_bytes(B, Lab):
+    """Bytes of the workspace of torsion_scores (abx_torsion_scores_workspace_bytes)."""
+    return int(_lib.load().abx_torsion_scores_workspace_bytes(int(B), int(Lab)))
+
+
+def torsion_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, residx, tables, thresholds, Lab=None, region=None, mask=None,
+                   res_mask=None, gly=7, pro=14, out=None, rows=None, classes=None, workspace=None):
+    """Torsion analysis of B structures of one complex (abx_torsion_scores; columns: abx_amd.torsions.TORSIONS_COLUMNS): cis and twisted
+    peptides, phi >= 0, the ABEGO classes, the backbone dihedrals and the chi angles against the crystal structure.
+    atom14, seq, the complex, region, mask, res_mask as for accuracy_scores (only the rows < Lab are read); chain_id (L) and residx (L)
+    or None as for design_scores; tables = (chi_atoms (21,4,4) int32, chi_pi (21,4) uint8) on the device (abx_amd.torsions.chi_table);
+    thresholds: {name: (cos, sin)} of abx_amd.torsions.thresholds; gly / pro: the residue types of phi_pos / cis_nonpro.
+    out: (B, 25) float64 with unit column stride and any row stride, or None; rows (B,Lab,8) float64 and classes (B,Lab) int32:
+    contiguous tensors to receive the optional outputs, or None; workspace: a uint8 tensor of at least torsion_workspace_bytes(B, Lab)
+    bytes, or None (allocated here).  One launch, no synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = gt_seq.shape[-1]
+    chi_atoms, chi_pi = tables
+    assert chi_atoms.dtype == torch.int32 and tuple(chi_atoms.shape) == (21, 4, 4) and chi_pi.dtype == torch.uint8 and tuple(chi_pi.shape) == (21, 4) and \
+        all(t.is_contiguous() and t.device == dev for t in tables), 'tables: chi_atoms (21,4,4) int32, chi_pi (21,4) uint8 on the device of atom14'
+    a = AbxTorsionArgs()
+    B, _, Lab, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region,
+                                           extra=(chain_id,) + ((residx,) if residx is not None else ()))
+    a.chain_id = own(chain_id, torch.int32)
+    if residx is not None:
+        a.residx = own(residx, torch.int32)
+    a.chi_atoms, a.chi_pi = _p(chi_atoms), _p(chi_pi)
+    for name in ('cis', 'trans', 'o', 'a_mid', 'a_half', 'g_half', 'chi_tol'):
+        pair = getattr(a, name)
+        pair[0], pair[1] = float(thresholds[name][0]), float(thresholds[name][1])
+    a.gly, a.pro = int(gly), int(pro)
+    out = _out_rows(a, out, B, _lib.TORSION_COLS, dev)
+    _side_output(a, 'rows', rows, torch.float64, (B, Lab, 8))
+    _side_output(a, 'classes', classes, torch.int32, (B, Lab))
+    need = int(lib.abx_torsion_scores_workspace_bytes(B, Lab))
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
+        f'workspace: at least {need} uint8 on the device of atom14'
+    check(lib.abx_torsion_scores(C.byref(a), _p(workspace), _stream()), 'abx_torsion_scores')
     return out
 
 

@@ -25,7 +25,7 @@ def set_t_feats(feats, diffuser, t, ones):
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
               scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None, developability=None, shape=None,
-              patches=None):
+              patches=None, torsions=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -77,7 +77,12 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     gets 'patches' (B, len(patches.PATCHES_COLUMNS)) float64 - the patches of surface hydrophobicity and charge around the CDRs of the
     free antibody, its charge symmetry, the charge pairing across the interface - with a relaxer 'patches_relaxed', and with
     `patches.want_rows` 'patches_rows' (B, L, 4) float64 of the designs.  It shares the point counts of `interface` like `polar`,
-    `developability` and `shape`.  Three launches per table, outside any captured step, no host synchronisation."""
+    `developability` and `shape`.  Three launches per table, outside any captured step, no host synchronisation.
+    torsions: None (the records have exactly today's keys and bits), or an abx_amd.torsions.TorsionScorer of the complex: the LAST record
+    gets 'torsions' (B, len(torsions.TORSIONS_COLUMNS)) float64 - cis and twisted peptides, phi >= 0, the ABEGO classes, the backbone
+    dihedrals and the chi angles against the crystal structure - and 'torsions_classes' (B, Lab) int32, the ABEGO codes; with a relaxer
+    'torsions_relaxed', and with `torsions.want_rows` 'torsions_rows' (B, Lab, 8) float64 of the designs.  One launch per table, outside
+    any captured step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -148,7 +153,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 if scorer is not None:
                     traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
                 if k == len(steps) - 1:
-                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability, shape, patches)
+                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability, shape, patches, torsions)
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)
@@ -170,7 +175,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     return traj
 
 
-def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None, shape=None, patches=None):
+def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None, shape=None, patches=None, torsions=None):
     """What the analyses of sample_fn add to the LAST record, from the model's output `out` of the call that made it and its per-residue
     pLDDT, each on the design and, with a relaxer, on the relaxed structure.  Launches only, no host synchronisation."""
     x, seq, B = rec['atom14_results'], rec['seq'], rec['seq'].shape[0]
@@ -214,6 +219,13 @@ def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accu
         rec['patches'] = patches.score(x, seq, points=pts if shared else None, rows=rec.get('patches_rows'))
         if relaxer is not None:
             rec['patches_relaxed'] = patches.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
+    if torsions is not None:
+        if torsions.want_rows:
+            rec['torsions_rows'] = torsions.new_rows(B)
+        rec['torsions_classes'] = torsions.new_classes(B)
+        rec['torsions'] = torsions.score(x, seq, rows=rec.get('torsions_rows'), classes=rec['torsions_classes'])
+        if relaxer is not None:
+            rec['torsions_relaxed'] = torsions.score(rec['atom14_relaxed'], seq)
     if confidence is not None:
         pair = out['representations']['pair']                   # of the call just made: nothing between it and here runs the network
         got = confidence.score(pair, x, seq, planes=bool(confidence.want_planes))

@@ -1247,6 +1247,80 @@ long long abx_patch_scores_workspace_bytes(int B, int L, int Lab);
 int abx_patch_scores(const AbxPatchArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Torsion analysis of designs: the backbone dihedrals between the residues (phi, psi, omega - cis and twisted peptides, phi >= 0, the
+ * ABEGO class) and the chi angles against the crystal structure (chi1 / chi1+2 recovery).  No upstream file:line: the reference has no
+ * such analysis (its torsions exist as network features only, abx/model/atom.py); the definitions are the ones written here.  One row
+ * of ABX_TORSION_COLS float64 values per structure of a batch of B designs of ONE complex (abx_amd.torsions.TORSIONS_COLUMNS).  No
+ * Ramachandran probability surface, no hydrogens, no chirality check; the chi of a mutated residue is not compared.
+ * The design and the complex are given as for abx_accuracy_scores (pred_* rows < Lpred, Lab <= Lpred <= L, residue types of rows < Lab
+ * from pred_seq, clamped to 0..20; pred_mask (B,L,14) NULL: a row has the atoms of its residue type, `radius` [21][14] > 0; res_mask = 0
+ * removes a row from both structures).  Only the rows < Lab are read: the antigen is not.  The wild type is gt_atom14 / gt_exists /
+ * gt_seq.  chain_id (L); residx (L) optional.  region: (L) bytes, optional (NULL: no row is a region row).
+ * LINK (i-1, i), 1 <= i < Lab: chain_id equal, residx consecutive when given (the rule of abx_design_scores), and N, CA, C present in
+ * both rows.  Distance is not asked: a broken bond still has an omega.
+ * DIHEDRAL of a, b, c, d, float64 from the float32 coordinates, no operation fused, sums as bracketed:
+ *   b1 = b - a, b2 = c - b, b3 = d - c;  n1 = b1 x b2, n2 = b2 x b3  (n_x = u_y*v_z - u_z*v_y, ...);
+ *   x = (n1x*n2x + n1y*n2y) + n1z*n2z;  y = sqrt((b2x*b2x + b2y*b2y) + b2z*b2z) * ((b1x*n2x + b1y*n2y) + b1z*n2z);
+ *   r = sqrt(x*x + y*y);  angle = atan2(y, x) in degrees (reported only: no decision reads it).
+ *   omega_i = (CA, C of i-1; N, CA of i) and phi_i = (C of i-1; N, CA, C of i) with link (i-1, i); psi_i = (N, CA, C of i; N of i+1)
+ *   with link (i, i+1); chi_k of a row: the four atom14 slots chi_atoms[type][k] (< 0: the type has no chi_k), all present.
+ * DECISIONS, on (x, y, r) and the (cos, sin) pairs of the caller (computed once on the host, so that a twin uses the same bits):
+ *   negative(angle):      y < 0
+ *   wider(angle, h):      x <= h[0] * r                                    |angle| >= h
+ *   within(angle, m, h):  x*m[0] + y*m[1] >= h[0] * r                      |angle - m| <= h
+ *   cis = !wider(omega, cis);  twisted = wider(omega, cis) && !wider(omega, trans);  phi_pos = !negative(phi) and the type is not gly.
+ *   ABEGO code of a row with phi, psi and omega: 5 (O) if !wider(omega, o); else 1 (A) if negative(phi) and within(psi, a_mid, a_half);
+ *   else 2 (B) if negative(phi); else 3 (G) if x_psi >= g_half[0] * r_psi (|psi| <= 100); else 4 (E).  0: undefined.  (An interval
+ *   is closed at both ends here; the half-open statement differs on a set of measure zero, which a twin counts as borderline.)
+ *   The shipped pairs: cis 30, trans 150, o 90, a_mid -12.5, a_half 62.5, g_half 100 degrees, chi_tol 40 (abx_amd.torsions.thresholds).
+ * DIFFERENCE of an angle of the design (x, y) and of the wild type (u, v):  c = x*u + y*v;  s = y*u - x*v;  for a chi with
+ *   chi_pi[type][k] != 0 (a symmetric end: Asp chi2, Glu chi3, Phe / Tyr chi2) c = fabs(c);  |delta| = atan2(fabs(s), c) in degrees;
+ *   ok = c >= chi_tol[0] * sqrt(c*c + s*s).
+ * A chi is COMPARED in a region row whose two tokens are equal when it is defined in both structures.
+ *   0 n_links          links of the design                   13 abego_O
+ *   1 cis              2 cis_nonpro (row i is not pro)       14 n_abego         region rows with a code in both structures
+ *   3 twisted                                                15 abego_same      ... and the same code
+ *   4 n_links_region   links with region[i-1] | region[i]    16 dphi_region     mean |delta phi| over the region rows with phi in both
+ *   5 cis_region       6 twisted_region                      17 dpsi_region     18 domega_region     likewise
+ *   7 phi_pos          8 phi_pos_region (region[i])          19 dbb_max_region  the largest |delta phi| or |delta psi| of 16, 17
+ *   9 abego_A  10 abego_B  11 abego_G  12 abego_E            20 n_chi1  21 chi1_ok   rows with chi1 compared / ok
+ *     (9-13: the region rows of the design by code)          22 n_chi12 23 chi12_ok  rows with chi1 and chi2 compared / both ok
+ *                                                            24 chi_mae_region  mean |delta chi| over all compared chi
+ *   16-19 and 24 are NaN where nothing is comparable.
+ * rows: optional (B, Lab, 8) doubles: phi, psi, omega of the preceding link, chi1..chi4 in degrees (NaN: undefined) and the flag word
+ * code | 8 cis | 16 twisted | 32 phi_pos | 64 region | 128 chi1 compared | 256 chi1 ok.  classes: optional (B, Lab) int32, the codes.
+ * out / out_stride as in AbxDesignScoreArgs (out_stride >= ABX_TORSION_COLS).
+ * One launch, one workgroup of 256 per structure, one lane per row (strided): N, CA, C of the wild type are staged as float64 in LDS
+ * (72 Lab bytes, dynamic) and every row's seven (x, y) pairs and code go to the workspace (16 doubles a row, written and read back by
+ * the same lane); then the design is staged the same way and measured against them.  Integer LDS counters, the four float sums in a
+ * fixed order, the maximum as an integer LDS maximum of the bit pattern: a structure's row depends on nothing but its own inputs.
+ * Lab <= ABX_TORSION_MAX_LAB (the LDS image stays below 64 KiB); more is an argument error.  No allocation, no synchronisation.  The
+ * caller allocates the workspace (abx_torsion_scores_workspace_bytes). */
+#define ABX_TORSION_COLS 25
+#define ABX_TORSION_MAX_LAB 800
+typedef struct AbxTorsionArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const unsigned char* region;                    /* optional (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs (> 0: the type has the slot) */
+    const int* chain_id;                            /* (L) */
+    const int* residx;                              /* optional (L) */
+    const int* chi_atoms;                           /* [21][4][4] atom14 slots of chi_k of a residue type, < 0: no such chi */
+    const unsigned char* chi_pi;                    /* [21][4] != 0: chi_k is compared modulo 180 degrees */
+    double cis[2], trans[2], o[2], a_mid[2], a_half[2], g_half[2], chi_tol[2];      /* (cos, sin) of the thresholds */
+    double* out; long long out_stride;
+    double* rows;                                   /* optional (B,Lab,8) */
+    int* classes;                                   /* optional (B,Lab) */
+    int gly, pro;                                   /* the residue types of phi_pos and cis_nonpro */
+    int B, L, Lab;
+} AbxTorsionArgs;
+long long abx_torsion_scores_workspace_bytes(int B, int Lab);
+int abx_torsion_scores(const AbxTorsionArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
