@@ -415,6 +415,23 @@ class AbxTorsionArgs(C.Structure):
     ]
 
 
+SECONDARY_COLS = 22       # ABX_SECONDARY_COLS
+SECONDARY_MAX_LAB = 800   # ABX_SECONDARY_MAX_LAB
+
+
+class AbxSecondaryArgs(C.Structure):
+    _fields_ = _STRUCTURE_FIELDS + [
+        ('region', c_f),
+        ('radius', c_f),
+        ('chain_id', c_f), ('residx', c_f),
+        ('hb_energy', C.c_double), ('bend', _PAIR),
+        ('out', c_f), ('out_stride', LL),
+        ('rows', c_f), ('classes', c_f),
+        ('pro', I),
+        ('B', I), ('L', I), ('Lab', I),
+    ]
+
+
 _S = c_f   # hipStream_t
 
 _PROTOS = {
@@ -498,6 +515,8 @@ _PROTOS = {
     'abx_patch_scores': (I, [C.POINTER(AbxPatchArgs), c_f, _S]),
     'abx_torsion_scores_workspace_bytes': (LL, [I, I]),
     'abx_torsion_scores': (I, [C.POINTER(AbxTorsionArgs), c_f, _S]),
+    'abx_secondary_scores_workspace_bytes': (LL, [I, I]),
+    'abx_secondary_scores': (I, [C.POINTER(AbxSecondaryArgs), c_f, _S]),
     'abx_pack_linear_bytes': (LL, [I, I]),
     'abx_pack_linear': (I, [C.POINTER(AbxLinearSrc), I, I, c_f, c_f, I, c_f, C.POINTER(AbxLinearPack), _S]),
     'abx_transition_workspace_bytes': (LL, [LL, I, I]),

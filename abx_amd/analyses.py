@@ -11,7 +11,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import accuracy, confidence, developability, ensemble, interface, metrics, patches, polar, relax, shape, torsions
+from . import accuracy, confidence, developability, ensemble, interface, metrics, patches, polar, relax, secondary, shape, torsions
 from .io import index_to_str_seq
 
 F64 = torch.float64
@@ -341,28 +341,65 @@ PATCHES = _wild_table('patches', patches.PATCHES_COLUMNS, _write_patches, _patch
                       Extra('patches_rows', Field('patches_rows', F64, ('L', 4), False), lambda last: last['patches_rows'], lambda t: t.cpu().numpy()))
 
 
-# --torsions: cis and twisted peptides, phi >= 0, the ABEGO classes and the chi recovery of the designs.  A wild table like the others
-# with one text column more, `abego`: the ABEGO string of the designed residues.  Declared directly, not through _wild_table: beside its
-# row the analysis gathers 'torsions_abego' (n, 3, Lab) int32 - the codes of the design, those of the wild type and the region mask, so
-# that any rank can write the column on both schedules (it travels in the rows like `seq`) - and --torsions_rows is its Extra.
+# A wild table like the others with one text column more: the class string of the designed residues (--torsions: `abego`, --secondary:
+# `dssp`).  Declared directly, not through _wild_table: beside its row such an analysis gathers a second field (n, 3, Lab) int32 - the
+# codes of the design, those of the wild type and the region mask, so that any rank can write the column on both schedules (it travels
+# in the rows like `seq`) - and its per-residue table is its Extra.
+def _write_wild_text(kind, columns, delta_columns, fmt, fmt_delta, text, out_dir, cname, wild, rows, relaxed, strings=None):
+    """<out_dir>/<complex>_<kind>.tsv: the `wild` line, then (sample id, values) per sample; values = the `columns` row and, when relaxed,
+    the row of the relaxed structure.  After the columns: delta_<column> = row minus wild for delta_columns, the _relaxed columns, and
+    last the column `text`: strings = (the wild type's string, [the string of every sample]); None: '-'."""
+    N = len(columns)
+    wild_s, row_s = strings if strings is not None else ('-', ['-'] * len(rows))
+    tsv = os.path.join(out_dir, f'{cname}_{kind}.tsv')
+    with open(tsv, 'w') as f:
+        f.write('sample\t' + '\t'.join(columns + tuple('delta_' + c for c in delta_columns) +
+                                       (tuple(c + '_relaxed' for c in columns) if relaxed else ()) + (text,)) + '\n')
+        f.write('wild\t' + '\t'.join(fmt(wild) + fmt_delta(wild, wild) + (['nan'] * N if relaxed else []) + [wild_s]) + '\n')
+        for (i, v), st in zip(rows, row_s):
+            f.write(f'{i}\t' + '\t'.join(fmt(v[:N]) + fmt_delta(v[:N], wild) + (fmt(v[N:2 * N]) if relaxed else []) + [st]) + '\n')
+    return tsv
+
+
+def _wild_text_table(kind, columns, writer, build, text_field, string, checks, extra):
+    """The Analysis of a wild table with a text column: the sampler's records carry <kind>, <kind>_classes, <kind>_relaxed and
+    <extra.option>; text_field: the name of the gathered (n, 3, Lab) int32 field; string(classes, region) -> the text of a line."""
+    N = len(columns)
+
+    def fields(a):
+        return [Field(kind, F64, (N * (3 if a.relax else 2),), True), Field(text_field, torch.int32, (3, 'Lab'), True)] + \
+            ([extra.field] if getattr(a, extra.option) else [])
+
+    def collect(a, traj, scorers):
+        last, sc = traj[-1], scorers[kind]
+        n = last['seq'].shape[0]
+        wild_classes = sc.new_classes(1)
+        wild = sc.wild(classes=wild_classes)
+        out = {kind: torch.cat([last[kind]] + ([last[kind + '_relaxed']] if a.relax else []) + [wild.expand(n, -1)], 1),
+               text_field: torch.stack([last[kind + '_classes'], wild_classes.expand(n, -1), sc.region[None, :sc.Lab].to(torch.int32).expand(n, -1)], 1)}
+        if getattr(a, extra.option):
+            out[extra.option] = extra.of_record(last)
+        return out
+
+    def write(a, out_dir, cname, ids, F, scorer):
+        t, ab = F[kind].tolist(), F[text_field].cpu().numpy()
+        strings = (string(ab[0, 1], ab[0, 2]), [string(r[0], r[2]) for r in ab])
+        files = [writer(out_dir, cname, t[0][-N:], list(zip(ids, t)), a.relax, strings)]
+        if getattr(a, extra.option):
+            files.append(_save(out_dir, cname, extra.option, extra.to_array(F[extra.option])))
+        return files
+
+    return Analysis(kind, kind, build, fields, collect, write, checks, extra.option)
+
+
+# --torsions: cis and twisted peptides, phi >= 0, the ABEGO classes and the chi recovery of the designs; the text column is `abego`.
 TORSIONS_ROWS = Extra('torsions_rows', Field('torsions_rows', F64, ('Lab', 8), False), lambda last: last['torsions_rows'], lambda t: t.cpu().numpy())
 
 
 def _write_torsions(out_dir, cname, wild, rows, relaxed, strings=None):
-    """<out_dir>/<complex>_torsions.tsv: the `wild` line, then (sample id, values) per sample; values = the torsions.TORSIONS_COLUMNS row
-    and, when relaxed, the row of the relaxed structure.  After the columns: delta_<column> = row minus wild for torsions.DELTA_COLUMNS,
-    the _relaxed columns, and last `abego`: strings = (the wild type's ABEGO string, [the string of every sample]); None: '-'."""
-    columns, fmt = torsions.TORSIONS_COLUMNS, torsions.format_torsions
-    N = len(columns)
-    wild_s, row_s = strings if strings is not None else ('-', ['-'] * len(rows))
-    tsv = os.path.join(out_dir, f'{cname}_torsions.tsv')
-    with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(columns + tuple('delta_' + c for c in torsions.DELTA_COLUMNS) +
-                                       (tuple(c + '_relaxed' for c in columns) if relaxed else ()) + ('abego',)) + '\n')
-        f.write('wild\t' + '\t'.join(fmt(wild) + torsions.format_delta(wild, wild) + (['nan'] * N if relaxed else []) + [wild_s]) + '\n')
-        for (i, v), st in zip(rows, row_s):
-            f.write(f'{i}\t' + '\t'.join(fmt(v[:N]) + torsions.format_delta(v[:N], wild) + (fmt(v[N:2 * N]) if relaxed else []) + [st]) + '\n')
-    return tsv
+    """<out_dir>/<complex>_torsions.tsv (_write_wild_text): torsions.TORSIONS_COLUMNS, delta_* for torsions.DELTA_COLUMNS, last `abego`."""
+    return _write_wild_text('torsions', torsions.TORSIONS_COLUMNS, torsions.DELTA_COLUMNS, torsions.format_torsions, torsions.format_delta, 'abego',
+                            out_dir, cname, wild, rows, relaxed, strings)
 
 
 def _torsions_build(batch, a, model, cfg, scorers):
@@ -371,40 +408,35 @@ def _torsions_build(batch, a, model, cfg, scorers):
     return tor
 
 
-def _torsions_fields(a):
-    return [Field('torsions', F64, (len(torsions.TORSIONS_COLUMNS) * (3 if a.relax else 2),), True),
-            Field('torsions_abego', torch.int32, (3, 'Lab'), True)] + ([TORSIONS_ROWS.field] if a.torsions_rows else [])
+TORSIONS = _wild_text_table('torsions', torsions.TORSIONS_COLUMNS, _write_torsions, _torsions_build, 'torsions_abego', torsions.abego_string,
+                            [(lambda a: not 0.0 < a.torsions_chi_tol <= 180.0, '--torsions_chi_tol must be in (0, 180] degrees')], TORSIONS_ROWS)
+
+# --secondary: DSSP's backbone hydrogen bonds, bridges and states of the antibody against the crystal structure; the text column is
+# `dssp`, the state string of the designed residues.
+SECONDARY_ROWS = Extra('secondary_rows', Field('secondary_rows', torch.int32, ('Lab', 6), False), lambda last: last['secondary_rows'],
+                       lambda t: t.cpu().numpy())
 
 
-def _torsions_collect(a, traj, scorers):
-    last, sc = traj[-1], scorers['torsions']
-    n = last['seq'].shape[0]
-    wild_classes = sc.new_classes(1)
-    wild = sc.wild(classes=wild_classes)
-    out = {'torsions': torch.cat([last['torsions']] + ([last['torsions_relaxed']] if a.relax else []) + [wild.expand(n, -1)], 1),
-           'torsions_abego': torch.stack([last['torsions_classes'], wild_classes.expand(n, -1), sc.region[None, :sc.Lab].to(torch.int32).expand(n, -1)], 1)}
-    if a.torsions_rows:
-        out['torsions_rows'] = TORSIONS_ROWS.of_record(last)
-    return out
+def _write_secondary(out_dir, cname, wild, rows, relaxed, strings=None):
+    """<out_dir>/<complex>_secondary.tsv (_write_wild_text): secondary.SECONDARY_COLUMNS, delta_* for secondary.DELTA_COLUMNS, last `dssp`."""
+    return _write_wild_text('secondary', secondary.SECONDARY_COLUMNS, secondary.DELTA_COLUMNS, secondary.format_secondary, secondary.format_delta,
+                            'dssp', out_dir, cname, wild, rows, relaxed, strings)
 
 
-def _torsions_write(a, out_dir, cname, ids, F, scorer):
-    N = len(torsions.TORSIONS_COLUMNS)
-    t, ab = F['torsions'].tolist(), F['torsions_abego'].cpu().numpy()
-    strings = (torsions.abego_string(ab[0, 1], ab[0, 2]), [torsions.abego_string(r[0], r[2]) for r in ab])
-    files = [_write_torsions(out_dir, cname, t[0][-N:], list(zip(ids, t)), a.relax, strings)]
-    if a.torsions_rows:
-        files.append(_save(out_dir, cname, 'torsions_rows', TORSIONS_ROWS.to_array(F['torsions_rows'])))
-    return files
+def _secondary_build(batch, a, model, cfg, scorers):
+    sec = secondary.SecondaryScorer(batch, hb_energy=a.secondary_hb_energy)
+    sec.want_rows = a.secondary_rows
+    return sec
 
 
-TORSIONS = Analysis('torsions', 'torsions', _torsions_build, _torsions_fields, _torsions_collect, _torsions_write,
-                    [(lambda a: not 0.0 < a.torsions_chi_tol <= 180.0, '--torsions_chi_tol must be in (0, 180] degrees')], 'torsions_rows')
+SECONDARY = _wild_text_table('secondary', secondary.SECONDARY_COLUMNS, _write_secondary, _secondary_build, 'secondary_ss', secondary.ss_string,
+                             [(lambda a: not (math.isfinite(a.secondary_hb_energy) and a.secondary_hb_energy < 0.0),
+                               '--secondary_hb_energy must be a finite energy below 0 kcal/mol')], SECONDARY_ROWS)
 
 # The analyses added since LATER was pinned, walked after the three tuples before it.  The NEXT analysis is appended HERE: a test asserts
 # that its own flag is in FURTHER and that ANALYSES, EXTENSIONS and LATER come first, never the contents of FURTHER, so no fifth tuple
 # is needed.
-FURTHER = (PATCHES, TORSIONS)
+FURTHER = (PATCHES, TORSIONS, SECONDARY)
 
 
 def check_options(a, set_level):

@@ -47,6 +47,9 @@ symmetry and the charge pairing across the interface, <complex>_patches.tsv (--p
 --torsions: cis and twisted peptides, residues with phi >= 0, the ABEGO classes of the designed residues and the chi1 / chi1+2 recovery
 against the input structure, <complex>_torsions.tsv with the ABEGO string as its last column (--torsions_rows: also
 <complex>_torsions_rows.npy).
+--secondary: DSSP over the antibody - backbone hydrogen bonds on a virtual H, bridges and the eight states of the designed residues
+against the input structure, <complex>_secondary.tsv with the state string as its last column (--secondary_rows: also
+<complex>_secondary_rows.npy).
 --ensemble: the designs of a complex compared with each other, Daura clusters and their centres, <complex>_ensemble.tsv
 (--ensemble_matrix: also <complex>_ensemble_rmsd.npy).  No flag changes a file that another one writes; the _rows / _planes tables need
 the sample-sharded schedule (--shard_samples).
@@ -62,7 +65,7 @@ import torch
 
 from . import analyses, features, sampler, synthetic
 from .analyses import (_write_accuracy, _write_confidence, _write_designs, _write_ensemble, _write_interface, _write_polar,      # noqa: F401
-                       _write_relax, _write_trajectory_scores, _write_developability, _write_shape, _write_patches, _write_torsions)                 # (the table writers, under the names the host tests call)
+                       _write_relax, _write_trajectory_scores, _write_developability, _write_shape, _write_patches, _write_torsions, _write_secondary)                 # (the table writers, under the names the host tests call)
 from .config import default_config, load_config
 from .diffuser.full_diffuser import FullDiffuser
 from .io import TrajectoryWriter, index_to_str_seq
@@ -247,6 +250,17 @@ def build_parser():
     ap.add_argument('--torsions_rows', action='store_true', help='--torsions: also write <complex>_torsions_rows.npy, (N, Lab, 8) float64 per '
                     'antibody residue: phi, psi, omega of the preceding link, chi1..chi4 in degrees (nan: undefined) and its flags (bits 0-2 the '
                     'ABEGO code 1 A, 2 B, 3 G, 4 E, 5 O; 8 cis, 16 twisted, 32 phi >= 0 and not Gly, 64 region, 128 chi1 compared, 256 chi1 ok)')
+    ap.add_argument('--secondary', action='store_true', help='secondary structure of every design on the GPU (abx_secondary_scores): DSSP over '
+                    'the antibody - backbone hydrogen bonds on a virtual H, in total, touching and inside the designed residues and kept from the input '
+                    'structure, their energy, bridge pairs, the eight states of the designed residues and their agreement with the input structure '
+                    '(Q8, Q3), and their difference to the input complex; writes <complex>_secondary.tsv, whose last column is the state string of '
+                    'the designed residues (H G I helices, E strand, B bridge, T turn, S bend, - coil)')
+    ap.add_argument('--secondary_hb_energy', type=float, default=-0.5, help='--secondary: a backbone hydrogen bond has an energy below this '
+                    '(kcal/mol, < 0)')
+    ap.add_argument('--secondary_rows', action='store_true', help='--secondary: also write <complex>_secondary_rows.npy, (N, Lab, 6) int32 per '
+                    'antibody residue: its state (0 absent, 1 H, 2 G, 3 I, 4 E, 5 B, 6 T, 7 S, 8 coil), bonds donated, bonds accepted, its two lowest '
+                    'bridge partner rows (-1: none) and its flags (1 region, 2 present, 4 has H, 8 parallel bridge, 16 antiparallel bridge, 32 bend, '
+                    '64 / 128 / 256 a 3- / 4- / 5-turn starts here)')
     ap.add_argument('--ensemble', action='store_true', help='compare the designs of a complex with each other on the GPU (abx_ensemble_pairs, '
                     'abx_ensemble_cluster): pairwise RMSD of the designed residues, Daura clusters and their centres; writes <complex>_ensemble.tsv')
     ap.add_argument('--ensemble_cutoff', type=float, default=1.0, help='--ensemble: neighbour distance of the clusters (Angstrom)')

@@ -7,7 +7,7 @@ import os
 import torch
 
 from abx_amd import _lib
-from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxShapeArgs, AbxPatchArgs, AbxTorsionArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
+from abx_amd._lib import (AbxGemm, AbxTriAttn, AbxIpaTail, AbxHeadsTail, AbxScoreArgs, AbxReverseArgs, AbxGuidanceArgs, AbxContactArgs, AbxDesignScoreArgs, AbxRelaxArgs, AbxInterfaceArgs, AbxPolarArgs, AbxDevelopabilityArgs, AbxShapeArgs, AbxPatchArgs, AbxTorsionArgs, AbxSecondaryArgs, AbxDistogramArgs, AbxAccuracyArgs, AbxEnsemblePairsArgs, AbxEnsembleClusterArgs, AbxLinearPack, AbxLinearSrc,
                            AbxTriMulPack, AbxTriAttnPack, AbxTriRowPack, check)
 
 
@@ -1499,6 +1499,45 @@ def torsion_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, residx, 
     assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
         f'workspace: at least {need} uint8 on the device of atom14'
     check(lib.abx_torsion_scores(C.byref(a), _p(workspace), _stream()), 'abx_torsion_scores')
+    return out
+
+
+def secondary_workspace_bytes(B, Lab):
+    """Bytes of the workspace of secondary_scores (abx_secondary_scores_workspace_bytes)."""
+    return int(_lib.load().abx_secondary_scores_workspace_bytes(int(B), int(Lab)))
+
+
+def secondary_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, residx, thresholds, Lab=None, region=None, mask=None, res_mask=None,
+                     pro=14, out=None, rows=None, classes=None, workspace=None):
+    """Secondary structure of B structures of one complex (abx_secondary_scores; columns: abx_amd.secondary.SECONDARY_COLUMNS): DSSP's
+    backbone hydrogen bonds on a virtual H, turns, helices, bridges, ladders and bends over the antibody rows, against the crystal structure.
+    atom14, seq, the complex, region, mask, res_mask as for accuracy_scores (only the rows < Lab are read); chain_id (L) and residx (L)
+    or None as for design_scores; thresholds: dict(hb_energy, bend = (cos, sin)) of abx_amd.secondary.thresholds; pro: the residue type
+    without an H.
+    out: (B, 22) float64 with unit column stride and any row stride, or None; rows (B,Lab,6) int32 and classes (B,Lab) int32: contiguous
+    tensors to receive the optional outputs, or None; workspace: a uint8 tensor of at least secondary_workspace_bytes(B, Lab) bytes, or
+    None (allocated here).  One launch, no synchronisation."""
+    lib = _lib.load()
+    dev = atom14.device
+    L = gt_seq.shape[-1]
+    a = AbxSecondaryArgs()
+    B, _, Lab, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region,
+                                           extra=(chain_id,) + ((residx,) if residx is not None else ()))
+    a.chain_id = own(chain_id, torch.int32)
+    if residx is not None:
+        a.residx = own(residx, torch.int32)
+    a.hb_energy = float(thresholds['hb_energy'])
+    a.bend[0], a.bend[1] = float(thresholds['bend'][0]), float(thresholds['bend'][1])
+    a.pro = int(pro)
+    out = _out_rows(a, out, B, _lib.SECONDARY_COLS, dev)
+    _side_output(a, 'rows', rows, torch.int32, (B, Lab, 6))
+    _side_output(a, 'classes', classes, torch.int32, (B, Lab))
+    need = int(lib.abx_secondary_scores_workspace_bytes(B, Lab))
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
+        f'workspace: at least {need} uint8 on the device of atom14'
+    check(lib.abx_secondary_scores(C.byref(a), _p(workspace), _stream()), 'abx_secondary_scores')
     return out
 
 

@@ -25,7 +25,7 @@ def set_t_feats(feats, diffuser, t, ones):
 def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_t=0.01, center=True, self_condition=True,
               noise_scale=1.0, eps=1e-8, noise_fn=None, sample_ids=None, on_step=None, on_record=None, guidance=None, use_graph=False,
               scorer=None, relaxer=None, interface=None, confidence=None, accuracy=None, polar=None, constraints=None, developability=None, shape=None,
-              patches=None, torsions=None):
+              patches=None, torsions=None, secondary=None):
     """Returns the trajectory: list of dicts {seq (B,Lab) i64, atom14_results (B,Lab,14,3), pLDDT (B,Lab), time,
     rigids_t, seq_t}; only the last element unless mode == 'trajectory'.  All tensors stay on the device.
     on_record(rec): called for every element that enters the trajectory, e.g. `abx_amd.io.TrajectoryWriter.submit` to dump the
@@ -82,7 +82,12 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     gets 'torsions' (B, len(torsions.TORSIONS_COLUMNS)) float64 - cis and twisted peptides, phi >= 0, the ABEGO classes, the backbone
     dihedrals and the chi angles against the crystal structure - and 'torsions_classes' (B, Lab) int32, the ABEGO codes; with a relaxer
     'torsions_relaxed', and with `torsions.want_rows` 'torsions_rows' (B, Lab, 8) float64 of the designs.  One launch per table, outside
-    any captured step, no host synchronisation."""
+    any captured step, no host synchronisation.
+    secondary: None (the records have exactly today's keys and bits), or an abx_amd.secondary.SecondaryScorer of the complex: the LAST
+    record gets 'secondary' (B, len(secondary.SECONDARY_COLUMNS)) float64 - DSSP's backbone hydrogen bonds, bridges and states of the
+    antibody against the crystal structure - and 'secondary_classes' (B, Lab) int32, the states; with a relaxer 'secondary_relaxed',
+    and with `secondary.want_rows` 'secondary_rows' (B, Lab, 6) int32 of the designs.  One launch per table, outside any captured
+    step, no host synchronisation."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -153,7 +158,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 if scorer is not None:
                     traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
                 if k == len(steps) - 1:
-                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability, shape, patches, torsions)
+                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability, shape, patches, torsions, secondary)
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)
@@ -175,7 +180,8 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     return traj
 
 
-def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None, shape=None, patches=None, torsions=None):
+def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None, shape=None, patches=None, torsions=None,
+                  secondary=None):
     """What the analyses of sample_fn add to the LAST record, from the model's output `out` of the call that made it and its per-residue
     pLDDT, each on the design and, with a relaxer, on the relaxed structure.  Launches only, no host synchronisation."""
     x, seq, B = rec['atom14_results'], rec['seq'], rec['seq'].shape[0]
@@ -226,6 +232,13 @@ def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accu
         rec['torsions'] = torsions.score(x, seq, rows=rec.get('torsions_rows'), classes=rec['torsions_classes'])
         if relaxer is not None:
             rec['torsions_relaxed'] = torsions.score(rec['atom14_relaxed'], seq)
+    if secondary is not None:
+        if secondary.want_rows:
+            rec['secondary_rows'] = secondary.new_rows(B)
+        rec['secondary_classes'] = secondary.new_classes(B)
+        rec['secondary'] = secondary.score(x, seq, rows=rec.get('secondary_rows'), classes=rec['secondary_classes'])
+        if relaxer is not None:
+            rec['secondary_relaxed'] = secondary.score(rec['atom14_relaxed'], seq)
     if confidence is not None:
         pair = out['representations']['pair']                   # of the call just made: nothing between it and here runs the network
         got = confidence.score(pair, x, seq, planes=bool(confidence.want_planes))

@@ -1321,6 +1321,87 @@ long long abx_torsion_scores_workspace_bytes(int B, int Lab);
 int abx_torsion_scores(const AbxTorsionArgs* a, void* workspace, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Secondary structure of designs: DSSP (Kabsch & Sander 1983) over the antibody rows - the electrostatic N-H...O=C energy between every
+ * pair of residues on a virtual hydrogen, and from the bonds turns, helices, bridges, ladders and bends - against the crystal structure.
+ * No upstream file:line: the reference has no such analysis (its evaluation is RMSD, AAR, cal_vio.py and PyRosetta); the definitions
+ * are the ones written here.  One row of ABX_SECONDARY_COLS float64 values per structure of a batch of B designs of ONE complex
+ * (abx_amd.secondary.SECONDARY_COLUMNS).  Declared limits: ALL bonds below the threshold are kept (mkdssp keeps the two best per
+ * residue), no beta-bulge merging of ladders, no sheet labels, no kappa / alpha / phi / psi columns, I has the classic priority below G,
+ * the antigen is not read, and the criterion is DSSP's electrostatic one, not the heavy-atom rule of abx_polar_scores.
+ * The design and the complex are given as for abx_torsion_scores (pred_*, gt_*, res_mask, region, radius, chain_id, optional residx);
+ * only the rows i < Lab are read.  All arithmetic is float64 from the float32 coordinates, no operation fused, sums as bracketed, sqrt
+ * and / the IEEE ones.
+ * PRESENT(i): N, CA, C and O (atom14 slots 0..3) of the row exist, and res_mask keeps it.
+ * LINK (i-1, i), 1 <= i < Lab: chain_id equal, residx consecutive when given, both rows present.  CONT(i, j), i <= j: every link from
+ *   i+1 to j holds.
+ * DIST(a, b) = sqrt((dx*dx + dy*dy) + dz*dz), d = a - b.
+ * H of row i: needs link (i-1, i) and a type other than `pro`;  v = C(i-1) - O(i-1);  n = sqrt((vx*vx + vy*vy) + vz*vz);
+ *   H = N(i) + v / n component by component;  n == 0: the row has no H.
+ * ENERGY of donor i (with an H) and acceptor j (present), j != i, and not j == i-1 with link (i-1, i):
+ *   needs ((dx*dx + dy*dy) + dz*dz) < 81.0, d = CA_i - CA_j;
+ *   e = 27.888 * (((1/DIST(N_i,O_j) + 1/DIST(H_i,C_j)) - 1/DIST(H_i,O_j)) - 1/DIST(N_i,C_j));  any of the four distances < 0.5: e = -9.9.
+ *   hb(j -> i), C=O of j to N-H of i, holds when e < hb_energy (the caller's, finite and < 0; shipped -0.5 kcal/mol).
+ * TURN_n(i), n = 3, 4, 5: CONT(i, i+n) and hb(i -> i+n).
+ * BRIDGE(i, j): 1 <= i, j <= Lab-2, |i - j| >= 3, CONT(i-1, i+1) and CONT(j-1, j+1);
+ *   parallel:      [hb(i-1 -> j) and hb(j -> i+1)] or [hb(j-1 -> i) and hb(i -> j+1)];
+ *   antiparallel:  [hb(i -> j) and hb(j -> i)] or [hb(i-1 -> j+1) and hb(j-1 -> i+1)].   Both are symmetric in (i, j); chains may differ.
+ * LADDERED: a parallel bridge (i, j) if (i+1, j+1) or (i-1, j-1) is a parallel bridge; an antiparallel one if (i+1, j-1) or (i-1, j+1)
+ *   is an antiparallel bridge.
+ * BEND(i): CONT(i-2, i+2);  u = CA_i - CA_(i-2);  v = CA_(i+2) - CA_i;  c = (ux*vx + uy*vy) + uz*vz;  the row bends when
+ *   c < bend[0] * (|u| * |v|), |.| as DIST.  bend: (cos, sin) of 70 degrees, computed once on the host (abx_amd.secondary.thresholds)
+ *   and checked as a unit pair.
+ * STATE of row k, by order-free per-row rules; START_n(i) = TURN_n(i-1) and TURN_n(i):
+ *   0 '.'  the row is not present;                      1 'H'  some i in [k-3, k] has START_4(i);
+ *   4 'E' / 5 'B'  not H and the row has a bridge: E if one of its bridges is laddered, else B;
+ *   2 'G'  not H, E, B and some i in [k-2, k] has START_3(i) with none of the rows i..i+2 being H, E or B;
+ *   3 'I'  none of those and some i in [k-4, k] has START_5(i) with none of the rows i..i+4 being H, E, B or G;
+ *   6 'T'  none of those and TURN_n(i) for some n and some i in [k-n+1, k-1];     7 'S'  none of those and BEND(k);     8 '-' otherwise.
+ *   Three-state class: helix {H, G, I}, strand {E, B}, coil the rest.
+ * A bond is an ordered (donor, acceptor) pair; "region end": its donor or its acceptor row is a region row.  A bridge pair is unordered
+ * and counts once per type.
+ *   0 n_hb             bonds in the antibody                  9-16 ss_H ss_G ss_I ss_E ss_B ss_T ss_S ss_C  region rows of the design by state
+ *   1 n_hb_region      bonds with a region end               17 n_ss          region rows present in both structures
+ *   2 n_hb_inside      bonds with both rows in the region    18 q8_same       ... with the same state in both
+ *   3 hb_wild_region   the wild type's bonds of column 1     19 q3_same       ... with the same three-state class in both
+ *   4 hb_kept_region   of those, the ones the design has     20 strand_ab     rows of the whole antibody in E or B
+ *   5 hb_energy_region sum of e over the bonds of column 1   21 helix_ab      rows of the whole antibody in H, G or I
+ *   6 n_bridge_region  bridge pairs with a region row         7 bridge_wild_region  the wild type's
+ *   8 bridge_kept_region  bridge pairs in both structures, same pair and same type
+ *   Column 5 is accumulated as rint(e * 2^20) in a 64-bit integer (the adds commute) and reported divided by 2^20.
+ * rows: optional (B, Lab, 6) int32: the state, bonds donated, bonds accepted, the lowest and the next bridge partner row (-1: none), and
+ * the flag word 1 region | 2 present | 4 has H | 8 parallel bridge | 16 antiparallel bridge | 32 bend | 64 / 128 / 256 TURN_3 / 4 / 5
+ * starts here.  classes: optional (B, Lab) int32, the states.  out / out_stride as in AbxDesignScoreArgs (>= ABX_SECONDARY_COLS).
+ * One launch, one workgroup of 256 per structure, the wild type first: N, CA, C, O staged as float32 in LDS (48 Lab bytes; widening at
+ * the use is exact), one lane per donor with its own N and H in registers and the acceptor rows broadcast, the bonds of a donor as the
+ * bits of its own row of an LDS matrix [Lab][ceil(Lab/32) | 1] written by that lane alone; then pattern phases of one lane per row
+ * between barriers.  The wild type's bit image and one word per row (state, present, CONT(i-1, i+1)) go to this workgroup's slice of
+ * the workspace and are read back, after a workgroup barrier, by the same workgroup.  Dynamic LDS up to 118400 bytes at Lab = 800, so
+ * the entry raises the kernel's limit once per device; one workgroup per CU.  Lab <= ABX_SECONDARY_MAX_LAB; more is an argument error.
+ * No allocation, no synchronisation.  The caller allocates the workspace (abx_secondary_scores_workspace_bytes). */
+#define ABX_SECONDARY_COLS 22
+#define ABX_SECONDARY_MAX_LAB 800
+typedef struct AbxSecondaryArgs {
+    const float* pred_atom14; long long pred_sb; int Lpred;
+    const long long* pred_seq; long long pred_seq_sb;
+    const unsigned char* pred_mask;                 /* optional (B,L,14) */
+    const unsigned char* res_mask;                  /* optional (L) */
+    const float* gt_atom14; const unsigned char* gt_exists; const long long* gt_seq;
+    const unsigned char* region;                    /* optional (L) */
+    const float* radius;                            /* [21][14] van-der-Waals radii as in AbxGuidanceArgs (> 0: the type has the slot) */
+    const int* chain_id;                            /* (L) */
+    const int* residx;                              /* optional (L) */
+    double hb_energy;                               /* a bond: e < hb_energy; finite, < 0 */
+    double bend[2];                                 /* (cos, sin) of the bend angle */
+    double* out; long long out_stride;
+    int* rows;                                      /* optional (B,Lab,6) */
+    int* classes;                                   /* optional (B,Lab) */
+    int pro;                                        /* the residue type without an H */
+    int B, L, Lab;
+} AbxSecondaryArgs;
+long long abx_secondary_scores_workspace_bytes(int B, int Lab);
+int abx_secondary_scores(const AbxSecondaryArgs* a, void* workspace, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Op-group entry points: one call per reference module of the pair stack, for a maintainer who binds
  * abx/model/seqformer.py without the Python orchestration of abx_amd/model/forward.py.  Each is a fixed sequence of the launches above
  * (abx_gemm descriptors filled here exactly as forward.py fills them; same kernels, same bits), asynchronous on the stream, no
