@@ -22,6 +22,7 @@ import functools
 import numpy as np
 
 from . import complex_view
+from .complex_view import to_np
 
 # The row of abx_accuracy_scores (include/abx_hip.h, ABX_ACC_COLS)
 ACCURACY_COLUMNS = ('lddt_all', 'lddt_antibody', 'lddt_region', 'lddt_bb_region', 'lddt_ca_all', 'lddt_ca_region', 'plddt_region',
@@ -71,6 +72,15 @@ class AccuracyScorer(complex_view.ComplexView):
         table = ops.accuracy_scores(atom14, seq, self.gt_atom14, self.gt_seq, self.gt_exists, Lab=self.Lab, region=self.region, mask=mask,
                                     res_mask=self.res_mask, plddt=plddt, out=out, rows=r, counts=c, contacts=k, **self.kw)
         return (table, r, c, k) if (rows or counts or contacts) else table
+
+    def record(self, rec, key, atom14, seq, design=True, plddt=None, **context):
+        """ComplexView.record: 'accuracy' - lDDT, TM-score / GDT and native-contact recovery against the crystal structure, and the
+        calibration of the per-residue pLDDT of the last network call (before it is averaged into the record's 'pLDDT') -, for the designs
+        'accuracy_rows' (B, L, 4) per residue, and with a relaxer 'accuracy_relaxed'.  Two launches per table."""
+        if design:
+            rec[key], rec[key + '_rows'] = self.score(atom14, seq, plddt=plddt, rows=True)[:2]
+        else:
+            rec[key] = self.score(atom14, seq, plddt=plddt)
 
     # wild(**kw): the crystal structure against itself - every lDDT 1, fnat 1, rmsd_ca 0, the pLDDT columns nan: the first line of the
     # driver's table and the check that the conventions line up
@@ -163,7 +173,6 @@ def accuracy_host(x, mask, aa, gt_x, gt_mask, gt_aa, Lab, region=None, res_mask=
             n_borderline: atom pairs whose |d_wild - radius|, ||d_wild - d_design| - t| or |d^2 - contact^2| is <= 1e-9,
             n_borderline_gdt: C-alpha whose distance after the superposition lies within 1e-6 of a GDT cutoff)
     - the decisions a device evaluation may legitimately take differently.  The pair walk runs over `chunk` row residues at a time."""
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     xd = to_np(x).astype(np.float32).astype(np.float64)
     xw = to_np(gt_x).astype(np.float32).astype(np.float64)
     L = xd.shape[0]

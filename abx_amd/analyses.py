@@ -1,8 +1,7 @@
-"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES (or, the later ones, in EXTENSIONS, LATER and
-FURTHER) beside the writers of its tables, and RowLayout, the columns of the row table that a set-level run gathers.  design.main walks
-ANALYSES + EXTENSIONS + LATER + FURTHER in their order for the option checks, the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and
-zero-row blocks come from the same declarations), the set-level rows and the files of rank 0: the next analysis is one more entry here
-and nothing in main."""
+"""The per-design analyses of the design driver (abx_amd.design), each stated ONCE in ANALYSES beside the writers of its tables, and
+RowLayout, the columns of the row table that a set-level run gathers.  design.main walks ANALYSES in its order for the option checks,
+the scorers, the keywords of sampler.sample_fn, the gathered fields (filled and zero-row blocks come from the same declarations), the
+set-level rows and the files of rank 0: the next analysis is one more entry here and nothing in main."""
 import functools
 import math
 import os
@@ -99,52 +98,85 @@ RELAX = Analysis('relax', 'relaxer', lambda batch, a, *_: relax.ViolationRelaxer
                  lambda a, out_dir, cname, ids, F, scorer: [_write_relax(out_dir, cname, list(zip(ids, F['relax'].tolist())), a.score)])
 
 
-def _write_with_wild_deltas(kind, out_dir, cname, wild, rows, relaxed):
-    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence, developability, shape, patches): the `wild` line, then (sample
-    id, values) per sample; values = the module's <KIND>_COLUMNS row and, when relaxed, the row of the relaxed structure.  After the
-    columns: delta_<column> = row minus wild for the module's DELTA_COLUMNS.  wild None: every sample has a wild row of its own, the
-    last columns of its values, and the `wild` line is their mean."""
-    mod = {'interface': interface, 'polar': polar, 'confidence': confidence, 'developability': developability, 'shape': shape, 'patches': patches}[kind]
+def _write_with_wild_deltas(kind, out_dir, cname, wild, rows, relaxed, strings=None, text=None):
+    """<out_dir>/<complex>_<kind>.tsv of the analysis module abx_amd.<kind> (interface, polar, confidence, developability, shape, patches,
+    torsions, secondary): the `wild` line, then (sample id, values) per sample; values = the module's <KIND>_COLUMNS row and, when
+    relaxed, the row of the relaxed structure.  After the columns: delta_<column> = row minus wild for the module's DELTA_COLUMNS, then
+    the _relaxed columns.  wild None: every sample has a wild row of its own, the last columns of its values, and the `wild` line is
+    their mean.  text: the name of a last column of strings; strings = (the wild type's string, [the string of every sample]); None: '-'."""
+    mod = {'interface': interface, 'polar': polar, 'confidence': confidence, 'developability': developability, 'shape': shape, 'patches': patches,
+           'torsions': torsions, 'secondary': secondary}[kind]
     columns, fmt = getattr(mod, f'{kind.upper()}_COLUMNS'), getattr(mod, f'format_{kind}')
     N = len(columns)
     wilds = [wild if wild is not None else v[len(v) - N:] for _, v in rows]
     if wild is None:
         wild = [sum(w[k] for w in wilds) / max(len(wilds), 1) for k in range(N)]
+    wild_s, row_s = strings if strings is not None else ('-', ['-'] * len(rows))
+    last = (lambda s: [s]) if text else (lambda s: [])
     tsv = os.path.join(out_dir, f'{cname}_{kind}.tsv')
     with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(columns + tuple('delta_' + c for c in mod.DELTA_COLUMNS) +
-                                       (tuple(c + '_relaxed' for c in columns) if relaxed else ())) + '\n')
-        f.write('wild\t' + '\t'.join(fmt(wild) + mod.format_delta(wild, wild) + (['nan'] * N if relaxed else [])) + '\n')
-        for (i, v), w in zip(rows, wilds):
-            f.write(f'{i}\t' + '\t'.join(fmt(v[:N]) + mod.format_delta(v[:N], w) + (fmt(v[N:2 * N]) if relaxed else [])) + '\n')
+        f.write('sample\t' + '\t'.join(list(columns) + ['delta_' + c for c in mod.DELTA_COLUMNS] +
+                                       ([c + '_relaxed' for c in columns] if relaxed else []) + last(text)) + '\n')
+        f.write('wild\t' + '\t'.join(fmt(wild) + mod.format_delta(wild, wild) + (['nan'] * N if relaxed else []) + last(wild_s)) + '\n')
+        for (i, v), w, st in zip(rows, wilds, row_s):
+            f.write(f'{i}\t' + '\t'.join(fmt(v[:N]) + mod.format_delta(v[:N], w) + (fmt(v[N:2 * N]) if relaxed else []) + last(st)) + '\n')
     return tsv
 
 
 # What --<flag>_rows / _planes adds to a wild table.  of_record: last record -> the field; to_array: gathered field -> <complex>_<field>.npy
 Extra = namedtuple('Extra', 'option field of_record to_array')
+# The text column of a wild table: the class string of the designed residues.  field: the name of a second gathered field (n, 3, Lab)
+# int32 - the codes of the design, those of the wild type and the region mask, so that any rank can write the column on both schedules
+# (it travels in the rows like `seq`); string(classes, region) -> the text of a line.  The sampler's record carries <flag>_classes, the
+# scorer has new_classes(1) and wild(classes=).
+Text = namedtuple('Text', 'field string')
 
 
-def _wild_table(flag, columns, writer, build, wild, checks, extra=None):
+def _wild_table(flag, columns, writer, build, wild, checks, extra=None, text=None):
     """An analysis whose <complex>_<flag>.tsv compares every design with a wild row.  Its field is the design's row, with --relax the
     relaxed structure's, then the wild row, so that any rank can write the table: (n, 2 or 3 x columns).  wild(last, scorers) -> the
-    wild row(s): (1, columns) of the complex, or (n, columns), one per sample; writer(out_dir, cname, wild of row 0, rows, relaxed)."""
+    wild row(s): (1, columns) of the complex, or (n, columns), one per sample (with a Text: unused, the wild row comes with the wild
+    type's classes); writer(out_dir, cname, wild of row 0, rows, relaxed), with a Text one argument more, the strings."""
     def fields(a):
-        return [Field(flag, F64, (len(columns) * (3 if a.relax else 2),), True)] + ([extra.field] if extra and getattr(a, extra.option) else [])
+        return [Field(flag, F64, (len(columns) * (3 if a.relax else 2),), True)] + ([Field(text.field, torch.int32, (3, 'Lab'), True)] if text else []) + \
+            ([extra.field] if extra and getattr(a, extra.option) else [])
 
     def collect(a, traj, scorers):
-        last = traj[-1]
-        out = {flag: torch.cat([last[flag]] + ([last[flag + '_relaxed']] if a.relax else []) + [wild(last, scorers).expand(last['seq'].shape[0], -1)], 1)}
+        last, n = traj[-1], traj[-1]['seq'].shape[0]
+        if text:
+            sc = scorers[flag]
+            wild_classes = sc.new_classes(1)
+            w = sc.wild(classes=wild_classes)
+        else:
+            w = wild(last, scorers)
+        out = {flag: torch.cat([last[flag]] + ([last[flag + '_relaxed']] if a.relax else []) + [w.expand(n, -1)], 1)}
+        if text:
+            out[text.field] = torch.stack([last[flag + '_classes'], wild_classes.expand(n, -1), sc.region[None, :sc.Lab].to(torch.int32).expand(n, -1)], 1)
         if extra and getattr(a, extra.option):
             out[extra.field.name] = extra.of_record(last)
         return out
 
     def write(a, out_dir, cname, ids, F, scorer):
-        t = F[flag].tolist()
-        files = [writer(out_dir, cname, t[0][-len(columns):], list(zip(ids, t)), a.relax)]
+        t, strings = F[flag].tolist(), []
+        if text:
+            ab = F[text.field].cpu().numpy()
+            strings = [(text.string(ab[0, 1], ab[0, 2]), [text.string(r[0], r[2]) for r in ab])]
+        files = [writer(out_dir, cname, t[0][-len(columns):], list(zip(ids, t)), a.relax, *strings)]
         if extra and getattr(a, extra.option):
             files.append(_save(out_dir, cname, extra.field.name, extra.to_array(F[extra.field.name])))
         return files
     return Analysis(flag, flag, build, fields, collect, write, checks, extra and extra.option)
+
+
+def _build(make, rows_option=None):
+    """build of an analysis from make(batch, a, the interface scorer of the batch or None) -> the scorer; rows_option: the --<flag>_rows
+    option that sets its want_rows."""
+    def build(batch, a, model, cfg, scorers):
+        sc = make(batch, a, scorers.get('interface'))
+        if rows_option:
+            sc.want_rows = getattr(a, rows_option)
+        return sc
+    return build
 
 
 _write_interface = functools.partial(_write_with_wild_deltas, 'interface')
@@ -153,6 +185,32 @@ INTERFACE = _wild_table('interface', interface.INTERFACE_COLUMNS, _write_interfa
                         lambda last, scorers: scorers['interface'].wild(points=_shared_wild_points(scorers)),
                         [(lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0 or a.interface_cutoff <= 0,
                           '--interface_points must be in 1..1024, --interface_probe >= 0, --interface_cutoff > 0')])
+
+
+# The analyses on the point counts of the interface analysis (the interface.SurfaceScorer classes: polar, developability, shape,
+# patches) are coupled to --interface in three places: with --interface the scorer is built on THAT InterfaceScorer and the surface kernel
+# runs once per structure set for all tables (sampler.sample_fn hands the counts over); one buffer of counts serves all wild rows
+# (_shared_wild_points); and without --interface each validates the options of the surface, --interface_points and --interface_probe,
+# itself (SURFACE_CHECK).
+SURFACE_CHECK = (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')
+SURFACE_FLAGS = []
+
+
+def _surface_table(flag, columns, writer, make, check, extra=None):
+    """_wild_table of an analysis whose scorer make(batch, a, interface) is a SurfaceScorer; check: of its own options."""
+    SURFACE_FLAGS.append(flag)
+    return _wild_table(flag, columns, writer, _build(make, extra and extra.option),
+                       lambda last, scorers: scorers[flag].wild(points=_shared_wild_points(scorers)), [check, SURFACE_CHECK], extra)
+
+
+def _shared_wild_points(scorers):
+    """A surface analysis with --interface: the (1, L, 14, 2) point counts of the wild type that interface.wild() fills and the wild()
+    of every SurfaceScorer reads instead of running the surface kernel again, kept with the scorers of the batch; None without
+    --interface or without any of them."""
+    users = [scorers[k] for k in SURFACE_FLAGS if k in scorers]
+    if users and 'interface' in scorers and 'wild_points' not in scorers:
+        scorers['wild_points'] = users[0].new_points(1)
+    return scorers.get('wild_points')
 
 
 # --confidence: every sample carries a wild row of its own, the input complex's coordinates under the SAME design's prediction; the
@@ -196,36 +254,15 @@ ACCURACY = _wild_table('accuracy', accuracy.ACCURACY_COLUMNS, _write_accuracy,
                        Extra('accuracy_rows', Field('accuracy_rows', F64, ('L', 4), False), lambda last: last['accuracy_rows'], lambda t: t.cpu().numpy()))
 
 
-# --polar: the unsatisfied atoms come from the point counts of the interface analysis, so polar is coupled to --interface in three
-# places: with --interface the scorer is built on THAT InterfaceScorer and the surface kernel runs once per structure set for both tables
-# (sampler.sample_fn hands the counts over); one buffer of counts serves both wild rows (_shared_wild_points); and without --interface
-# polar validates the options of the surface, --interface_points and --interface_probe, itself.
-POLAR_CHECKS = [(lambda a: not a.polar_hb_max >= 2.0 or not 90.0 <= a.polar_hb_angle < 180.0 or not a.polar_salt >= 0,
-                 '--polar_hb_max must be >= 2.0 (the smallest donor-acceptor distance), --polar_hb_angle in [90, 180), --polar_salt >= 0'),
-                (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')]
-
-
-def _polar_build(batch, a, model, cfg, scorers):
-    pol = polar.PolarScorer(batch, hb_max=a.polar_hb_max, hb_angle=a.polar_hb_angle, salt=a.polar_salt, n_points=a.interface_points,
-                            probe=a.interface_probe, interface=scorers.get('interface'))
-    pol.want_rows = a.polar_rows
-    return pol
-
-
-def _shared_wild_points(scorers):
-    """--polar, --developability, --shape or --patches with --interface: the (1, L, 14, 2) point counts of the wild type that
-    interface.wild() fills and polar.wild() / developability.wild() / shape.wild() / patches.wild() read instead of running the surface
-    kernel again, kept with the scorers of the batch; None without --interface or without any of the four."""
-    users = [scorers[k] for k in ('polar', 'developability', 'shape', 'patches') if k in scorers]
-    if users and 'interface' in scorers and 'wild_points' not in scorers:
-        scorers['wild_points'] = users[0].new_points(1)
-    return scorers.get('wild_points')
-
-
+# --polar: hydrogen bonds and salt bridges across the interface; the unsatisfied atoms come from the point counts of the interface analysis.
 _write_polar = functools.partial(_write_with_wild_deltas, 'polar')
-POLAR = _wild_table('polar', polar.POLAR_COLUMNS, _write_polar, _polar_build, lambda last, scorers: scorers['polar'].wild(points=_shared_wild_points(scorers)),
-                    POLAR_CHECKS, Extra('polar_rows', Field('polar_rows', torch.int32, ('L', 4), False), lambda last: last['polar_rows'],
-                                        lambda t: t.cpu().numpy().astype('int16')))
+POLAR = _surface_table('polar', polar.POLAR_COLUMNS, _write_polar,
+                       lambda batch, a, it: polar.PolarScorer(batch, hb_max=a.polar_hb_max, hb_angle=a.polar_hb_angle, salt=a.polar_salt,
+                                                              n_points=a.interface_points, probe=a.interface_probe, interface=it),
+                       (lambda a: not a.polar_hb_max >= 2.0 or not 90.0 <= a.polar_hb_angle < 180.0 or not a.polar_salt >= 0,
+                        '--polar_hb_max must be >= 2.0 (the smallest donor-acceptor distance), --polar_hb_angle in [90, 180), --polar_salt >= 0'),
+                       Extra('polar_rows', Field('polar_rows', torch.int32, ('L', 4), False), lambda last: last['polar_rows'],
+                             lambda t: t.cpu().numpy().astype('int16')))
 
 
 # --ensemble: the designs of a complex compared with each other (ensemble.EnsembleAnalyzer) by the rank that writes, after the gather: the
@@ -266,41 +303,20 @@ ENSEMBLE = Analysis('ensemble', None, lambda batch, a, *_: ensemble.EnsembleAnal
                     [(lambda a: not 1 <= a.num_samples <= ensemble.MAX_N or not a.ensemble_cutoff >= 0,
                       f'--ensemble compares 1..{ensemble.MAX_N} samples of a complex, --ensemble_cutoff must be >= 0')])
 
-ANALYSES = (SCORE, RELAX, INTERFACE, CONFIDENCE, ACCURACY, POLAR, ENSEMBLE)
-
-
-# --developability: aggregation propensity, chain charges and sequence liabilities of the free antibody.  Its exposure comes from the
-# point counts of the interface analysis, so it is coupled to --interface exactly as --polar is (the three places named there).
-DEVELOPABILITY_CHECKS = [(lambda a: not a.developability_radius > 0 or not 0.0 <= a.developability_exposed <= 1.0,
-                          '--developability_radius must be > 0, --developability_exposed in [0, 1]'),
-                         (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')]
-
-
-def _developability_build(batch, a, model, cfg, scorers):
-    dev = developability.DevelopabilityScorer(batch, radius=a.developability_radius, exposed=a.developability_exposed, n_points=a.interface_points,
-                                              probe=a.interface_probe, interface=scorers.get('interface'))
-    dev.want_rows = a.developability_rows
-    return dev
-
-
+# --developability: aggregation propensity, chain charges and sequence liabilities of the free antibody; its exposure comes from the point
+# counts of the interface analysis.
 _write_developability = functools.partial(_write_with_wild_deltas, 'developability')
-DEVELOPABILITY = _wild_table('developability', developability.DEVELOPABILITY_COLUMNS, _write_developability, _developability_build,
-                             lambda last, scorers: scorers['developability'].wild(points=_shared_wild_points(scorers)), DEVELOPABILITY_CHECKS,
-                             Extra('developability_rows', Field('developability_rows', F64, ('L', 4), False), lambda last: last['developability_rows'],
-                                   lambda t: t.cpu().numpy()))
-
-# The analyses added after ANALYSES was pinned: walked after it, declared the same way
-EXTENSIONS = (DEVELOPABILITY,)
-
-
-# --shape: the shape complementarity Sc of the interface.  Its dots are the sphere points of the interface analysis, so it is coupled to
-# --interface exactly as --polar is (the three places named there).  A row of -1 says that a dot list outgrew --shape_max_dots: no
-# table is written with such a row.
-SHAPE_CHECKS = [(lambda a: not a.shape_trim >= 0 or not a.shape_weight >= 0 or not a.shape_max_dots >= 1,
-                 '--shape_trim must be >= 0, --shape_weight >= 0, --shape_max_dots >= 1'),
-                (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')]
+DEVELOPABILITY = _surface_table('developability', developability.DEVELOPABILITY_COLUMNS, _write_developability,
+                                lambda batch, a, it: developability.DevelopabilityScorer(batch, radius=a.developability_radius, exposed=a.developability_exposed,
+                                                                                         n_points=a.interface_points, probe=a.interface_probe, interface=it),
+                                (lambda a: not a.developability_radius > 0 or not 0.0 <= a.developability_exposed <= 1.0,
+                                 '--developability_radius must be > 0, --developability_exposed in [0, 1]'),
+                                Extra('developability_rows', Field('developability_rows', F64, ('L', 4), False), lambda last: last['developability_rows'],
+                                      lambda t: t.cpu().numpy()))
 
 
+# --shape: the shape complementarity Sc of the interface; its dots are the sphere points of the interface analysis.  A row of -1 says
+# that a dot list outgrew --shape_max_dots: no table is written with such a row.
 def _write_shape(out_dir, cname, wild, rows, relaxed):
     """_write_with_wild_deltas('shape', ...); a row of -1 (its dot count is negative) ends the run by the name of the option to raise."""
     N = len(shape.SHAPE_COLUMNS)
@@ -310,139 +326,52 @@ def _write_shape(out_dir, cname, wild, rows, relaxed):
     return _write_with_wild_deltas('shape', out_dir, cname, wild, rows, relaxed)
 
 
-SHAPE = _wild_table('shape', shape.SHAPE_COLUMNS, _write_shape,
-                    lambda batch, a, model, cfg, scorers: shape.ShapeScorer(batch, trim=a.shape_trim, weight=a.shape_weight, n_points=a.interface_points,
-                                                                            probe=a.interface_probe, max_dots=a.shape_max_dots,
-                                                                            interface=scorers.get('interface')),
-                    lambda last, scorers: scorers['shape'].wild(points=_shared_wild_points(scorers)), SHAPE_CHECKS)
-
-# The analyses added after EXTENSIONS was pinned in its turn: walked after both
-LATER = (SHAPE,)
+SHAPE = _surface_table('shape', shape.SHAPE_COLUMNS, _write_shape,
+                       lambda batch, a, it: shape.ShapeScorer(batch, trim=a.shape_trim, weight=a.shape_weight, n_points=a.interface_points,
+                                                              probe=a.interface_probe, max_dots=a.shape_max_dots, interface=it),
+                       (lambda a: not a.shape_trim >= 0 or not a.shape_weight >= 0 or not a.shape_max_dots >= 1,
+                        '--shape_trim must be >= 0, --shape_weight >= 0, --shape_max_dots >= 1'))
 
 
 # --patches: the patches of surface hydrophobicity and of charge around the CDRs, the charge symmetry of the Fv and the charge pairing
-# across the interface.  Its exposure comes from the point counts of the interface analysis, so it is coupled to --interface exactly as
-# --polar is (the three places named there).
-PATCHES_CHECKS = [(lambda a: not a.patches_cutoff > 0 or not a.patches_vicinity > 0 or not a.patches_salt > 0 or not 0.0 <= a.patches_exposed <= 1.0,
-                   '--patches_cutoff, --patches_vicinity and --patches_salt must be > 0, --patches_exposed in [0, 1]'),
-                  (lambda a: not 1 <= a.interface_points <= 1024 or a.interface_probe < 0, '--interface_points must be in 1..1024, --interface_probe >= 0')]
-
-
-def _patches_build(batch, a, model, cfg, scorers):
-    pat = patches.PatchScorer(batch, cutoff=a.patches_cutoff, vicinity=a.patches_vicinity, salt=a.patches_salt, exposed=a.patches_exposed,
-                              n_points=a.interface_points, probe=a.interface_probe, interface=scorers.get('interface'))
-    pat.want_rows = a.patches_rows
-    return pat
-
-
+# across the interface; its exposure comes from the point counts of the interface analysis.
 _write_patches = functools.partial(_write_with_wild_deltas, 'patches')
-PATCHES = _wild_table('patches', patches.PATCHES_COLUMNS, _write_patches, _patches_build,
-                      lambda last, scorers: scorers['patches'].wild(points=_shared_wild_points(scorers)), PATCHES_CHECKS,
-                      Extra('patches_rows', Field('patches_rows', F64, ('L', 4), False), lambda last: last['patches_rows'], lambda t: t.cpu().numpy()))
-
-
-# A wild table like the others with one text column more: the class string of the designed residues (--torsions: `abego`, --secondary:
-# `dssp`).  Declared directly, not through _wild_table: beside its row such an analysis gathers a second field (n, 3, Lab) int32 - the
-# codes of the design, those of the wild type and the region mask, so that any rank can write the column on both schedules (it travels
-# in the rows like `seq`) - and its per-residue table is its Extra.
-def _write_wild_text(kind, columns, delta_columns, fmt, fmt_delta, text, out_dir, cname, wild, rows, relaxed, strings=None):
-    """<out_dir>/<complex>_<kind>.tsv: the `wild` line, then (sample id, values) per sample; values = the `columns` row and, when relaxed,
-    the row of the relaxed structure.  After the columns: delta_<column> = row minus wild for delta_columns, the _relaxed columns, and
-    last the column `text`: strings = (the wild type's string, [the string of every sample]); None: '-'."""
-    N = len(columns)
-    wild_s, row_s = strings if strings is not None else ('-', ['-'] * len(rows))
-    tsv = os.path.join(out_dir, f'{cname}_{kind}.tsv')
-    with open(tsv, 'w') as f:
-        f.write('sample\t' + '\t'.join(columns + tuple('delta_' + c for c in delta_columns) +
-                                       (tuple(c + '_relaxed' for c in columns) if relaxed else ()) + (text,)) + '\n')
-        f.write('wild\t' + '\t'.join(fmt(wild) + fmt_delta(wild, wild) + (['nan'] * N if relaxed else []) + [wild_s]) + '\n')
-        for (i, v), st in zip(rows, row_s):
-            f.write(f'{i}\t' + '\t'.join(fmt(v[:N]) + fmt_delta(v[:N], wild) + (fmt(v[N:2 * N]) if relaxed else []) + [st]) + '\n')
-    return tsv
-
-
-def _wild_text_table(kind, columns, writer, build, text_field, string, checks, extra):
-    """The Analysis of a wild table with a text column: the sampler's records carry <kind>, <kind>_classes, <kind>_relaxed and
-    <extra.option>; text_field: the name of the gathered (n, 3, Lab) int32 field; string(classes, region) -> the text of a line."""
-    N = len(columns)
-
-    def fields(a):
-        return [Field(kind, F64, (N * (3 if a.relax else 2),), True), Field(text_field, torch.int32, (3, 'Lab'), True)] + \
-            ([extra.field] if getattr(a, extra.option) else [])
-
-    def collect(a, traj, scorers):
-        last, sc = traj[-1], scorers[kind]
-        n = last['seq'].shape[0]
-        wild_classes = sc.new_classes(1)
-        wild = sc.wild(classes=wild_classes)
-        out = {kind: torch.cat([last[kind]] + ([last[kind + '_relaxed']] if a.relax else []) + [wild.expand(n, -1)], 1),
-               text_field: torch.stack([last[kind + '_classes'], wild_classes.expand(n, -1), sc.region[None, :sc.Lab].to(torch.int32).expand(n, -1)], 1)}
-        if getattr(a, extra.option):
-            out[extra.option] = extra.of_record(last)
-        return out
-
-    def write(a, out_dir, cname, ids, F, scorer):
-        t, ab = F[kind].tolist(), F[text_field].cpu().numpy()
-        strings = (string(ab[0, 1], ab[0, 2]), [string(r[0], r[2]) for r in ab])
-        files = [writer(out_dir, cname, t[0][-N:], list(zip(ids, t)), a.relax, strings)]
-        if getattr(a, extra.option):
-            files.append(_save(out_dir, cname, extra.option, extra.to_array(F[extra.option])))
-        return files
-
-    return Analysis(kind, kind, build, fields, collect, write, checks, extra.option)
+PATCHES = _surface_table('patches', patches.PATCHES_COLUMNS, _write_patches,
+                         lambda batch, a, it: patches.PatchScorer(batch, cutoff=a.patches_cutoff, vicinity=a.patches_vicinity, salt=a.patches_salt,
+                                                                  exposed=a.patches_exposed, n_points=a.interface_points, probe=a.interface_probe, interface=it),
+                         (lambda a: not a.patches_cutoff > 0 or not a.patches_vicinity > 0 or not a.patches_salt > 0 or not 0.0 <= a.patches_exposed <= 1.0,
+                          '--patches_cutoff, --patches_vicinity and --patches_salt must be > 0, --patches_exposed in [0, 1]'),
+                         Extra('patches_rows', Field('patches_rows', F64, ('L', 4), False), lambda last: last['patches_rows'], lambda t: t.cpu().numpy()))
 
 
 # --torsions: cis and twisted peptides, phi >= 0, the ABEGO classes and the chi recovery of the designs; the text column is `abego`.
-TORSIONS_ROWS = Extra('torsions_rows', Field('torsions_rows', F64, ('Lab', 8), False), lambda last: last['torsions_rows'], lambda t: t.cpu().numpy())
-
-
-def _write_torsions(out_dir, cname, wild, rows, relaxed, strings=None):
-    """<out_dir>/<complex>_torsions.tsv (_write_wild_text): torsions.TORSIONS_COLUMNS, delta_* for torsions.DELTA_COLUMNS, last `abego`."""
-    return _write_wild_text('torsions', torsions.TORSIONS_COLUMNS, torsions.DELTA_COLUMNS, torsions.format_torsions, torsions.format_delta, 'abego',
-                            out_dir, cname, wild, rows, relaxed, strings)
-
-
-def _torsions_build(batch, a, model, cfg, scorers):
-    tor = torsions.TorsionScorer(batch, chi_tol=a.torsions_chi_tol)
-    tor.want_rows = a.torsions_rows
-    return tor
-
-
-TORSIONS = _wild_text_table('torsions', torsions.TORSIONS_COLUMNS, _write_torsions, _torsions_build, 'torsions_abego', torsions.abego_string,
-                            [(lambda a: not 0.0 < a.torsions_chi_tol <= 180.0, '--torsions_chi_tol must be in (0, 180] degrees')], TORSIONS_ROWS)
+_write_torsions = functools.partial(_write_with_wild_deltas, 'torsions', text='abego')
+TORSIONS = _wild_table('torsions', torsions.TORSIONS_COLUMNS, _write_torsions,
+                       _build(lambda batch, a, it: torsions.TorsionScorer(batch, chi_tol=a.torsions_chi_tol), 'torsions_rows'), None,
+                       [(lambda a: not 0.0 < a.torsions_chi_tol <= 180.0, '--torsions_chi_tol must be in (0, 180] degrees')],
+                       Extra('torsions_rows', Field('torsions_rows', F64, ('Lab', 8), False), lambda last: last['torsions_rows'], lambda t: t.cpu().numpy()),
+                       Text('torsions_abego', torsions.abego_string))
 
 # --secondary: DSSP's backbone hydrogen bonds, bridges and states of the antibody against the crystal structure; the text column is
 # `dssp`, the state string of the designed residues.
-SECONDARY_ROWS = Extra('secondary_rows', Field('secondary_rows', torch.int32, ('Lab', 6), False), lambda last: last['secondary_rows'],
-                       lambda t: t.cpu().numpy())
+_write_secondary = functools.partial(_write_with_wild_deltas, 'secondary', text='dssp')
+SECONDARY = _wild_table('secondary', secondary.SECONDARY_COLUMNS, _write_secondary,
+                        _build(lambda batch, a, it: secondary.SecondaryScorer(batch, hb_energy=a.secondary_hb_energy), 'secondary_rows'), None,
+                        [(lambda a: not (math.isfinite(a.secondary_hb_energy) and a.secondary_hb_energy < 0.0),
+                          '--secondary_hb_energy must be a finite energy below 0 kcal/mol')],
+                        Extra('secondary_rows', Field('secondary_rows', torch.int32, ('Lab', 6), False), lambda last: last['secondary_rows'],
+                              lambda t: t.cpu().numpy()),
+                        Text('secondary_ss', secondary.ss_string))
 
-
-def _write_secondary(out_dir, cname, wild, rows, relaxed, strings=None):
-    """<out_dir>/<complex>_secondary.tsv (_write_wild_text): secondary.SECONDARY_COLUMNS, delta_* for secondary.DELTA_COLUMNS, last `dssp`."""
-    return _write_wild_text('secondary', secondary.SECONDARY_COLUMNS, secondary.DELTA_COLUMNS, secondary.format_secondary, secondary.format_delta,
-                            'dssp', out_dir, cname, wild, rows, relaxed, strings)
-
-
-def _secondary_build(batch, a, model, cfg, scorers):
-    sec = secondary.SecondaryScorer(batch, hb_energy=a.secondary_hb_energy)
-    sec.want_rows = a.secondary_rows
-    return sec
-
-
-SECONDARY = _wild_text_table('secondary', secondary.SECONDARY_COLUMNS, _write_secondary, _secondary_build, 'secondary_ss', secondary.ss_string,
-                             [(lambda a: not (math.isfinite(a.secondary_hb_energy) and a.secondary_hb_energy < 0.0),
-                               '--secondary_hb_energy must be a finite energy below 0 kcal/mol')], SECONDARY_ROWS)
-
-# The analyses added since LATER was pinned, walked after the three tuples before it.  The NEXT analysis is appended HERE: a test asserts
-# that its own flag is in FURTHER and that ANALYSES, EXTENSIONS and LATER come first, never the contents of FURTHER, so no fifth tuple
-# is needed.
-FURTHER = (PATCHES, TORSIONS, SECONDARY)
+# Every analysis, in the order they are walked: it fixes the order of the gathered fields and of the collectives.  The next analysis is
+# appended here.
+ANALYSES = (SCORE, RELAX, INTERFACE, CONFIDENCE, ACCURACY, POLAR, ENSEMBLE, DEVELOPABILITY, SHAPE, PATCHES, TORSIONS, SECONDARY)
 
 
 def check_options(a, set_level):
     """The analyses that the parsed options `a` switch on, in order, after their option checks.  set_level: the run gathers rows."""
     active = []
-    for an in ANALYSES + EXTENSIONS + LATER + FURTHER:
+    for an in ANALYSES:
         if getattr(a, an.flag):
             for bad, text in an.checks:
                 if bad(a):

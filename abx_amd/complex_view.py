@@ -1,8 +1,33 @@
 """One complex as the per-design analyses see it, and the pieces their scorers share (metrics.DesignScorer, relax.ViolationRelaxer,
-interface.InterfaceScorer, polar.PolarScorer, accuracy.AccuracyScorer, confidence.DistogramScorer): the extraction of the complex from
-a featurised batch, the default region, the result tables, the wild-type row and the TSV formatting of a row.  The device side of
-the same conventions is csrc/structure_dev.h; ops._structure_args passes one to the other."""
+interface.InterfaceScorer and the interface.SurfaceScorer classes on its point counts - polar.PolarScorer,
+developability.DevelopabilityScorer, shape.ShapeScorer, patches.PatchScorer -, accuracy.AccuracyScorer, confidence.DistogramScorer,
+torsions.TorsionScorer, secondary.SecondaryScorer): the extraction of the complex from a featurised batch, the default region, the
+result tables, the wild-type row, what a scorer adds to the sampler's last record, the TSV formatting of a row and the conversions that
+open the host twins.  The device side of the same conventions is csrc/structure_dev.h; ops._structure_args passes one to the other."""
+import numpy as np
 import torch
+
+
+def to_np(t):
+    """A tensor (on any device) or an array-like as a numpy array: what every host twin reads its arguments through."""
+    return t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
+
+
+def type_index(letter):
+    """The token of a one-letter residue type."""
+    from . import residue_constants as rc
+    return rc.restypes.index(letter)
+
+
+class Borderline:
+    """Counts the decisions `lhs ? rhs` of a host twin whose two sides differ by less than 1e-9 relative (of the size of the operands)."""
+
+    def __init__(self):
+        self.n = 0
+
+    def __call__(self, lhs, rhs, scale, where=True):
+        near = np.abs(lhs - rhs) < 1e-9 * np.maximum(np.abs(scale), 1e-300)
+        self.n += int(np.count_nonzero(near & where))
 
 
 def one_of(batch):
@@ -28,6 +53,8 @@ class ComplexView:
     gt_seq (L) int64, res_mask (L) uint8 or None; with chains: chain_id (L) int32 and residx (L) int32 (None without link_by_residx:
     array neighbours are then linked by chain id alone); with cdr: cdr_def (L) int32.  A scorer names its row in COLUMNS."""
     COLUMNS = ()
+    want_rows = False                   # set on an instance: the design's record also carries the per-residue tables of side_outputs
+    takes_points = False                # score(..., points=): the (B,L,14,2) point counts of the surface kernel, written or read
 
     def __init__(self, batch, chains=False, link_by_residx=True, cdr=False):
         one = one_of(batch)
@@ -50,6 +77,19 @@ class ComplexView:
     def wild(self, **kw):
         """(1, len(COLUMNS)): the row of the ground-truth complex itself with its own atoms; kw: the optional outputs of score()."""
         return self.score(self.gt_atom14[None, :self.Lab], self.gt_seq[None, :self.Lab], mask=self.gt_exists[None], **kw)
+
+    def side_outputs(self, B):
+        """{keyword of score(): an uninitialised tensor for B structures}: what the record of the designs carries beside their row."""
+        return {}
+
+    def record(self, rec, key, atom14, seq, design=True, points=None, **context):
+        """What sampler.sample_fn adds to its last record for this scorer: rec[key] = the (B, len(COLUMNS)) float64 rows of the structures
+        atom14; design: they are the designs themselves, not their relaxed structures, and rec[f'{key}_{k}'] receives the side_outputs.
+        points: the point counts that the scorers of one surface share (takes_points), or None; context: what other scorers read - the
+        model's output `out` and the per-residue `plddt` of the last network call.  Launches only, no host synchronisation."""
+        side = self.side_outputs(atom14.shape[0]) if design else {}
+        rec.update({f'{key}_{k}': v for k, v in side.items()})
+        rec[key] = self.score(atom14, seq, **side, **({'points': points} if self.takes_points else {}))
 
 
 def _places(places, column):

@@ -11,6 +11,7 @@ import functools
 import numpy as np
 
 from . import complex_view
+from .complex_view import to_np
 
 # The row of abx_distogram_scores (include/abx_hip.h, ABX_DISTO_COLS).  region = the designed rows; pairs are ordered, i != j, both valid.
 CONFIDENCE_COLUMNS = ('nll_all', 'nll_antibody_antigen', 'nll_region', 'nll_region_antigen', 'dist_err_region', 'entropy_region',
@@ -122,6 +123,22 @@ class DistogramScorer(complex_view.ComplexView):
         B = pair.shape[0]
         return self.score(pair, self.gt_atom14[None].expand(B, -1, -1, -1), self.gt_seq[None].expand(B, -1), wild=True)
 
+    def record(self, rec, key, atom14, seq, design=True, out=None, **context):
+        """ComplexView.record: 'confidence' and, for the designs, 'confidence_rows' (B, L, 4) - the distogram head of the last network call
+        against the designs it emitted -, 'confidence_wild' (the input complex's own coordinates against the same predictions) and with
+        want_planes 'confidence_planes' = (p_contact, exp_dist); with a relaxer 'confidence_relaxed'.  Reads out['representations']['pair']
+        of the call just made (the next call overwrites that buffer: model/abx.py:16-18, and nothing between it and here runs the
+        network); two launches per table."""
+        pair = out['representations']['pair']
+        if not design:
+            rec[key] = self.score(pair, atom14, seq)[0]
+            return
+        got = self.score(pair, atom14, seq, planes=bool(self.want_planes))
+        rec[key], rec[key + '_rows'] = got[0], got[1]
+        if len(got) > 2:
+            rec[key + '_planes'] = got[2]
+        rec[key + '_wild'] = self.wild(pair)[0]
+
     def logits(self, pair, samples):
         """{'logits': (n,L,L,64) f32, 'breaks': (63) f32} of the designs `samples` (indices into the batch), the layout of upstream's
         heads['distogram'] (head.py:44).  For a few designs: an output above 1 GiB is refused."""
@@ -151,7 +168,6 @@ def distogram_host(pair, W, b, breaks, pb, classes, valid, cutoff=8.0):
     fused multiply-add); everything else is float64.  -> dict: logits (B,L,L,64) f64, bound_scale (B,L,L,64) f64 = sum_k |zs_k W_kn| +
     |b_n| (what the fp32 dot-product bound multiplies), d2 (B,L,L) f32, bin_real, contact, ok (the pair sets' base: i != j, both
     valid), nll, entropy, p_contact, exp_dist (B,L,L) f64, table (B, len(CONFIDENCE_COLUMNS)), rows (B, L, len(ROW_COLUMNS))."""
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     z = to_np(pair).astype(np.float32)
     B, L = z.shape[:2]
     W64, b64 = to_np(W).astype(np.float32).astype(np.float64), to_np(b).astype(np.float32).astype(np.float64)

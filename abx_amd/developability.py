@@ -16,7 +16,8 @@ import functools
 import numpy as np
 
 from . import complex_view
-from .interface import FOUR_PI
+from .complex_view import to_np
+from .interface import FOUR_PI, SurfaceScorer
 
 # The row of abx_developability_scores (include/abx_hip.h, ABX_DEV_COLS)
 DEVELOPABILITY_COLUMNS = ('sap_pos', 'sap_pos_cdr', 'sap_pos_region', 'sap_max_res', 'n_res_sap_pos', 'n_res_sap_pos_region', 'charge_heavy',
@@ -121,46 +122,30 @@ def weight_table(P=128, probe=1.4):
     return _weight_table(int(P), float(probe))
 
 
-class DevelopabilityScorer:
+class DevelopabilityScorer(SurfaceScorer):
     """Developability rows of batches of designs of ONE complex on the device.  Built once per complex from its featurised batch (or the
-    un-batched complex) like polar.PolarScorer, and holds an InterfaceScorer for the point counts.  region: (L) mask of the rows the
-    `*_region` columns count (default: the rows the sampler diffuses).  radius: of the SAP sphere (Angstrom); exposed: smallest relative
-    side-chain area of an exposed residue; n_points / probe: of the surface.  interface: an existing InterfaceScorer of the same
-    complex - `score(..., points=)` then takes the counts of ITS call for the same structures, so that the surface kernel runs once
-    per structure set."""
+    un-batched complex) like polar.PolarScorer, and holds an InterfaceScorer for the point counts (interface.SurfaceScorer: region,
+    n_points / probe of the surface, interface).  radius: of the SAP sphere (Angstrom); exposed: smallest relative side-chain area of an
+    exposed residue."""
 
-    want_rows = False                   # set on an instance: sampler.sample_fn also records 'developability_rows'
+    COLUMNS = DEVELOPABILITY_COLUMNS
 
     def __init__(self, batch, region=None, radius=10.0, exposed=0.075, n_points=128, probe=1.4, interface=None):
         import torch
-        from .interface import InterfaceScorer
         if not (radius > 0 and 0.0 <= exposed <= 1.0):
             raise ValueError(f'developability: needs radius > 0 and exposed in [0, 1] (got {radius}, {exposed})')
-        self.interface = interface if interface is not None else InterfaceScorer(batch, region=region, n_points=n_points, probe=probe)
-        it = self.interface
-        dev = it.gt_atom14.device
-        self.region = it.region if region is None else complex_view.region_mask(batch, region, dev)
-        self.Lab, self.L = it.Lab, int(it.gt_seq.shape[0])
+        super().__init__(batch, region, n_points, probe, interface)
         view = complex_view.ComplexView(batch, chains=True, cdr=True)
         self.chain_id, self.residx, self.cdr_def = view.chain_id, view.residx, view.cdr_def
-        P, probe = int(it.sphere.shape[0]), it.kw['probe']
+        P, probe = int(self.interface.sphere.shape[0]), self.interface.kw['probe']
         q, a, ref = weight_table(P, probe)
-        self.tables = tuple(torch.from_numpy(np.array(t)).to(dev) for t in (q, a, ref))     # (copies: the cached tables are read-only)
+        self.tables = tuple(torch.from_numpy(np.array(t)).to(self.device) for t in (q, a, ref))     # (copies: the cached tables are read-only)
         self.kw = dict(radius=float(radius), exposed=float(exposed), n_points=P, q_max=int(np.abs(q).max()))
-
-    def new_table(self, *lead):
-        """An uninitialised (*lead, len(DEVELOPABILITY_COLUMNS)) float64 table on the complex's device for `score(..., out=table[i])`."""
-        return complex_view.new_table(DEVELOPABILITY_COLUMNS, self.region.device, *lead)
-
-    def new_points(self, B):
-        """An uninitialised (B, L, 14, 2) int32 tensor for the point counts of B structures."""
-        import torch
-        return torch.empty(B, self.L, 14, 2, dtype=torch.int32, device=self.region.device)
 
     def new_rows(self, B):
         """An uninitialised (B, L, 4) float64 tensor for ROW_COLUMNS of B structures."""
         import torch
-        return torch.empty(B, self.L, 4, dtype=torch.float64, device=self.region.device)
+        return torch.empty(B, self.L, 4, dtype=torch.float64, device=self.device)
 
     def score(self, atom14, seq, out=None, points=None, rows=None, mask=None, j_chunk=0):
         """atom14 (B, Lab or L, 14, 3) f32 predicted coordinates, seq (B, Lab) tokens -> (B, len(DEVELOPABILITY_COLUMNS)) float64 on the
@@ -168,19 +153,17 @@ class DevelopabilityScorer:
         (B,L,14,2) int32 acc_alone / acc_cplx that the interface scorer returned for THESE structures (None: its kernel runs here).
         No host synchronisation."""
         from abx_amd import ops
-        it = self.interface
-        if points is None:
-            points = self.new_points(atom14.shape[0])
-            it.score(atom14, seq, points=points, mask=mask)
-        return ops.developability_scores(atom14, seq, it.gt_atom14, it.gt_seq, it.gt_exists, self.chain_id, self.cdr_def, self.tables, points,
-                                         Lab=self.Lab, residx=self.residx, region=self.region, mask=mask, res_mask=it.res_mask, out=out,
+        points = self.points_of(atom14, seq, points, mask)
+        return ops.developability_scores(atom14, seq, self.gt_atom14, self.gt_seq, self.gt_exists, self.chain_id, self.cdr_def, self.tables, points,
+                                         Lab=self.Lab, residx=self.residx, region=self.region, mask=mask, res_mask=self.res_mask, out=out,
                                          rows=rows, j_chunk=j_chunk, **self.kw)
 
-    def wild(self, points=None, rows=None):
-        """(1, len(DEVELOPABILITY_COLUMNS)): the row of the ground-truth antibody itself with its own atoms (a design's row minus this
-        one is what the design gained or lost)."""
-        it = self.interface
-        return self.score(it.gt_atom14[None, :self.Lab], it.gt_seq[None, :self.Lab], points=points, rows=rows, mask=it.gt_exists[None])
+    def side_outputs(self, B):
+        """want_rows: the record of the designs also carries 'developability_rows' (B, L, 4) float64."""
+        return dict(rows=self.new_rows(B)) if self.want_rows else {}
+
+    # record(): 'developability' - aggregation propensity, chain charges and sequence liabilities of the free antibody - and, with a
+    # relaxer, 'developability_relaxed'; three launches per table
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -195,7 +178,6 @@ def developability_host(x, mask, aa, Lab, chain_id, residx, cdr_def, region=None
     -> (row (len(DEVELOPABILITY_COLUMNS),) float64, rows (L,4) float64 ROW_COLUMNS); details=True adds a dict: 'sap' (L,14) int64 SAP_i
     of every counted atom (0 elsewhere), 'w' (L,14) int64 the weights, 'counted' (L,14) bool, 'exposed' (L) bool."""
     from .interface import _radius_table, interface_host
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     x = to_np(x).astype(np.float32)
     L, Lab = x.shape[0], int(Lab)
     aa = np.clip(to_np(aa).astype(np.int64), 0, 20)

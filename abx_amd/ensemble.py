@@ -9,6 +9,8 @@ On the device: `EnsembleAnalyzer` (abx_ensemble_pairs + abx_ensemble_cluster, cs
 twin; its rmsd_fit goes through `abx_amd.metrics.kabsch`."""
 import numpy as np
 
+from .complex_view import to_np
+
 # The row of abx_ensemble_cluster (include/abx_hip.h, ABX_ENS_COLS)
 ENSEMBLE_COLUMNS = ('cluster', 'is_centre', 'n_neighbours', 'rmsd_fit_mean', 'rmsd_fit_min', 'rmsd_frame_mean', 'rmsd_frame_min',
                     'seq_diff_mean', 'n_same_seq', 'first_same_seq')
@@ -132,7 +134,6 @@ def ensemble_host(x, seq, region, atoms='backbone', metric='fit', cutoff=1.0):
     point sets, then the root mean square of the aligned difference."""
     from abx_amd.metrics import kabsch
     _check(atoms, metric, cutoff)
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     x = to_np(x).astype(np.float32).astype(np.float64)
     seq = to_np(seq).astype(np.int64)
     rows = np.nonzero(to_np(region) != 0)[0]

@@ -13,6 +13,7 @@ import functools
 import numpy as np
 
 from . import complex_view
+from .complex_view import to_np
 
 # The row of abx_interface_scores (include/abx_hip.h, ABX_IFACE_COLS)
 INTERFACE_COLUMNS = ('sasa_complex', 'sasa_antibody', 'sasa_antigen', 'dsasa_int', 'dsasa_antibody', 'dsasa_region',
@@ -60,6 +61,7 @@ class InterfaceScorer(complex_view.ComplexView):
     probe: probe radius; cutoff: contact distance of heavy atoms (Angstrom)."""
 
     COLUMNS = INTERFACE_COLUMNS
+    takes_points = True                 # record(): sampler.sample_fn hands it the buffer that the SurfaceScorers built on it read
 
     def __init__(self, batch, region=None, n_points=128, probe=1.4, cutoff=4.0):
         super().__init__(batch)
@@ -77,6 +79,40 @@ class InterfaceScorer(complex_view.ComplexView):
                                     mask=mask, res_mask=self.res_mask, out=out, points=points, **self.kw)
 
     # wild(points=None): the counterpart of upstream's dG_wild - a design's row minus this one is the geometric analogue of ddG
+    # record(): 'interface' and, with a relaxer, 'interface_relaxed'; three launches each
+
+
+class SurfaceScorer(complex_view.ComplexView):
+    """The base of the scorers that read the point counts of the interface analysis (polar.PolarScorer, developability.
+    DevelopabilityScorer, shape.ShapeScorer, patches.PatchScorer): holds an InterfaceScorer of the complex and sees the complex through
+    it.  interface: an existing InterfaceScorer of the same complex (None: one is built from region, n_points and probe) -
+    `score(..., points=)` then takes the counts of ITS call for the same structures, so that the surface kernel runs once per structure
+    set: sampler.sample_fn hands one buffer to every SurfaceScorer whose `.interface` is its `interface=` scorer.  region: (L) mask of the
+    rows the `*_region` columns count (default: the interface scorer's)."""
+
+    takes_points = True
+
+    def __init__(self, batch, region, n_points, probe, interface):
+        it = self.interface = interface if interface is not None else InterfaceScorer(batch, region=region, n_points=n_points, probe=probe)
+        self.device = it.gt_atom14.device
+        self.region = it.region if region is None else complex_view.region_mask(batch, region, self.device)
+        self.Lab, self.L = it.Lab, it.L
+        self.gt_atom14, self.gt_exists, self.gt_seq, self.res_mask = it.gt_atom14, it.gt_exists, it.gt_seq, it.res_mask
+
+    def new_points(self, B):
+        """An uninitialised (B, L, 14, 2) int32 tensor for the point counts of B structures."""
+        import torch
+        return torch.empty(B, self.L, 14, 2, dtype=torch.int32, device=self.device)
+
+    def points_of(self, atom14, seq, points, mask):
+        """`points`, or (None) the counts of these structures from a call of the surface kernel here."""
+        if points is None:
+            points = self.new_points(atom14.shape[0])
+            self.interface.score(atom14, seq, points=points, mask=mask)
+        return points
+
+    # new_table(*lead), wild(**kw) - the row of the ground-truth complex itself with its own atoms: a design's row minus this one is what
+    # the design gained or lost - and record() are ComplexView's
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -94,7 +130,6 @@ def interface_host(x, mask, aa, Lab, region=None, n_points=128, probe=1.4, cutof
     -> (row (len(INTERFACE_COLUMNS),) float64, points (L,14,2) int32: acc_alone, acc_cplx of every slot).
     Neighbours by a dense float64 distance matrix (N <= 14 L atoms) with the kernel's conservative prefilter, then the point tests
     of at most `chunk` atoms at a time on flat (pair, point) arrays."""
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     x = to_np(x).astype(np.float32)
     L = x.shape[0]
     aa = np.clip(to_np(aa).astype(np.int64), 0, 20)

@@ -1280,6 +1280,20 @@ def relax(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, movable, Lab=None
     return (out, report, grad) if return_grad else (out, report)
 
 
+def _check_sphere(sphere, dev):
+    assert sphere.dtype == torch.float64 and sphere.dim() == 2 and sphere.shape[1] == 3 and sphere.is_contiguous() and sphere.device == dev, \
+        'sphere: (P,3) float64 on the device of atom14'
+
+
+def _workspace(workspace, need, dev):
+    """The caller's workspace, checked, or (None) one of `need` bytes allocated here."""
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
+        f'workspace: at least {need} uint8 on the device of atom14'
+    return workspace
+
+
 def interface_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, Lab=None, region=None, mask=None, res_mask=None, probe=1.4,
                      cutoff=4.0, out=None, points=None):
     """Interface analysis of B structures of one complex (abx_interface_scores; columns: abx_amd.interface.INTERFACE_COLUMNS): buried
@@ -1293,8 +1307,7 @@ def interface_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, Lab=None
     lib = _lib.load()
     dev = atom14.device
     L = gt_seq.shape[-1]
-    assert sphere.dtype == torch.float64 and sphere.dim() == 2 and sphere.shape[1] == 3 and sphere.is_contiguous() and sphere.device == dev, \
-        'sphere: (P,3) float64 on the device of atom14'
+    _check_sphere(sphere, dev)
     a = AbxInterfaceArgs()
     B, _, _, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region)
     a.sphere, a.P = _p(sphere), int(sphere.shape[0])
@@ -1390,8 +1403,7 @@ def shape_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, points, Lab=
     lib = _lib.load()
     dev = atom14.device
     L = gt_seq.shape[-1]
-    assert sphere.dtype == torch.float64 and sphere.dim() == 2 and sphere.shape[1] == 3 and sphere.is_contiguous() and sphere.device == dev, \
-        'sphere: (P,3) float64 on the device of atom14'
+    _check_sphere(sphere, dev)
     a = AbxShapeArgs()
     B, _, _, own, keep = _structure_args(a, atom14, seq, L, Lab, gt_atom14, gt_seq, gt_exists, mask, res_mask, region)
     a.sphere, a.P = _p(sphere), int(sphere.shape[0])
@@ -1400,10 +1412,7 @@ def shape_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, sphere, points, Lab=
     a.probe, a.trim, a.weight, a.max_dots, a.j_chunk = float(probe), float(trim), float(weight), int(max_dots), int(j_chunk)
     out = _out_rows(a, out, B, _lib.SHAPE_COLS, dev)
     need = int(lib.abx_shape_scores_workspace_bytes(B, L, a.P, a.max_dots))
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
-        f'workspace: at least {need} uint8 on the device of atom14'
+    workspace = _workspace(workspace, need, dev)
     check(lib.abx_shape_scores(C.byref(a), _p(workspace), _stream()), 'abx_shape_scores')
     return out
 
@@ -1450,10 +1459,7 @@ def patch_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, cdr_def, t
     out = _out_rows(a, out, B, _lib.PATCH_COLS, dev)
     _side_output(a, 'rows', rows, torch.float64, (B, L, 4))
     need = int(lib.abx_patch_scores_workspace_bytes(B, L, Lab))
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
-        f'workspace: at least {need} uint8 on the device of atom14'
+    workspace = _workspace(workspace, need, dev)
     check(lib.abx_patch_scores(C.byref(a), _p(workspace), _stream()), 'abx_patch_scores')
     return out
 
@@ -1494,10 +1500,7 @@ def torsion_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, residx, 
     _side_output(a, 'rows', rows, torch.float64, (B, Lab, 8))
     _side_output(a, 'classes', classes, torch.int32, (B, Lab))
     need = int(lib.abx_torsion_scores_workspace_bytes(B, Lab))
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
-        f'workspace: at least {need} uint8 on the device of atom14'
+    workspace = _workspace(workspace, need, dev)
     check(lib.abx_torsion_scores(C.byref(a), _p(workspace), _stream()), 'abx_torsion_scores')
     return out
 
@@ -1533,10 +1536,7 @@ def secondary_scores(atom14, seq, gt_atom14, gt_seq, gt_exists, chain_id, residx
     _side_output(a, 'rows', rows, torch.int32, (B, Lab, 6))
     _side_output(a, 'classes', classes, torch.int32, (B, Lab))
     need = int(lib.abx_secondary_scores_workspace_bytes(B, Lab))
-    if workspace is None:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev and workspace.numel() >= need, \
-        f'workspace: at least {need} uint8 on the device of atom14'
+    workspace = _workspace(workspace, need, dev)
     check(lib.abx_secondary_scores(C.byref(a), _p(workspace), _stream()), 'abx_secondary_scores')
     return out
 

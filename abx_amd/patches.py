@@ -18,6 +18,8 @@ import functools
 import numpy as np
 
 from . import complex_view
+from .complex_view import to_np
+from .interface import SurfaceScorer
 from .developability import CDR_CODES, FIXED_ONE, side_chain_area, weight_table
 
 # The row of abx_patch_scores (include/abx_hip.h, ABX_PATCH_COLS)
@@ -66,51 +68,35 @@ def gly_type():
     return rc.restypes.index('G')
 
 
-class PatchScorer:
+class PatchScorer(SurfaceScorer):
     """Patch rows of batches of designs of ONE complex on the device.  Built once per complex from its featurised batch (or the
-    un-batched complex) like developability.DevelopabilityScorer, and holds an InterfaceScorer for the point counts.  region: (L) mask
-    of the rows the `*_region` columns count (default: the rows the sampler diffuses).  cutoff: of a patch pair and of a cross pair,
+    un-batched complex) like developability.DevelopabilityScorer, and holds an InterfaceScorer for the point counts
+    (interface.SurfaceScorer: region, n_points / probe of the surface, interface).  cutoff: of a patch pair and of a cross pair,
     vicinity: of a CDR residue, salt: of a salt bridge (closest heavy-atom distances, Angstrom); exposed: smallest relative side-chain
-    area of an exposed residue (Gly and X are never exposed); n_points / probe: of the surface.  interface: an existing InterfaceScorer
-    of the same complex - `score(..., points=)` then takes the counts of ITS call for the same structures, so that the surface kernel
-    runs once per structure set."""
+    area of an exposed residue (Gly and X are never exposed)."""
 
-    want_rows = False                   # set on an instance: sampler.sample_fn also records 'patches_rows'
+    COLUMNS = PATCHES_COLUMNS
 
     def __init__(self, batch, region=None, cutoff=7.5, vicinity=4.0, salt=3.2, exposed=0.075, n_points=128, probe=1.4, interface=None):
         import torch
-        from .interface import InterfaceScorer
         from .polar import polar_table_on
         if not (cutoff > 0 and vicinity > 0 and salt > 0 and 0.0 <= exposed <= 1.0):
             raise ValueError(f'patches: needs cutoff, vicinity and salt > 0 and exposed in [0, 1] (got {cutoff}, {vicinity}, {salt}, {exposed})')
-        self.interface = interface if interface is not None else InterfaceScorer(batch, region=region, n_points=n_points, probe=probe)
-        it = self.interface
-        dev = it.gt_atom14.device
-        self.region = it.region if region is None else complex_view.region_mask(batch, region, dev)
-        self.Lab, self.L = it.Lab, int(it.gt_seq.shape[0])
+        super().__init__(batch, region, n_points, probe, interface)
+        dev = self.device
         view = complex_view.ComplexView(batch, chains=True, cdr=True)
         self.chain_id, self.cdr_def = view.chain_id, view.cdr_def
-        P, probe = int(it.sphere.shape[0]), it.kw['probe']
-        _, a, ref = weight_table(P, probe)
+        _, a, ref = weight_table(int(self.interface.sphere.shape[0]), self.interface.kw['probe'])
         h, q10 = kyte_doolittle(), charge_table()
         # (copies: the cached tables are read-only)
         self.tables = tuple(torch.from_numpy(np.array(t)).to(dev) for t in (h, q10.astype(np.int32), a, ref)) + (polar_table_on(dev),)
         self.kw = dict(cutoff=float(cutoff), vicinity=float(vicinity), salt=float(salt), exposed=float(exposed),
                        h_max=float(np.abs(h).max()), q_max=int(np.abs(q10).max()), gly=gly_type())
 
-    def new_table(self, *lead):
-        """An uninitialised (*lead, len(PATCHES_COLUMNS)) float64 table on the complex's device for `score(..., out=table[i])`."""
-        return complex_view.new_table(PATCHES_COLUMNS, self.region.device, *lead)
-
-    def new_points(self, B):
-        """An uninitialised (B, L, 14, 2) int32 tensor for the point counts of B structures."""
-        import torch
-        return torch.empty(B, self.L, 14, 2, dtype=torch.int32, device=self.region.device)
-
     def new_rows(self, B):
         """An uninitialised (B, L, 4) float64 tensor for ROW_COLUMNS of B structures."""
         import torch
-        return torch.empty(B, self.L, 4, dtype=torch.float64, device=self.region.device)
+        return torch.empty(B, self.L, 4, dtype=torch.float64, device=self.device)
 
     def score(self, atom14, seq, out=None, points=None, rows=None, mask=None, workspace=None):
         """atom14 (B, Lab or L, 14, 3) f32 predicted coordinates, seq (B, Lab) tokens -> (B, len(PATCHES_COLUMNS)) float64 on the device;
@@ -118,19 +104,17 @@ class PatchScorer:
         int32 acc_alone / acc_cplx that the interface scorer returned for THESE structures (None: its kernel runs here); workspace: a
         uint8 tensor of at least ops.patch_workspace_bytes(B, L, Lab) bytes (None: allocated here).  No host synchronisation."""
         from abx_amd import ops
-        it = self.interface
-        if points is None:
-            points = self.new_points(atom14.shape[0])
-            it.score(atom14, seq, points=points, mask=mask)
-        return ops.patch_scores(atom14, seq, it.gt_atom14, it.gt_seq, it.gt_exists, self.chain_id, self.cdr_def, self.tables, points,
-                                Lab=self.Lab, region=self.region, mask=mask, res_mask=it.res_mask, out=out, rows=rows,
+        points = self.points_of(atom14, seq, points, mask)
+        return ops.patch_scores(atom14, seq, self.gt_atom14, self.gt_seq, self.gt_exists, self.chain_id, self.cdr_def, self.tables, points,
+                                Lab=self.Lab, region=self.region, mask=mask, res_mask=self.res_mask, out=out, rows=rows,
                                 workspace=workspace, **self.kw)
 
-    def wild(self, points=None, rows=None):
-        """(1, len(PATCHES_COLUMNS)): the row of the ground-truth complex itself with its own atoms (a design's row minus this one is
-        what the design gained or lost)."""
-        it = self.interface
-        return self.score(it.gt_atom14[None, :self.Lab], it.gt_seq[None, :self.Lab], points=points, rows=rows, mask=it.gt_exists[None])
+    def side_outputs(self, B):
+        """want_rows: the record of the designs also carries 'patches_rows' (B, L, 4) float64."""
+        return dict(rows=self.new_rows(B)) if self.want_rows else {}
+
+    # record(): 'patches' - the patches of surface hydrophobicity and charge around the CDRs of the free antibody, its charge symmetry,
+    # the charge pairing across the interface - and, with a relaxer, 'patches_relaxed'; three launches per table
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -169,7 +153,6 @@ def patches_host(x, mask, aa, Lab, chain_id, residx, cdr_def, region=None, point
     'present' (L) and 'exposed', 'seed', 'vicinity', 'salt' (Lab) bool."""
     from .interface import _radius_table, interface_host
     from .polar import polar_table
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     x = to_np(x).astype(np.float32)
     L, Lab = x.shape[0], int(Lab)
     aa = np.clip(to_np(aa).astype(np.int64), 0, 20)

@@ -14,7 +14,8 @@ import math
 import numpy as np
 
 from . import complex_view
-from .interface import FOUR_PI
+from .complex_view import to_np
+from .interface import FOUR_PI, SurfaceScorer
 
 # The row of abx_polar_scores (include/abx_hip.h, ABX_POLAR_COLS)
 POLAR_COLUMNS = ('n_hbond_int', 'n_hbond_int_bb', 'n_hbond_region', 'n_hbond_intra_region', 'n_salt_int', 'n_salt_region', 'n_polar_int',
@@ -85,36 +86,22 @@ format_polar = functools.partial(complex_view.format_row, POLAR_COLUMNS, COUNT_C
 format_delta = functools.partial(complex_view.format_delta, POLAR_COLUMNS, COUNT_COLUMNS, DELTA_COLUMNS, 2)
 
 
-class PolarScorer:
+class PolarScorer(SurfaceScorer):
     """Polar rows of batches of designs of ONE complex on the device.  Built once per complex from its featurised batch (or the
-    un-batched complex) like interface.InterfaceScorer, and holds one for the point counts.  region: (L) mask of the rows the `*_region`
-    columns count (default: the rows the sampler diffuses).  hb_min / hb_max: donor - acceptor distance range (Angstrom); hb_angle:
-    smallest antecedent - atom ... partner angle (degrees, [90, 180)); salt: cation - anion distance; n_points / probe: of the surface.
-    interface: an existing InterfaceScorer of the same complex - `score(..., points=)` then takes the counts of ITS call for the same
-    structures, so that the surface kernel runs once per structure set."""
+    un-batched complex) like interface.InterfaceScorer, and holds one for the point counts (interface.SurfaceScorer: region, n_points /
+    probe of the surface, interface).  hb_min / hb_max: donor - acceptor distance range (Angstrom); hb_angle: smallest antecedent - atom
+    ... partner angle (degrees, [90, 180)); salt: cation - anion distance."""
 
-    want_rows = False                   # set on an instance: sampler.sample_fn also records 'polar_bonds' and 'polar_rows'
+    COLUMNS = POLAR_COLUMNS
 
     def __init__(self, batch, region=None, hb_min=2.0, hb_max=3.5, hb_angle=90.0, salt=4.0, n_points=128, probe=1.4, interface=None):
-        from .interface import InterfaceScorer
         if not (0 <= hb_min <= hb_max and 90.0 <= hb_angle < 180.0 and salt >= 0):
             raise ValueError(f'polar: needs 0 <= hb_min <= hb_max, 90 <= hb_angle < 180, salt >= 0 (got {hb_min}, {hb_max}, {hb_angle}, {salt})')
-        self.interface = interface if interface is not None else InterfaceScorer(batch, region=region, n_points=n_points, probe=probe)
+        super().__init__(batch, region, n_points, probe, interface)
         it = self.interface
-        self.region = it.region if region is None else complex_view.region_mask(batch, region, it.gt_atom14.device)
-        self.Lab, self.L = it.Lab, int(it.gt_seq.shape[0])
-        self.table = polar_table_on(it.gt_atom14.device)
+        self.table = polar_table_on(self.device)
         self.kw = dict(hb_min=float(hb_min), hb_max=float(hb_max), hb_angle=float(hb_angle), salt=float(salt),
                        n_points=int(it.sphere.shape[0]), probe=it.kw['probe'])
-
-    def new_table(self, *lead):
-        """An uninitialised (*lead, len(POLAR_COLUMNS)) float64 table on the complex's device for `score(..., out=table[i])`."""
-        return complex_view.new_table(POLAR_COLUMNS, self.table.device, *lead)
-
-    def new_points(self, B):
-        """An uninitialised (B, L, 14, 2) int32 tensor for the point counts of B structures."""
-        import torch
-        return torch.empty(B, self.L, 14, 2, dtype=torch.int32, device=self.table.device)
 
     def score(self, atom14, seq, out=None, bonds=None, points=None, rows=None, mask=None):
         """atom14 (B, Lab or L, 14, 3) f32 predicted coordinates, seq (B, Lab) tokens -> (B, len(POLAR_COLUMNS)) float64 on the device;
@@ -122,18 +109,20 @@ class PolarScorer:
         rows: (B,L,4) int32 to receive ROW_COLUMNS of every residue; points: the (B,L,14,2) int32 acc_alone / acc_cplx that the
         interface scorer returned for THESE structures (None: its kernel runs here).  No host synchronisation."""
         from abx_amd import ops
-        it = self.interface
-        if points is None:
-            points = self.new_points(atom14.shape[0])
-            it.score(atom14, seq, points=points, mask=mask)
-        return ops.polar_scores(atom14, seq, it.gt_atom14, it.gt_seq, it.gt_exists, self.table, Lab=self.Lab, region=self.region, mask=mask,
-                                res_mask=it.res_mask, points=points, out=out, bonds=bonds, rows=rows, **self.kw)
+        points = self.points_of(atom14, seq, points, mask)
+        return ops.polar_scores(atom14, seq, self.gt_atom14, self.gt_seq, self.gt_exists, self.table, Lab=self.Lab, region=self.region, mask=mask,
+                                res_mask=self.res_mask, points=points, out=out, bonds=bonds, rows=rows, **self.kw)
 
-    def wild(self, bonds=None, points=None, rows=None):
-        """(1, len(POLAR_COLUMNS)): the row of the ground-truth complex itself with its own atoms (a design's row minus this one is what
-        the design gained or lost)."""
-        it = self.interface
-        return self.score(it.gt_atom14[None, :self.Lab], it.gt_seq[None, :self.Lab], bonds=bonds, points=points, rows=rows, mask=it.gt_exists[None])
+    def side_outputs(self, B):
+        """want_rows: the record of the designs also carries 'polar_bonds' (B, L, 14, 2) and 'polar_rows' (B, L, 4) int32."""
+        import torch
+        if not self.want_rows:
+            return {}
+        return dict(bonds=torch.empty(B, self.L, 14, 2, dtype=torch.int32, device=self.device),
+                    rows=torch.empty(B, self.L, 4, dtype=torch.int32, device=self.device))
+
+    # record(): 'polar' - hydrogen bonds and salt bridges across the interface, polar atoms buried without a partner - and, with a
+    # relaxer, 'polar_relaxed'; one launch per table
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -177,7 +166,6 @@ def polar_host(x, mask, aa, Lab, region=None, points=None, hb_min=2.0, hb_max=3.
     -> (row (len(POLAR_COLUMNS),) float64, bonds (L,14,2) int32: same-side, cross-side bonds of every slot); details=True adds a dict:
     'pairs' [(row_a, slot_a, row_b, slot_b), ...] the bonds, 'salt' [(row, row), ...], 'rows' (L,4) int32 ROW_COLUMNS."""
     from .interface import _radius_table, interface_host
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     x = to_np(x).astype(np.float32)
     L = x.shape[0]
     aa = np.clip(to_np(aa).astype(np.int64), 0, 20)

@@ -39,55 +39,19 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     relaxer: None, or an abx_amd.relax.ViolationRelaxer of the complex: the LAST record (the designs; the earlier records of trajectory
     mode are noisy states) gets 'atom14_relaxed' (B,Lab,14,3) and 'relax' (B, len(relax.RELAX_COLUMNS)) float64, and with a scorer
     'scores_relaxed'; 'atom14_results' is left as it is.  One launch, outside any captured step, no host synchronisation.
-    interface: None, or an abx_amd.interface.InterfaceScorer of the complex: the LAST record gets 'interface' (B, len(interface.
-    INTERFACE_COLUMNS)) float64 - buried surface, interface residues, antibody-antigen contacts of the designs - and with a relaxer
-    'interface_relaxed' of the relaxed structures.  Three launches each, outside any captured step, no host synchronisation.
-    confidence: None, or an abx_amd.confidence.DistogramScorer of the complex: the LAST record (in trajectory mode too) gets 'confidence'
-    (B, len(confidence.CONFIDENCE_COLUMNS)) float64 and 'confidence_rows' (B, L, 4) - the distogram head of the last network call
-    against the designs it emitted - 'confidence_wild' (the input complex's own coordinates against the same predictions), with a
-    relaxer 'confidence_relaxed', and with `confidence.want_planes` 'confidence_planes' = (p_contact, exp_dist).  The scorer reads
-    out['representations']['pair'] right after the last model call (the next call overwrites that buffer: model/abx.py:16-18); two
-    launches per table, outside any captured step, no host synchronisation.
-    accuracy: None, or an abx_amd.accuracy.AccuracyScorer of the complex: the LAST record gets 'accuracy' (B, len(accuracy.
-    ACCURACY_COLUMNS)) float64 - lDDT, TM-score / GDT and native-contact recovery of the designs against the crystal structure, and the
-    calibration of the per-residue pLDDT of the last network call (before it is averaged into the record's 'pLDDT') - 'accuracy_rows'
-    (B, L, 4) per residue, and with a relaxer 'accuracy_relaxed'.  Two launches per table, outside any captured step, no host
-    synchronisation.
-    polar: None, or an abx_amd.polar.PolarScorer of the complex: the LAST record gets 'polar' (B, len(polar.POLAR_COLUMNS)) float64 -
-    hydrogen bonds and salt bridges across the interface, polar atoms buried without a partner - with a relaxer 'polar_relaxed', and
-    with `polar.want_rows` 'polar_bonds' (B, L, 14, 2) and 'polar_rows' (B, L, 4) int32 of the designs.  When `interface` is the
-    scorer's own InterfaceScorer, its point counts serve both tables: the surface kernel runs once per structure set.  One launch per
-    table, outside any captured step, no host synchronisation.
+    interface, polar, developability, shape, patches, torsions, secondary, confidence, accuracy: each None (the records have exactly
+    today's keys and bits), or the scorer of the complex from the module of that name (InterfaceScorer, PolarScorer, DevelopabilityScorer,
+    ShapeScorer, PatchScorer, TorsionScorer, SecondaryScorer, DistogramScorer, AccuracyScorer).  The LAST record (in trajectory mode too)
+    gets under the keyword a (B, len(COLUMNS)) float64 table of the designs, with a relaxer under '<keyword>_relaxed' that of the relaxed
+    structures, and the side outputs of the designs that the scorer's `record` method names (the per-residue tables of `want_rows` /
+    `want_planes` among them).  They run in the order above, each on the designs and then on the relaxed structures: launches only,
+    outside any captured step, no host synchronisation.  The interface.SurfaceScorer classes (polar, developability, shape, patches)
+    built on the `interface=` scorer read ITS point counts: the surface kernel then runs once per structure set for all of them.
     constraints: None (the reference's unconstrained sampler, bit-identical code path, the records have exactly today's keys) or an
     abx_amd.constraints.SequenceConstraints of the complex: its (L,20) table goes into this call's copy of the batch as 'seq_bias' (the
     masked argmax of every network pass), a designed residue's forbidden start token is projected onto the nearest allowed letter before
     the warm-up call, and every reverse step reads the table (no rate towards a forbidden letter, a leap onto one is rejected).  The
-    table's address is static, so a captured step stays replayable.
-    developability: None (the records have exactly today's keys and bits), or an abx_amd.developability.DevelopabilityScorer of the
-    complex: the LAST record gets 'developability' (B, len(developability.DEVELOPABILITY_COLUMNS)) float64 - aggregation propensity,
-    chain charges and sequence liabilities of the free antibody - with a relaxer 'developability_relaxed', and with
-    `developability.want_rows` 'developability_rows' (B, L, 4) float64 of the designs.  It shares the point counts of `interface` like
-    `polar`: with all three the surface kernel still runs once per structure set.  Three launches per table, outside any captured step,
-    no host synchronisation.
-    shape: None (the records have exactly today's keys and bits), or an abx_amd.shape.ShapeScorer of the complex: the LAST record gets
-    'shape' (B, len(shape.SHAPE_COLUMNS)) float64 - the shape complementarity Sc of the interface, both directions, the designed
-    residues' dots, the gaps and the dot counts - and with a relaxer 'shape_relaxed'.  It shares the point counts of `interface` like
-    `polar` and `developability`.  Five launches per table, outside any captured step, no host synchronisation.
-    patches: None (the records have exactly today's keys and bits), or an abx_amd.patches.PatchScorer of the complex: the LAST record
-    gets 'patches' (B, len(patches.PATCHES_COLUMNS)) float64 - the patches of surface hydrophobicity and charge around the CDRs of the
-    free antibody, its charge symmetry, the charge pairing across the interface - with a relaxer 'patches_relaxed', and with
-    `patches.want_rows` 'patches_rows' (B, L, 4) float64 of the designs.  It shares the point counts of `interface` like `polar`,
-    `developability` and `shape`.  Three launches per table, outside any captured step, no host synchronisation.
-    torsions: None (the records have exactly today's keys and bits), or an abx_amd.torsions.TorsionScorer of the complex: the LAST record
-    gets 'torsions' (B, len(torsions.TORSIONS_COLUMNS)) float64 - cis and twisted peptides, phi >= 0, the ABEGO classes, the backbone
-    dihedrals and the chi angles against the crystal structure - and 'torsions_classes' (B, Lab) int32, the ABEGO codes; with a relaxer
-    'torsions_relaxed', and with `torsions.want_rows` 'torsions_rows' (B, Lab, 8) float64 of the designs.  One launch per table, outside
-    any captured step, no host synchronisation.
-    secondary: None (the records have exactly today's keys and bits), or an abx_amd.secondary.SecondaryScorer of the complex: the LAST
-    record gets 'secondary' (B, len(secondary.SECONDARY_COLUMNS)) float64 - DSSP's backbone hydrogen bonds, bridges and states of the
-    antibody against the crystal structure - and 'secondary_classes' (B, Lab) int32, the states; with a relaxer 'secondary_relaxed',
-    and with `secondary.want_rows` 'secondary_rows' (B, Lab, 6) int32 of the designs.  One launch per table, outside any captured
-    step, no host synchronisation."""
+    table's address is static, so a captured step stays replayable."""
     model_conf = config.model
     sc_conf = model_conf.heads.diffusion_module
     batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_init.items()}
@@ -109,6 +73,8 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
         seq_bias = batch['seq_bias'] = constraints.table.to(device)
         batch['seq_t'] = constraints.project(batch['seq_t'], diffuse_mask)
     log_start = len(getattr(model, 'range_log', None) or [])     # (the model's range log is cumulative: report this trajectory's part)
+    scorers = {k: v for k, v in dict(interface=interface, polar=polar, developability=developability, shape=shape, patches=patches,
+                                     torsions=torsions, secondary=secondary, confidence=confidence, accuracy=accuracy).items() if v is not None}
     traj = []
     score_table = scorer.new_table(len(steps) if mode == 'trajectory' else 1, B) if scorer is not None else None
     with torch.no_grad():
@@ -158,7 +124,7 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
                 if scorer is not None:
                     traj[-1]['scores'] = scorer.score(rec['atom14_results'], rec['seq'], out=score_table[len(traj) - 1])
                 if k == len(steps) - 1:
-                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability, shape, patches, torsions, secondary)
+                    _analyse_last(traj[-1], out, pl_res, scorer, relaxer, scorers)
                 if on_record is not None:
                     # finiteness before a file is written: on the first record, every 10th and the last one (a host synchronisation each;
                     # an out-of-range activation never gets here: ScoreNetwork repeats that pass on the exact kernels)
@@ -180,78 +146,28 @@ def sample_fn(data_init, config, diffuser, model, mode='design', num_t=100, min_
     return traj
 
 
-def _analyse_last(rec, out, pl_res, scorer, relaxer, interface, confidence, accuracy, polar, developability=None, shape=None, patches=None, torsions=None,
-                  secondary=None):
+def _analyse_last(rec, out, pl_res, scorer, relaxer, scorers):
     """What the analyses of sample_fn add to the LAST record, from the model's output `out` of the call that made it and its per-residue
-    pLDDT, each on the design and, with a relaxer, on the relaxed structure.  Launches only, no host synchronisation."""
+    pLDDT.  scorers: {keyword: scorer} in the order they run; each one's `record` method (complex_view.ComplexView.record) is called on the
+    design and, with a relaxer, on the relaxed structure.  A scorer that SurfaceScorers of the mapping are built on fills one buffer of
+    point counts per structure set, which they read; any other SurfaceScorer gets None and runs the surface kernel itself.  Launches only,
+    no host synchronisation."""
+    from abx_amd.interface import SurfaceScorer
     x, seq, B = rec['atom14_results'], rec['seq'], rec['seq'].shape[0]
+    structures = [('', x)]
     if relaxer is not None:
         rec['atom14_relaxed'], rec['relax'] = relaxer.relax(x, seq)
         if scorer is not None:
             rec['scores_relaxed'] = scorer.score(rec['atom14_relaxed'], seq)
-    pts = pts_relaxed = None                                    # point counts of the interface call, when a later scorer shares it
-    if interface is not None:
-        sharing = [sc for sc in (polar, developability, shape, patches) if sc is not None and sc.interface is interface]
-        if sharing:
-            pts = sharing[0].new_points(B)
-            pts_relaxed = sharing[0].new_points(B) if relaxer is not None else None
-        rec['interface'] = interface.score(x, seq, points=pts)
-        if relaxer is not None:
-            rec['interface_relaxed'] = interface.score(rec['atom14_relaxed'], seq, points=pts_relaxed)
-    if polar is not None:
-        if polar.want_rows:
-            rec['polar_bonds'] = torch.empty(B, polar.L, 14, 2, dtype=torch.int32, device=x.device)
-            rec['polar_rows'] = torch.empty(B, polar.L, 4, dtype=torch.int32, device=x.device)
-        shared = polar.interface is interface
-        rec['polar'] = polar.score(x, seq, points=pts if shared else None, bonds=rec.get('polar_bonds'), rows=rec.get('polar_rows'))
-        if relaxer is not None:
-            rec['polar_relaxed'] = polar.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
-    if developability is not None:
-        shared = developability.interface is interface
-        if developability.want_rows:
-            rec['developability_rows'] = developability.new_rows(B)
-        rec['developability'] = developability.score(x, seq, points=pts if shared else None, rows=rec.get('developability_rows'))
-        if relaxer is not None:
-            rec['developability_relaxed'] = developability.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
-    if shape is not None:
-        shared = shape.interface is interface
-        rec['shape'] = shape.score(x, seq, points=pts if shared else None)
-        if relaxer is not None:
-            rec['shape_relaxed'] = shape.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
-    if patches is not None:
-        shared = patches.interface is interface
-        if patches.want_rows:
-            rec['patches_rows'] = patches.new_rows(B)
-        rec['patches'] = patches.score(x, seq, points=pts if shared else None, rows=rec.get('patches_rows'))
-        if relaxer is not None:
-            rec['patches_relaxed'] = patches.score(rec['atom14_relaxed'], seq, points=pts_relaxed if shared else None)
-    if torsions is not None:
-        if torsions.want_rows:
-            rec['torsions_rows'] = torsions.new_rows(B)
-        rec['torsions_classes'] = torsions.new_classes(B)
-        rec['torsions'] = torsions.score(x, seq, rows=rec.get('torsions_rows'), classes=rec['torsions_classes'])
-        if relaxer is not None:
-            rec['torsions_relaxed'] = torsions.score(rec['atom14_relaxed'], seq)
-    if secondary is not None:
-        if secondary.want_rows:
-            rec['secondary_rows'] = secondary.new_rows(B)
-        rec['secondary_classes'] = secondary.new_classes(B)
-        rec['secondary'] = secondary.score(x, seq, rows=rec.get('secondary_rows'), classes=rec['secondary_classes'])
-        if relaxer is not None:
-            rec['secondary_relaxed'] = secondary.score(rec['atom14_relaxed'], seq)
-    if confidence is not None:
-        pair = out['representations']['pair']                   # of the call just made: nothing between it and here runs the network
-        got = confidence.score(pair, x, seq, planes=bool(confidence.want_planes))
-        rec['confidence'], rec['confidence_rows'] = got[0], got[1]
-        if len(got) > 2:
-            rec['confidence_planes'] = got[2]
-        rec['confidence_wild'] = confidence.wild(pair)[0]
-        if relaxer is not None:
-            rec['confidence_relaxed'] = confidence.score(pair, rec['atom14_relaxed'], seq)[0]
-    if accuracy is not None:
-        rec['accuracy'], rec['accuracy_rows'] = accuracy.score(x, seq, plddt=pl_res, rows=True)[:2]
-        if relaxer is not None:
-            rec['accuracy_relaxed'] = accuracy.score(rec['atom14_relaxed'], seq, plddt=pl_res)
+        structures.append(('_relaxed', rec['atom14_relaxed']))
+    points = {}                                                 # id of the scorer that fills them -> the buffer of every structure set
+    for key, sc in scorers.items():
+        users = [u for u in scorers.values() if isinstance(u, SurfaceScorer) and u.interface is sc]
+        if users:
+            points[id(sc)] = [users[0].new_points(B) for _ in structures]
+        source = sc.interface if isinstance(sc, SurfaceScorer) else sc
+        for (suffix, atoms), pts in zip(structures, points.get(id(source), [None] * len(structures))):
+            sc.record(rec, key + suffix, atoms, seq, design=not suffix, points=pts, out=out, plddt=pl_res)
 
 
 def check_finite(*tensors, what='the end of the trajectory'):

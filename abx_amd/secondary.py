@@ -24,6 +24,7 @@ import functools
 import numpy as np
 
 from . import complex_view
+from .complex_view import Borderline as _Borderline, to_np, type_index
 
 # The row of abx_secondary_scores (include/abx_hip.h, ABX_SECONDARY_COLS)
 SECONDARY_COLUMNS = ('n_hb', 'n_hb_region', 'n_hb_inside', 'hb_wild_region', 'hb_kept_region', 'hb_energy_region', 'n_bridge_region',
@@ -63,11 +64,6 @@ def thresholds(hb_energy=-0.5):
     return dict(hb_energy=hb_energy, bend=(float(np.cos(r)), float(np.sin(r))))
 
 
-def type_index(letter):
-    from . import residue_constants as rc
-    return rc.restypes.index(letter)
-
-
 def ss_string(classes, region):
     """The state letters of the rows of `region` (a mask over the rows of `classes`, or longer)."""
     cl = np.asarray(classes).astype(np.int64)
@@ -81,7 +77,6 @@ class SecondaryScorer(complex_view.ComplexView):
     (default: the rows the sampler diffuses).  hb_energy: the energy below which a bond counts, kcal/mol, < 0."""
 
     COLUMNS = SECONDARY_COLUMNS
-    want_rows = False                   # set on an instance: sampler.sample_fn also records 'secondary_rows'
 
     def __init__(self, batch, region=None, hb_energy=-0.5):
         super().__init__(batch, chains=True)
@@ -110,24 +105,20 @@ class SecondaryScorer(complex_view.ComplexView):
                                     region=self.region, mask=mask, res_mask=self.res_mask, out=out, rows=rows, classes=classes,
                                     workspace=workspace, **self.kw)
 
+    def side_outputs(self, B):
+        """The record of the designs also carries 'secondary_classes' (B, Lab) int32, the states, and with want_rows 'secondary_rows'
+        (B, Lab, 6) int32."""
+        return dict({'rows': self.new_rows(B)} if self.want_rows else {}, classes=self.new_classes(B))
+
     # wild(**kw): the crystal structure against itself - hb_kept_region == hb_wild_region == n_hb_region, q8_same == n_ss: the first
     # line of the driver's table
+    # record(): 'secondary' - DSSP's backbone hydrogen bonds, bridges and states of the antibody against the crystal structure - and,
+    # with a relaxer, 'secondary_relaxed'; one launch per table
 
 
 # -------------------------------------------------------------------------------------------------------------------
 # host twin (float64, numpy)
 # -------------------------------------------------------------------------------------------------------------------
-class _Borderline:
-    """Counts the decisions `lhs ? rhs` whose two sides differ by less than 1e-9 relative (of the size of the operands)."""
-
-    def __init__(self):
-        self.n = 0
-
-    def __call__(self, lhs, rhs, scale, where=True):
-        near = np.abs(lhs - rhs) < 1e-9 * np.maximum(np.abs(scale), 1e-300)
-        self.n += int(np.count_nonzero(near & where))
-
-
 def _norm(d):
     """sqrt((dx*dx + dy*dy) + dz*dz) over the last axis, the bracketing of csrc/secondary.hip::norm3."""
     return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
@@ -261,7 +252,6 @@ def secondary_host(x, mask, aa, gt_x, gt_mask, gt_aa, Lab, chain_id, residx=None
             than 1e-9 relative: those a device evaluation could take differently).
     mistake: None, or the name of a deliberate error the tests show a column or a string for (MISTAKES)."""
     assert mistake is None or mistake in MISTAKES, mistake
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     Lab = int(Lab)
     keep = np.ones(Lab, bool) if res_mask is None else (to_np(res_mask)[:Lab] != 0)
     xd = to_np(x)[:Lab].astype(np.float32).astype(np.float64)

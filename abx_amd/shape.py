@@ -17,6 +17,8 @@ import functools
 import numpy as np
 
 from . import complex_view
+from .complex_view import to_np
+from .interface import SurfaceScorer
 
 # The row of abx_shape_scores (include/abx_hip.h, ABX_SHAPE_COLS)
 SHAPE_COLUMNS = ('sc', 'sc_antibody', 'sc_antigen', 'sc_region', 'gap_antibody', 'gap_antigen', 'n_dots_antibody', 'n_dots_antigen',
@@ -32,33 +34,20 @@ format_shape = functools.partial(complex_view.format_row, SHAPE_COLUMNS, COUNT_C
 format_delta = functools.partial(complex_view.format_delta, SHAPE_COLUMNS, COUNT_COLUMNS, DELTA_COLUMNS, PLACES)
 
 
-class ShapeScorer:
+class ShapeScorer(SurfaceScorer):
     """Shape-complementarity rows of batches of designs of ONE complex on the device.  Built once per complex from its featurised batch
-    (or the un-batched complex) like developability.DevelopabilityScorer, and holds an InterfaceScorer for the point counts.  region:
-    (L) mask of the rows `sc_region` / `n_dots_region` count (default: the rows the sampler diffuses).  trim: width of the peripheral band
-    that is dropped (Angstrom); weight: of the squared distance in the exponent (1 / square Angstrom); n_points / probe: of the surface;
-    max_dots: capacity of each of the four dot lists of a structure - a structure beyond it gets a row of -1.  interface: an existing
-    InterfaceScorer of the same complex - `score(..., points=)` then takes the counts of ITS call for the same structures, so that the
-    surface kernel runs once per structure set."""
+    (or the un-batched complex) like developability.DevelopabilityScorer, and holds an InterfaceScorer for the point counts
+    (interface.SurfaceScorer: region - the rows `sc_region` / `n_dots_region` count -, n_points / probe of the surface, interface).
+    trim: width of the peripheral band that is dropped (Angstrom); weight: of the squared distance in the exponent (1 / square Angstrom);
+    max_dots: capacity of each of the four dot lists of a structure - a structure beyond it gets a row of -1."""
+
+    COLUMNS = SHAPE_COLUMNS
 
     def __init__(self, batch, region=None, trim=1.5, weight=0.5, n_points=128, probe=1.4, max_dots=8192, interface=None):
-        from .interface import InterfaceScorer
         if not (trim >= 0 and weight >= 0 and int(max_dots) >= 1):
             raise ValueError(f'shape: needs trim >= 0, weight >= 0 and max_dots >= 1 (got {trim}, {weight}, {max_dots})')
-        self.interface = interface if interface is not None else InterfaceScorer(batch, region=region, n_points=n_points, probe=probe)
-        it = self.interface
-        self.region = it.region if region is None else complex_view.region_mask(batch, region, it.gt_atom14.device)
-        self.Lab, self.L = it.Lab, int(it.gt_seq.shape[0])
-        self.kw = dict(trim=float(trim), weight=float(weight), probe=it.kw['probe'], max_dots=int(max_dots))
-
-    def new_table(self, *lead):
-        """An uninitialised (*lead, len(SHAPE_COLUMNS)) float64 table on the complex's device for `score(..., out=table[i])`."""
-        return complex_view.new_table(SHAPE_COLUMNS, self.region.device, *lead)
-
-    def new_points(self, B):
-        """An uninitialised (B, L, 14, 2) int32 tensor for the point counts of B structures."""
-        import torch
-        return torch.empty(B, self.L, 14, 2, dtype=torch.int32, device=self.region.device)
+        super().__init__(batch, region, n_points, probe, interface)
+        self.kw = dict(trim=float(trim), weight=float(weight), probe=self.interface.kw['probe'], max_dots=int(max_dots))
 
     def score(self, atom14, seq, out=None, points=None, mask=None, j_chunk=0, workspace=None):
         """atom14 (B, Lab or L, 14, 3) f32 predicted coordinates, seq (B, Lab) tokens -> (B, len(SHAPE_COLUMNS)) float64 on the device;
@@ -67,18 +56,12 @@ class ShapeScorer:
         default); workspace: a uint8 tensor of at least ops.shape_workspace_bytes(B, L, P, max_dots) bytes (None: allocated here).
         No host synchronisation."""
         from abx_amd import ops
-        it = self.interface
-        if points is None:
-            points = self.new_points(atom14.shape[0])
-            it.score(atom14, seq, points=points, mask=mask)
-        return ops.shape_scores(atom14, seq, it.gt_atom14, it.gt_seq, it.gt_exists, it.sphere, points, Lab=self.Lab, region=self.region,
-                                mask=mask, res_mask=it.res_mask, out=out, j_chunk=j_chunk, workspace=workspace, **self.kw)
+        points = self.points_of(atom14, seq, points, mask)
+        return ops.shape_scores(atom14, seq, self.gt_atom14, self.gt_seq, self.gt_exists, self.interface.sphere, points, Lab=self.Lab,
+                                region=self.region, mask=mask, res_mask=self.res_mask, out=out, j_chunk=j_chunk, workspace=workspace, **self.kw)
 
-    def wild(self, points=None):
-        """(1, len(SHAPE_COLUMNS)): the row of the ground-truth complex itself with its own atoms (a design's row minus this one is
-        what the design gained or lost)."""
-        it = self.interface
-        return self.score(it.gt_atom14[None, :self.Lab], it.gt_seq[None, :self.Lab], points=points, mask=it.gt_exists[None])
+    # record(): 'shape' - the shape complementarity Sc of the interface, both directions, the designed residues' dots, the gaps and the
+    # dot counts - and, with a relaxer, 'shape_relaxed'; five launches per table
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -108,7 +91,6 @@ def shape_host(x, mask, aa, Lab, region=None, points=None, trim=1.5, weight=0.5,
     details=True adds a dict: 'n_buried', 'n_open', 'n_kept' (two integers each, antibody / antigen), 'S' and 'd2' (two arrays each,
     in list order), 'region' (bool per kept dot of the antibody), 'bad' (why the row is -1, or None)."""
     from .interface import _radius_table, golden_spiral, interface_host
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     x = to_np(x).astype(np.float32)
     L, Lab = x.shape[0], int(Lab)
     aa = np.clip(to_np(aa).astype(np.int64), 0, 20)

@@ -24,6 +24,7 @@ import functools
 import numpy as np
 
 from . import complex_view
+from .complex_view import Borderline as _Borderline, to_np, type_index
 
 # The row of abx_torsion_scores (include/abx_hip.h, ABX_TORSION_COLS)
 TORSIONS_COLUMNS = ('n_links', 'cis', 'cis_nonpro', 'twisted', 'n_links_region', 'cis_region', 'twisted_region', 'phi_pos', 'phi_pos_region',
@@ -78,11 +79,6 @@ def chi_table():
     return atoms, pi.astype(np.uint8)
 
 
-def type_index(letter):
-    from . import residue_constants as rc
-    return rc.restypes.index(letter)
-
-
 def abego_string(classes, region):
     """The ABEGO letters of the rows of `region` (a mask over the rows of `classes`, or longer), '-' where the code is 0."""
     cl = np.asarray(classes).astype(np.int64)
@@ -96,7 +92,6 @@ class TorsionScorer(complex_view.ComplexView):
     rows the sampler diffuses).  chi_tol: the largest |delta chi| of a recovered chi angle, in (0, 180] degrees."""
 
     COLUMNS = TORSIONS_COLUMNS
-    want_rows = False                   # set on an instance: sampler.sample_fn also records 'torsions_rows'
 
     def __init__(self, batch, region=None, chi_tol=40.0):
         import torch
@@ -129,8 +124,15 @@ class TorsionScorer(complex_view.ComplexView):
                                   region=self.region, mask=mask, res_mask=self.res_mask, out=out, rows=rows, classes=classes,
                                   workspace=workspace, **self.kw)
 
+    def side_outputs(self, B):
+        """The record of the designs also carries 'torsions_classes' (B, Lab) int32, the ABEGO codes, and with want_rows 'torsions_rows'
+        (B, Lab, 8) float64."""
+        return dict({'rows': self.new_rows(B)} if self.want_rows else {}, classes=self.new_classes(B))
+
     # wild(**kw): the crystal structure against itself - abego_same == n_abego, every difference 0, every compared chi ok: the first line
     # of the driver's table
+    # record(): 'torsions' - cis and twisted peptides, phi >= 0, the ABEGO classes, the backbone dihedrals and the chi angles against the
+    # crystal structure - and, with a relaxer, 'torsions_relaxed'; one launch per table
 
 
 # -------------------------------------------------------------------------------------------------------------------
@@ -146,17 +148,6 @@ def dihedral_xy(a, b, c, d):
     y = np.sqrt((b2[..., 0] * b2[..., 0] + b2[..., 1] * b2[..., 1]) + b2[..., 2] * b2[..., 2]) * \
         ((b1[..., 0] * n2[0] + b1[..., 1] * n2[1]) + b1[..., 2] * n2[2])
     return x, y
-
-
-class _Borderline:
-    """Counts the decisions `lhs ? rhs` whose two sides differ by less than 1e-9 relative (of the size of the operands)."""
-
-    def __init__(self):
-        self.n = 0
-
-    def __call__(self, lhs, rhs, scale, where=True):
-        near = np.abs(lhs - rhs) < 1e-9 * np.maximum(np.abs(scale), 1e-300)
-        self.n += int(np.count_nonzero(near & where))
 
 
 def _measure(x, mask, aa, chain, residx, th, chi_atoms, near):
@@ -197,7 +188,6 @@ def torsions_host(x, mask, aa, gt_x, gt_mask, gt_aa, Lab, chain_id, residx=None,
             differently).
     mistake: None, or the name of a deliberate error the tests show a column for - 'atan2_swapped', 'phi_next', 'omega_following',
     'chain_linked', 'chi_unfolded', 'gly_phi_pos'."""
-    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
     Lab = int(Lab)
     keep = np.ones(Lab, bool) if res_mask is None else (to_np(res_mask)[:Lab] != 0)
     xd = to_np(x)[:Lab].astype(np.float32).astype(np.float64)

@@ -9,7 +9,7 @@ import torch
 
 from abx_amd import accuracy, analyses, confidence, design, ensemble, interface, polar, sampler
 
-FLAGS = [an.flag for an in analyses.ANALYSES]
+FLAGS = [an.flag for an in analyses.ANALYSES[:7]]
 L, LAB, N = 9, (5, 7), 3
 
 
@@ -99,7 +99,7 @@ def stand_ins(seen, flags=FLAGS):
 
 @pytest.mark.parametrize('flags', [[f] for f in FLAGS] + [FLAGS], ids=lambda f: '+'.join(f))
 def test_zero_row_block_matches_the_filled_block(flags):
-    extras = [an.extra for an in analyses.ANALYSES if an.flag in flags and an.extra]
+    extras = [an.extra for an in analyses.ANALYSES[:7] if an.flag in flags and an.extra]
     a = parse(flags + extras)
     active = analyses.check_options(a, set_level=False)
     assert [an.flag for an in active] == flags

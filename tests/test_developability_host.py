@@ -309,16 +309,16 @@ def parser():
 
 
 def test_driver_declares_an_extension():
-    """ANALYSES keeps its seven entries; --developability is walked after them."""
+    """ANALYSES keeps its order; --developability is walked after the first seven."""
     from abx_amd import analyses, developability as dv
-    assert [an.flag for an in analyses.ANALYSES] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble']
-    assert [an.flag for an in analyses.EXTENSIONS] == ['developability'] and analyses.DEVELOPABILITY.kw == 'developability'
+    assert [an.flag for an in analyses.ANALYSES] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble', 'developability', 'shape', 'patches', 'torsions', 'secondary']
+    assert analyses.DEVELOPABILITY.kw == 'developability'
     a = parser().parse_args([])
     assert a.developability is False and a.developability_rows is False and (a.developability_radius, a.developability_exposed) == (10.0, 0.075)
     assert analyses.check_options(a, False) == []
-    every = ['--' + an.flag for an in analyses.ANALYSES]
+    every = ['--' + an.flag for an in analyses.ANALYSES[:7]]
     a = parser().parse_args(['--developability'] + every)
-    assert [an.flag for an in analyses.check_options(a, True)] == [an.flag for an in analyses.ANALYSES] + ['developability']
+    assert [an.flag for an in analyses.check_options(a, True)] == [an.flag for an in analyses.ANALYSES[:7]] + ['developability']
     a = parser().parse_args(['--developability', '--developability_rows', '--developability_radius', '8', '--developability_exposed', '0.1'])
     assert [an.flag for an in analyses.check_options(a, False)] == ['developability']
     ND = len(dv.DEVELOPABILITY_COLUMNS)
@@ -363,8 +363,8 @@ class Wild:
 def test_zero_row_block_matches_the_filled_block(with_seven):
     from abx_amd import accuracy, analyses, confidence, developability as dv, interface, metrics, polar, relax
     L, Lab, n = 9, 7, 2
-    seven = [an.flag for an in analyses.ANALYSES] if with_seven else []
-    flags = seven + ['developability', 'developability_rows'] + [an.extra for an in analyses.ANALYSES if an.extra and with_seven]
+    seven = [an.flag for an in analyses.ANALYSES[:7]] if with_seven else []
+    flags = seven + ['developability', 'developability_rows'] + [an.extra for an in analyses.ANALYSES[:7] if an.extra and with_seven]
     a = parser().parse_args(['--' + f for f in flags])
     active = analyses.check_options(a, set_level=False)
     assert [an.flag for an in active] == seven + ['developability']

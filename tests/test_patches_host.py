@@ -246,10 +246,11 @@ def parser():
 
 
 def test_driver_declares_a_further_analysis():
-    """ANALYSES, EXTENSIONS and LATER keep their order and come first; --patches is walked after them."""
+    """ANALYSES keeps its order; --patches is walked after the first nine."""
     from abx_amd import analyses, patches
-    before = analyses.ANALYSES + analyses.EXTENSIONS + analyses.LATER
-    assert 'patches' in [an.flag for an in analyses.FURTHER] and analyses.PATCHES.kw == 'patches' and analyses.PATCHES.extra == 'patches_rows'
+    before = analyses.ANALYSES[:9]
+    assert [an.flag for an in analyses.ANALYSES] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble', 'developability', 'shape', 'patches', 'torsions', 'secondary']
+    assert analyses.PATCHES.kw == 'patches' and analyses.PATCHES.extra == 'patches_rows'
     assert 'patches' not in [an.flag for an in before]
     a = parser().parse_args([])
     assert a.patches is False and a.patches_rows is False
@@ -307,7 +308,7 @@ class Wild:
 def test_zero_row_block_matches_the_filled_block(with_all):
     from abx_amd import accuracy, analyses, confidence, developability as dv, interface, metrics, patches, polar, relax, shape
     L, Lab, n = 9, 7, 2
-    before = analyses.ANALYSES + analyses.EXTENSIONS + analyses.LATER
+    before = analyses.ANALYSES[:9]
     others = [an.flag for an in before] if with_all else []
     flags = others + ['patches', 'patches_rows'] + [an.extra for an in before if an.extra and with_all]
     a = parser().parse_args(['--' + f for f in flags])
@@ -367,4 +368,3 @@ def test_sampler_signature_defaults_to_no_patches():
     import inspect
     from abx_amd import sampler
     assert inspect.signature(sampler.sample_fn).parameters['patches'].default is None
-    assert inspect.signature(sampler._analyse_last).parameters['patches'].default is None

@@ -268,10 +268,11 @@ def parser():
 
 
 def test_driver_declares_a_further_analysis():
-    """ANALYSES, EXTENSIONS and LATER keep their order and come first, --patches stays in front; --secondary is walked after --torsions."""
+    """ANALYSES keeps its order: --patches stays in front, --secondary is walked after --torsions."""
     from abx_amd import analyses
-    before = analyses.ANALYSES + analyses.EXTENSIONS + analyses.LATER
-    further = [an.flag for an in analyses.FURTHER]
+    before = analyses.ANALYSES[:9]
+    further = [an.flag for an in analyses.ANALYSES[9:]]
+    assert [an.flag for an in analyses.ANALYSES] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble', 'developability', 'shape', 'patches', 'torsions', 'secondary']
     assert [an.flag for an in before] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble', 'developability', 'shape']
     assert further[0] == 'patches' and further.index('secondary') > further.index('torsions') > 0
     assert analyses.SECONDARY.kw == 'secondary' and analyses.SECONDARY.extra == 'secondary_rows'
@@ -387,4 +388,3 @@ def test_sampler_signature_defaults_to_no_secondary():
     import inspect
     from abx_amd import sampler
     assert inspect.signature(sampler.sample_fn).parameters['secondary'].default is None
-    assert inspect.signature(sampler._analyse_last).parameters['secondary'].default is None

@@ -197,17 +197,16 @@ def parser():
 
 
 def test_driver_declares_a_later_analysis():
-    """ANALYSES keeps its seven entries and EXTENSIONS its one; --shape is walked after both."""
+    """ANALYSES keeps its order; --shape is walked after the first eight."""
     from abx_amd import analyses, shape
-    assert [an.flag for an in analyses.ANALYSES] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble']
-    assert [an.flag for an in analyses.EXTENSIONS] == ['developability']
-    assert [an.flag for an in analyses.LATER] == ['shape'] and analyses.SHAPE.kw == 'shape' and analyses.SHAPE.extra is None
+    assert [an.flag for an in analyses.ANALYSES] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble', 'developability', 'shape', 'patches', 'torsions', 'secondary']
+    assert analyses.SHAPE.kw == 'shape' and analyses.SHAPE.extra is None
     a = parser().parse_args([])
     assert a.shape is False and (a.shape_trim, a.shape_weight, a.shape_max_dots) == (1.5, 0.5, 8192)
     assert analyses.check_options(a, False) == []
-    every = ['--' + an.flag for an in analyses.ANALYSES + analyses.EXTENSIONS]
+    every = ['--' + an.flag for an in analyses.ANALYSES[:8]]
     a = parser().parse_args(['--shape'] + every)
-    assert [an.flag for an in analyses.check_options(a, True)] == [an.flag for an in analyses.ANALYSES + analyses.EXTENSIONS] + ['shape']
+    assert [an.flag for an in analyses.check_options(a, True)] == [an.flag for an in analyses.ANALYSES[:8]] + ['shape']
     a = parser().parse_args(['--shape', '--shape_trim', '0', '--shape_weight', '0', '--shape_max_dots', '1'])
     assert [an.flag for an in analyses.check_options(a, False)] == ['shape']
     NS = len(shape.SHAPE_COLUMNS)
@@ -250,7 +249,7 @@ class Wild:
 def test_zero_row_block_matches_the_filled_block(with_all):
     from abx_amd import accuracy, analyses, confidence, developability as dv, interface, metrics, polar, relax, shape
     L, Lab, n = 9, 7, 2
-    before = analyses.ANALYSES + analyses.EXTENSIONS
+    before = analyses.ANALYSES[:8]
     others = [an.flag for an in before] if with_all else []
     flags = others + ['shape'] + [an.extra for an in before if an.extra and with_all]
     a = parser().parse_args(['--' + f for f in flags])

@@ -295,10 +295,11 @@ def parser():
 
 
 def test_driver_declares_a_further_analysis():
-    """ANALYSES, EXTENSIONS and LATER keep their order and come first, --patches stays in front; --torsions is walked after them."""
+    """ANALYSES keeps its order: --patches stays in front of --torsions, which is walked after the first nine."""
     from abx_amd import analyses, torsions
-    before = analyses.ANALYSES + analyses.EXTENSIONS + analyses.LATER
-    further = [an.flag for an in analyses.FURTHER]
+    before = analyses.ANALYSES[:9]
+    further = [an.flag for an in analyses.ANALYSES[9:]]
+    assert [an.flag for an in analyses.ANALYSES] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble', 'developability', 'shape', 'patches', 'torsions', 'secondary']
     assert [an.flag for an in before] == ['score', 'relax', 'interface', 'confidence', 'accuracy', 'polar', 'ensemble', 'developability', 'shape']
     assert further[0] == 'patches' and 'torsions' in further and analyses.TORSIONS.kw == 'torsions' and analyses.TORSIONS.extra == 'torsions_rows'
     assert 'torsions' not in [an.flag for an in before]
@@ -412,4 +413,3 @@ def test_sampler_signature_defaults_to_no_torsions():
     import inspect
     from abx_amd import sampler
     assert inspect.signature(sampler.sample_fn).parameters['torsions'].default is None
-    assert inspect.signature(sampler._analyse_last).parameters['torsions'].default is None
