@@ -911,11 +911,6 @@ __device__ __forceinline__ void tri8_row_compute(const AbxTriAttn& a, const Tri8
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) bad |= __builtin_amdgcn_classf(v[r], 0x207);
-#ifdef ABX_TRI_ROW_NT_STORE  // (probe build: non-temporal stores of the row-fused kernel's write-once output rows, 67 KB per slot that pass through an L2
-                             //  the z rows and the bias maps compete for)
-            if constexpr (!CHUNK_BARRIER) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(op + dd));
-            else
-#endif
             *reinterpret_cast<f32x4*>(op + dd) = v;
         }
     }

@@ -435,7 +435,9 @@ int launch_cfg(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
 #undef GEMM_LAUNCH
 }
 
-// tuning variants of the main weight-GEMM configuration (selected by AbxGemm.tune, ABX_TUNE_FORCE_MASK; 0 = default)
+// tuning variants of the main weight-GEMM configuration (AbxGemm.tune, ABX_TUNE_FORCE_MASK).  RETIRED, kept compiled: gemm_prepare refuses the
+// FORCE bits, so gemm_run never takes them; the two instantiations stay because removing them changes the machine code of
+// gemm_kernel<128, 128, 64, 64, 16, true, true, false, 3>, which shares its helper functions with them ("Retired GEMM variants")
 template <int BK, int MINW>
 int launch_main_variant(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
     const long long mt = ((long long)g.M + 127) / 128, ntn = ((long long)g.N + 127) / 128;
@@ -489,6 +491,13 @@ extern "C" int abx_gemm_check_modes(const AbxGemm* gp) {
 static int gemm_prepare(const AbxGemm* gp, AbxGemm& g) {
     if (int rc = abx_gemm_check_modes(gp)) return rc;
     g = *gp;
+    if (g.tune & ~ABX_TUNE_LIVE_MASK) {      // a retired or unknown variant: refused, never run under another bit's label
+        static thread_local char msg[160];
+        snprintf(msg, sizeof(msg), "abx_gemm: tune = %d has bits outside ABX_TUNE_LIVE_MASK (%d): retired or unknown variant (include/abx_hip.h, AbxGemm.tune)",
+                 g.tune, ABX_TUNE_LIVE_MASK);
+        abx_set_error(msg);
+        return ABX_ERR_ARG;
+    }
     ABX_REQUIRE((g.A || g.A_split) && (g.B || g.B_split) && (g.C || g.C_split), "abx_gemm: null operand");
     ABX_REQUIRE(!g.glu || (g.c_transposed && g.N % 128 == 0 && !g.gate), "abx_gemm: glu needs a transposed store, N % 128 == 0, no gate");
     const long long tile_rows = ((long long)(g.pair_L + 7) / 8 * 8) * ((long long)(g.pair_Lp + 15) / 16 * 16);

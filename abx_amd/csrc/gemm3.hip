@@ -35,12 +35,12 @@
 
 namespace {
 
-template <int BM, int BN, int WM, int WN, int AMODE, bool EDGE, bool TS, bool OLN = false, bool PROBE = true, int RING = 2, int JGO = 0>
+template <int BM, int BN, int WM, int WN, int AMODE, bool EDGE, bool TS, bool OLN = false, bool PROBE = true, int RING = 2>
 __device__ __forceinline__ void gemm3_block(const AbxGemm& g, float* smem, int mt, int nt, int b) {
     constexpr int TM = WM / 32, TN = WN / 32;
     f32x16 acc[TM][TN];
     float ls[TM], lq[TM], lsh[TM];
-    gemm3_mainloop<BM, BN, WM, WN, AMODE, false, true, RING, JGO>(g, smem, mt, nt, b, acc, ls, lq, lsh);
+    gemm3_mainloop<BM, BN, WM, WN, AMODE, false, true, RING>(g, smem, mt, nt, b, acc, ls, lq, lsh);
     float* st_lds = smem;                                   // [BM][2]
     const bool stats = gemm3_row_stats<BM, BN, WM, WN, EDGE>(g, st_lds, mt, b, ls, lq);
     __syncthreads();
@@ -51,7 +51,7 @@ __device__ __forceinline__ void gemm3_block(const AbxGemm& g, float* smem, int m
 // Two main loops over the same output tile into two accumulator sets: the channel-major product (AMODE 1) against proj_out, then
 // the rows of z (k-contiguous, inline LayerNorm) against the final-gate weights; the gate never travels through HBM and z is
 // read once for both the gate and the residual.
-template <int BM, int BN, int WM, int WN, bool EDGE, int JGO = 0, int TGO = 0>
+template <int BM, int BN, int WM, int WN, bool EDGE>
 __device__ __forceinline__ void gemm3_dual_block(const AbxGemm& g, float* smem, int mt, int nt, int b) {
     constexpr int TM = WM / 32, TN = WN / 32;
     f32x16 acc[TM][TN], acc2[TM][TN];
@@ -61,14 +61,14 @@ __device__ __forceinline__ void gemm3_dual_block(const AbxGemm& g, float* smem, 
     g2.A_split = nullptr; g2.a_relu = 0; g2.a_pair_transpose = 0; g2.a_pair = g.pair_Lp > 0 ? 1 : 0;
     g2.B_split = g.B2_split; g2.sB3p = g.sB23p; g2.sB3n = g.sB23n; g2.sB3k = g.sB23k; g2.sB3b = 0;
     g2.ln_csum = g.ln2_csum; g2.ln_stats = nullptr; g2.batch_inner = 0; g2.b_exp = g.b2_exp;
-    if (g.sAk == 1) gemm3_mainloop<BM, BN, WM, WN, 0, false, true, 2, JGO>(g, smem, mt, nt, b, acc, ls, lq, lsh);
-    else gemm3_mainloop<BM, BN, WM, WN, 1, false, true, 2, JGO>(g, smem, mt, nt, b, acc, ls, lq, lsh);
-    gemm3_mainloop<BM, BN, WM, WN, 0, false, true, 2, JGO>(g2, smem, mt, nt, b, acc2, ls2, lq2, lsh2);
+    if (g.sAk == 1) gemm3_mainloop<BM, BN, WM, WN, 0>(g, smem, mt, nt, b, acc, ls, lq, lsh);
+    else gemm3_mainloop<BM, BN, WM, WN, 1>(g, smem, mt, nt, b, acc, ls, lq, lsh);
+    gemm3_mainloop<BM, BN, WM, WN, 0>(g2, smem, mt, nt, b, acc2, ls2, lq2, lsh2);
     float* st_lds = smem;                                   // [BM][2] + [BM][2]
     const bool stats = gemm3_row_stats<BM, BN, WM, WN, EDGE>(g, st_lds, mt, b, ls, lq);
     gemm3_row_stats<BM, BN, WM, WN, EDGE>(g2, st_lds + 2 * BM, mt, b, ls2, lq2);
     __syncthreads();
-    gemm_epilogue<BM, BN, WM, WN, EDGE, false, false, true, TGO>(g, st_lds, smem + 4 * BM, acc, mt * BM, nt * BN, b, stats, &acc2, st_lds + 2 * BM);
+    gemm_epilogue<BM, BN, WM, WN, EDGE, false>(g, st_lds, smem + 4 * BM, acc, mt * BM, nt * BN, b, stats, &acc2, st_lds + 2 * BM);
 }
 
 // Round 6: the same dual GEMM with ONE walk over the rows of z.  The 128 x 96 tiles above give every row tile two blocks (one per column
@@ -161,25 +161,6 @@ __global__ __launch_bounds__(256, MINW) void gemm3_kernel(const AbxGemm g) {
     const int per_batch = ntn * ntm;
     const ClockProbe probe(g.clock_probe);
     constexpr bool PROBE = !(BM == 128 && BN == 128 && MINW >= 4);      // (no register for it at four blocks per CU: gemm_epilogue.h)
-#ifdef ABX_PERSIST
-    if (g.tune & ABX_TUNE_PERSIST) {
-        // experiment: resident blocks walk the tiles of their XCD's range (slot s takes x0 + s, x0 + s + slots, ...)
-        const long long total = (long long)per_batch * g.batch;
-        const long long q = total >> 3, r = total & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-        const long long x0 = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, xn = q + (xcd < r ? 1 : 0);
-        for (long long i = slot; i < xn; i += slots) {
-            const long long wgid = x0 + i;
-            const int b = (int)(wgid / per_batch);
-            const int rem = (int)(wgid - (long long)b * per_batch);
-            const int mt = rem / ntn, nt = rem % ntn;
-            const bool interior = (mt + 1) * BM <= g.M && (nt + 1) * BN <= g.N;
-            if (interior) gemm3_block<BM, BN, WM, WN, AMODE, false, TS, false, PROBE, RING>(g, smem, mt, nt, b);
-            else gemm3_block<BM, BN, WM, WN, AMODE, true, TS, false, PROBE, RING>(g, smem, mt, nt, b);
-            __syncthreads();
-        }
-        return;
-    }
-#endif
     // (32-bit: the dispatch keeps the grid below 2^31 tiles; a 64-bit division is ~80 instructions in front of the block's first DMA)
     const unsigned wgid = (g.tune & ABX_TUNE_NO_REMAP) ? blockIdx.x : xcd_contiguous(blockIdx.x, gridDim.x);
     const int b = (int)(wgid / (unsigned)per_batch);
@@ -252,10 +233,7 @@ template <int BM, int BN, int WM, int WN, int MINW>
 __global__ __launch_bounds__(256, MINW) void gemm3_dual_kernel(const AbxGemm g) {
     constexpr int A_STAGE = BM * 64, B_STAGE = 2 * BN * 32;
     constexpr int OPER = (2 * A_STAGE + 2 * B_STAGE) / 4;
-    // four blocks per CU (MINW 4): one B sub-tile in flight and 32-column store groups keep the two accumulator sets inside 128
-    // VGPRs and the block inside 40 KB of LDS
-    constexpr int JGO = MINW >= 4 ? 1 : 0, TGO = MINW >= 4 ? 1 : 0;
-    constexpr int TNW = WN / 32, TGW = TGO > 0 ? TGO : (TNW > 3 ? (TNW % 3 == 0 ? 3 : 2) : TNW);
+    constexpr int TNW = WN / 32, TGW = TNW > 3 ? (TNW % 3 == 0 ? 3 : 2) : TNW;
     constexpr int EPI = 4 * BM + 4 * 32 * (TGW * 32 + 4);
     __shared__ __attribute__((aligned(16))) float smem[OPER > EPI ? OPER : EPI];
     const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + BM - 1) / BM;
@@ -265,8 +243,8 @@ __global__ __launch_bounds__(256, MINW) void gemm3_dual_kernel(const AbxGemm g) 
     const int rem = (int)(wgid - (unsigned)b * (unsigned)per_batch);
     const int mt = rem / ntn, nt = rem % ntn;
     const bool interior = (mt + 1) * BM <= g.M && (nt + 1) * BN <= g.N;
-    if (interior) gemm3_dual_block<BM, BN, WM, WN, false, JGO, TGO>(g, smem, mt, nt, b);
-    else gemm3_dual_block<BM, BN, WM, WN, true, JGO, TGO>(g, smem, mt, nt, b);
+    if (interior) gemm3_dual_block<BM, BN, WM, WN, false>(g, smem, mt, nt, b);
+    else gemm3_dual_block<BM, BN, WM, WN, true>(g, smem, mt, nt, b);
 }
 
 // Fused two-layer transition (seqformer.py:358-376: LayerNorm -> Linear(4x) -> ReLU -> Linear, + residual) for 128 rows per block:
@@ -283,11 +261,10 @@ __global__ __launch_bounds__(256, MINW) void gemm3_dual_kernel(const AbxGemm g) 
 // A is read from HBM once (the 6 chunk walks of a block hit the L2 / MALL), the hidden never leaves the CU, the output rows are
 // written once: 2 x 192 floats of HBM traffic per pair row instead of 2 x 192 + 2 x 768.
 constexpr int MLP_NH = 768;                                                  // widest hidden layer of the fused transition (LDS table)
-// R1: stages of GEMM 1's operand ring (2: a step waits for the tiles it requested at its own start; 3: requested one step earlier, counted waits)
-template <bool EDGE, int R1 = 2>
+template <bool EDGE>
 __device__ __forceinline__ void gemm3_mlp_block(const AbxGemm& g, float* smem, int mt, int b) {
     constexpr int BM = 128, BN = 128, WM = 32, WN = 128, BN2 = 192, TN2 = BN2 / 32;
-    constexpr int G1_BYTES = R1 * (BM * 64 + 2 * BN * 32);                   // stages of GEMM 1 (A fp32 + W1 planes)
+    constexpr int G1_BYTES = 2 * (BM * 64 + 2 * BN * 32);                    // stages of GEMM 1 (A fp32 + W1 planes)
     constexpr int B2_IMG = 2 * BN2 * 32;                                     // one k-tile of W2: [2][192][16] f16
     constexpr int NL2 = (B2_IMG + 4095) / 4096;
     char* W2s = reinterpret_cast<char*>(smem) + G1_BYTES;                    // 2 stages
@@ -328,14 +305,14 @@ __device__ __forceinline__ void gemm3_mlp_block(const AbxGemm& g, float* smem, i
         issue_w2(c * (BN / 16), 0);                                          // first W2 k-tile of the chunk: lands under GEMM 1
         f32x16 acc1[1][BN / 32];
         if (c == 0) {
-            gemm3_mainloop<BM, BN, WM, WN, 0, true, true, R1>(g, smem, mt, c, b, acc1, ls, lq, lsh);
+            gemm3_mainloop<BM, BN, WM, WN, 0, true, true>(g, smem, mt, c, b, acc1, ls, lq, lsh);
             // row statistics of this lane's row (the two lane halves hold the two k halves)
             const float invK = 1.0f / (float)g.K;
             const float sm = ls[0] + __shfl_xor(ls[0], 32, 64), sq = lq[0] + __shfl_xor(lq[0], 32, 64);
             dmean = sm * invK;
             rstd = 1.0f / sqrtf(fmaxf(sq * invK - dmean * dmean, 0.f) + g.ln_eps);
         } else {
-            gemm3_mainloop<BM, BN, WM, WN, 0, true, false, R1>(g, smem, mt, c, b, acc1, ls, lq, lsh);
+            gemm3_mainloop<BM, BN, WM, WN, 0, true, false>(g, smem, mt, c, b, acc1, ls, lq, lsh);
         }
         // (the main loop ended with every DMA drained - the W2 tile included - and a block barrier)
         const int hid0 = c * BN;
@@ -418,19 +395,6 @@ __global__ __launch_bounds__(256, MINB) void gemm3_mlp_kernel(const AbxGemm g) {
     const ClockProbe probe(g.clock_probe);
     if ((mt + 1) * 128 <= g.M && g.N2 == 192) gemm3_mlp_block<false>(g, smem, mt, b);
     else gemm3_mlp_block<true>(g, smem, mt, b);
-    probe.finish();
-}
-
-// the same with a three-stage ring for GEMM 1 (dynamic LDS: 79.9 KB, still two blocks per CU)
-constexpr int MLP3_LDS = 3 * (128 * 64 + 2 * 128 * 32) + 2 * 2 * 192 * 32 + 2 * MLP_NH * 4;
-__global__ __launch_bounds__(256, 2) void gemm3_mlp3_kernel(const AbxGemm g) {
-    extern __shared__ __attribute__((aligned(16))) float mlp3_smem[];
-    const int ntm = (g.M + 127) / 128;
-    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
-    const int b = (int)(wgid / (unsigned)ntm), mt = (int)(wgid - (unsigned)b * (unsigned)ntm);
-    const ClockProbe probe(g.clock_probe);
-    if ((mt + 1) * 128 <= g.M && g.N2 == 192) gemm3_mlp_block<false, 3>(g, mlp3_smem, mt, b);
-    else gemm3_mlp_block<true, 3>(g, mlp3_smem, mt, b);
     probe.finish();
 }
 
@@ -772,9 +736,6 @@ template <int BM, int BN, int WM, int WN, int MINW>
 int launch3(const AbxGemm& g, hipStream_t st, AbxPlan* plan) {
     const long long mt = ((long long)g.M + BM - 1) / BM, ntn = ((long long)g.N + BN - 1) / BN;
     dim3 grid((unsigned)(mt * ntn * g.batch), 1, 1), block(256);
-#ifdef ABX_PERSIST
-    if ((g.tune & ABX_TUNE_PERSIST) && grid.x > 256u * MINW) grid.x = 256u * MINW;
-#endif
     const int amode = g.A_split ? 2 : (g.sAk == 1 ? 0 : 1);
 #define GEMM3_LAUNCH(AMODE, TS)                                                                                         \
     ABX_LAUNCH(plan, ("gemm3_kernel<%d, %d, %d, %d, %d, %s, %d>", BM, BN, WM, WN, AMODE, ABX_BOOL(TS), MINW), "abx_gemm", \
@@ -888,8 +849,10 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
         }
         const long long mt = ((long long)g.M + 127) / 128;
         const dim3 grid((unsigned)(mt * g.batch)), block(256);
-        if (g.tune & ABX_TUNE_MLP_RING3) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp3_kernel, MLP3_LDS, grid, block, MLP3_LDS, st, g);     // benchmarking
-        else if (g.tune & ABX_TUNE_MLP_MINB1) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp_kernel<1>, 0, grid, block, 0, st, g);         // benchmarking
+        // RETIRED, kept compiled: gemm_prepare refuses ABX_TUNE_MLP_MINB1 (and NARROW_RING below, FORCE in gemm.hip), so these branches are never
+        // taken.  They stay because they instantiate kernels whose removal changes the machine code of kernels that stay, which share helper
+        // functions with them ("Retired GEMM variants").  Take them out together with a measurement of those kernels.
+        if (g.tune & ABX_TUNE_MLP_MINB1) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp_kernel<1>, 0, grid, block, 0, st, g);         // (retired, unreachable: see below)
         else *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(mlp)", &gemm3_mlp_kernel<2>, 0, grid, block, 0, st, g);
         return 0;
     }
@@ -905,22 +868,17 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
         }
         // (128 x 192 tiles - A read and split once per row - need 2 x 96 accumulator registers and spill at 256 VGPRs)
         const long long mt = ((long long)g.M + 127) / 128, ntn = ((long long)g.N + 95) / 96;
-        // Three blocks per CU (142 VGPRs).  ABX_TUNE_DUAL_4BLOCK: the four-block build (one B sub-tile in flight, 32-column store groups, 128 VGPRs):
-        // 5 % faster (9.75 vs 10.28 ms at 100 samples), but the accumulator set of the first main loop is parked in scratch across the
-        // second and that is + 9 GB of HBM traffic per launch on the counters (43.9 vs 34.8 GB) - measured in profiles/r04l, not the default
-        // ABX_TUNE_DUAL_1WALK (round 6 probe, 96 < N <= 192): one block per row tile, z walked once (gemm3_dual1_kernel) - bit-identical, but its 96 kept
-        // gate registers + 48 accumulators leave two blocks per CU instead of three (256 VGPRs, 7 spilled): 10.97 vs 10.30 ms at 100 samples
-        // (profiles/r06c_kb_dual.txt); NOT the default
+        // Three blocks per CU (142 VGPRs).  ABX_TUNE_DUAL_1WALK (96 < N <= 192): one block per row tile, z walked once (gemm3_dual1_kernel),
+        // the bit-identical cross-check of the default
         const dim3 grid((unsigned)(mt * ntn * g.batch)), block(256);
         if (g.N > 96 && g.N <= 192 && (g.tune & ABX_TUNE_DUAL_1WALK)) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", &gemm3_dual1_kernel, 0, dim3((unsigned)(mt * g.batch)), block, 0, st, g);
-        else if (g.tune & ABX_TUNE_DUAL_4BLOCK) *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", (gemm3_dual_kernel<128, 96, 32, 96, 4>), 0, grid, block, 0, st, g);
         else *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(dual)", (gemm3_dual_kernel<128, 96, 32, 96, 3>), 0, grid, block, 0, st, g);
         return 0;
     }
     if (narrow) {
         const long long mt = ((long long)g.M + 127) / 128;
         dim3 grid((unsigned)(mt * g.batch), 1, 1), block(256);
-        if (const int v = (g.tune & ABX_TUNE_NARROW_RING_MASK) >> ABX_TUNE_NARROW_RING_SHIFT) {      // probe: deeper ring (1: 3 stages at 4 blocks per CU, 2: 4 stages at 3)
+        if (const int v = (g.tune & ABX_TUNE_NARROW_RING_MASK) >> ABX_TUNE_NARROW_RING_SHIFT) {      // (retired, unreachable: see the fused transition above)
             const char* what = "abx_gemm(narrow, ring)";
             if (g.c_transposed && v == 1) *rc = ABX_LAUNCH_LIT(plan, what, (gemm3_narrow_ring_kernel<true, 3, 4>), 0, grid, block, 0, st, g);
             else if (g.c_transposed) *rc = ABX_LAUNCH_LIT(plan, what, (gemm3_narrow_ring_kernel<true, 4, 3>), 0, grid, block, 0, st, g);
@@ -933,9 +891,8 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
         return 0;
     }
     const long long pad128 = ((g.N + 127) / 128) * 128, pad192 = ((g.N + 191) / 192) * 192;
-    const int force = (g.tune & ABX_TUNE_FORCE_MASK) >> ABX_TUNE_FORCE_SHIFT;      // 1: 128x128, 2: 128x192 (benchmarking)
     // (the plane x plane contraction at L = 352 pads to 384 either way: the wide tile measured 10 % faster)
-    const bool wide = g.glu ? false : force ? force == 2 : (g.A_split ? pad192 <= pad128 : (pad192 <= pad128 && g.N % 128 != 0));
+    const bool wide = g.glu ? false : (g.A_split ? pad192 <= pad128 : (pad192 <= pad128 && g.N % 128 != 0));
     // waves are stacked along M (4 x 1): every wave owns 32 rows and the full tile width, so each A row is read from LDS and
     // split into f16 pieces by exactly one wave (the VALU issue slots next to the MFMAs are the scarce resource)
     // Small problems (the per-residue GEMMs of the IPA loop / sequence track at a dozen samples per GPU: 4 224 rows x 256 columns = 66
@@ -943,7 +900,7 @@ int abx_gemm3_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan)
     // in the same order (same MFMA, same term order, same row statistics), so the tile choice does not change a single bit and
     // results stay independent of how many samples share a launch.
     const long long ntn128 = ((long long)g.N + 127) / 128;
-    if (!wide && !g.glu && !force && mt128 * ntn128 * g.batch < 384 && g.M > 64) *rc = launch3<64, 128, 32, 64, 4>(g, st, plan);
+    if (!wide && !g.glu && mt128 * ntn128 * g.batch < 384 && g.M > 64) *rc = launch3<64, 128, 32, 64, 4>(g, st, plan);
     else if (wide) *rc = launch3<128, 192, 32, 192, 3>(g, st, plan);
     else *rc = launch3<128, 128, 32, 128, 4>(g, st, plan);
     return 0;

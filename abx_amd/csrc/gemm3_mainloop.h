@@ -44,7 +44,7 @@ __device__ __forceinline__ void plane_sources(long long s_plane, long long s_row
 // meaning); a caller that walks the same A rows again passes STATS = false and the lshift of its first walk.
 // AMODE 3: the A operand is resident in LDS (a_lds: BM fp32 rows of a_lds_stride bytes, k-contiguous; written by the caller before
 // the call): no A stage, no A DMA - the fused IPA tail chains its GEMMs this way.
-template <int BM, int BN, int WM, int WN, int AMODE, bool SWAP = false, bool STATS = true, int RING = 2, int JGO = 0>
+template <int BM, int BN, int WM, int WN, int AMODE, bool SWAP = false, bool STATS = true, int RING = 2>
 __device__ __forceinline__ void gemm3_mainloop(const AbxGemm& g, float* smem, int mt, int nt, int b, f32x16 (&acc)[WM / 32][WN / 32],
                                                float (&ls)[WM / 32], float (&lq)[WM / 32], float (&lshift)[WM / 32],
                                                const char* a_lds = nullptr, int a_lds_stride = 0) {
@@ -258,7 +258,7 @@ __device__ __forceinline__ void gemm3_mainloop(const AbxGemm& g, float* smem, in
         // product terms, smallest first (SplitTerms); the B fragments are fetched per group of JG sub-tiles (register budget);
         // consecutive MFMAs hit different accumulators
         using T = SplitTerms;
-        constexpr int JG = JGO > 0 ? JGO : (TN > 3 ? (TN % 3 == 0 ? 3 : 2) : TN);
+        constexpr int JG = TN > 3 ? (TN % 3 == 0 ? 3 : 2) : TN;
 #pragma unroll
         for (int j0 = 0; j0 < TN; j0 += JG) {
             u32x4 bb[JG][3];

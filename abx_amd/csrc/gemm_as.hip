@@ -364,11 +364,7 @@ __device__ __forceinline__ void as_block(const AbxGemm& g, const AbxGemm& s2, ch
                 *reinterpret_cast<f32x2*>(cr + n + 2) = (f32x2){o[2], o[3]};
             }
         } else
-#ifdef ABX_AS_NT_STORE     // (probe build: non-temporal stores of the write-once projection output)
-        if (ABL != 1 && (!EDGE || m < g.M)) __builtin_nontemporal_store((f32x4){o[0], o[1], o[2], o[3]}, reinterpret_cast<f32x4*>(Cb + (long long)m * g.sCm + n));
-#else
         if (ABL != 1 && (!EDGE || m < g.M)) *reinterpret_cast<f32x4*>(Cb + (long long)m * g.sCm + n) = (f32x4){o[0], o[1], o[2], o[3]};
-#endif
     };
     // GLU: four value slices (row quad rq: the lane's 4 consecutive rows of its channel -> 8 bytes per plane), then two store slices:
     // v_permlane32_swap hands the h = 0 lane of a channel the rows 8 A .. 8 A + 7 and the h = 1 lane the rows 8 B .. 8 B + 7 of the row

@@ -33,7 +33,9 @@ def env_on(name):
     return os.environ.get(name, '') not in ('', '0')
 
 
-GEMM_TUNE = int(os.environ.get('ABX_GEMM_TUNE', '0'))      # kernel-variant selector (benchmarking only: AbxGemm.tune of every descriptor-level launch)
+# kernel-variant selector (benchmarking only: AbxGemm.tune of every descriptor-level launch).  The live bits are listed at AbxGemm.tune in
+# include/abx_hip.h (ABX_TUNE_LIVE_MASK: 1, 64, 128, 2048, 16384); any other bit - a retired variant's, DESIGN.md - is refused by the library at the first GEMM
+GEMM_TUNE = int(os.environ.get('ABX_GEMM_TUNE', '0'))
 
 # ---- range safety of the split-f16 kernels (include/abx_hip.h, AbxGemm.range_flag) ----------------------------------------------
 # Every split-f16 launch made through this module carries the address of one device word per GPU and a bit that names its call-site

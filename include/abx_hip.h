@@ -166,20 +166,16 @@ typedef struct AbxGemm {
      * bit; every variant computes the same values.  Each kernel family reads its own bits only, so a value set for one family changes no
      * other launch.  Constants: ABX_TUNE_* below the struct.
      *   bit 0      NO_REMAP       workgroups keep the launch order (no XCD-contiguous remap, csrc/grid_map.h): gemm_kernel, gemm3_kernel
-     *   bits 1-3   FORCE          tile kernels of gemm3.hip: 1 = 128 x 128 tiles, 2 = 128 x 192; exact fp32 kernels of gemm.hip: variant
-     *                             1 = BK 16 at two blocks per CU, 2 = at four, 3 = 128 x 128 at three (plain weight GEMM only)
-     *   bit 4      MLP_MINB1      fused transition: gemm3_mlp_kernel<1> (one block per CU: what the second resident block is worth)
-     *   bit 5      MLP_RING3      fused transition: gemm3_mlp3_kernel (three-stage ring for its first GEMM)
      *   bit 6      GTAIL_2WALK    gated attention tail: the two-walk form gemm3_gtail2w_kernel
      *   bit 7      DUAL_1WALK     dual GEMM, 96 < N <= 192: gemm3_dual1_kernel (one block per row tile, z walked once)
-     *   bit 8      PERSIST        gemm3_kernel: resident blocks walk the tiles of their XCD's range (-DABX_PERSIST builds only)
-     *   bits 9-10  NARROW_RING    skinny N <= 32 projections: gemm3_narrow_ring_kernel, 1 = 3 stages at 4 blocks per CU, 2 = 4 stages at 3
      *   bit 11     TILE_ONLY      the tile kernels of gemm3.hip for this call, never an A-stationary kernel of gemm_as.hip
      *   bits 12-13 ABLATE         gemm_as_kernel: 1 = no slice stores, 2 = no MFMA, 3 = half of the weight DMA (-DABX_AS_ABLATE builds only)
      *   bit 14     AS_DUAL        the dual descriptor of the TriangleMultiplication tail (A2, K = 128 channel-major, K2 = 192, N = 192, out
      *                             of place) takes gemm_as_dual_kernel also below its launch-size threshold of 1 024 blocks of 64 rows
      *                             (tests; the results are bit-identical to the tile kernel's either way)
-     *   bit 15     DUAL_4BLOCK    dual GEMM: gemm3_dual_kernel<128, 96, 32, 96, 4> (four blocks per CU instead of three)
+     * Every other bit is refused (ABX_ERR_ARG, ABX_TUNE_LIVE_MASK): the variants they selected are retired, their measurements are in
+     * DESIGN.md ("Retired GEMM variants").  Three retired fields keep their constant (FORCE 1-3, MLP_MINB1 4, NARROW_RING 9-10): their
+     * kernels and dispatch lines are still compiled, unreachable behind the guard, for the reason given there.
      * Environment: ABX_NO_DUAL_AS set, not empty and not "0" keeps gemm3_dual_kernel for every dual descriptor of the process (A / B
      * measurements); the on / off switches all read that way */
     int tune;
@@ -207,20 +203,25 @@ typedef struct AbxGemm {
 
 /* AbxGemm.tune: the table at the field says what each selects */
 #define ABX_TUNE_NO_REMAP 1
-#define ABX_TUNE_FORCE_SHIFT 1
-#define ABX_TUNE_FORCE_MASK (7 << ABX_TUNE_FORCE_SHIFT)
-#define ABX_TUNE_MLP_MINB1 16
-#define ABX_TUNE_MLP_RING3 32
 #define ABX_TUNE_GTAIL_2WALK 64
 #define ABX_TUNE_DUAL_1WALK 128
-#define ABX_TUNE_PERSIST 256
-#define ABX_TUNE_NARROW_RING_SHIFT 9
-#define ABX_TUNE_NARROW_RING_MASK (3 << ABX_TUNE_NARROW_RING_SHIFT)
 #define ABX_TUNE_TILE_ONLY 2048
 #define ABX_TUNE_ABLATE_SHIFT 12
 #define ABX_TUNE_ABLATE_MASK (3 << ABX_TUNE_ABLATE_SHIFT)
 #define ABX_TUNE_AS_DUAL 16384
-#define ABX_TUNE_DUAL_4BLOCK 32768
+/* retired and refused like every bit outside the mask below; named only by dispatch lines that stay compiled ("Retired GEMM variants") */
+#define ABX_TUNE_FORCE_SHIFT 1
+#define ABX_TUNE_FORCE_MASK (7 << ABX_TUNE_FORCE_SHIFT)
+#define ABX_TUNE_MLP_MINB1 16
+#define ABX_TUNE_NARROW_RING_SHIFT 9
+#define ABX_TUNE_NARROW_RING_MASK (3 << ABX_TUNE_NARROW_RING_SHIFT)
+/* the bits a descriptor may set: any other is refused where the descriptor is validated (launch and plan alike) */
+#define ABX_TUNE_BITS_ (ABX_TUNE_NO_REMAP | ABX_TUNE_GTAIL_2WALK | ABX_TUNE_DUAL_1WALK | ABX_TUNE_TILE_ONLY | ABX_TUNE_AS_DUAL)
+#ifdef ABX_AS_ABLATE
+#define ABX_TUNE_LIVE_MASK (ABX_TUNE_BITS_ | ABX_TUNE_ABLATE_MASK)
+#else
+#define ABX_TUNE_LIVE_MASK ABX_TUNE_BITS_
+#endif
 int abx_gemm(const AbxGemm* desc, hipStream_t stream);
 /* Two GEMMs over the SAME rows in one launch: `main_gemm` a plain-store split-f16 problem with N % 128 == 0 (k-contiguous fp32 A), `side_gemm` a
  * skinny (N <= 32) transposed-store projection - TriangleAttention's q | k | v | gate projection and its pair bias, which both read
@@ -439,8 +440,6 @@ int abx_assemble_seq(const float* seq_static, long long ss_b, const float* aa_ta
 int abx_assemble_pair(const float* pair_static, long long ps_b, const float* temb, const float* prev_pair,
                       const float* gamma, const float* beta, const long long* prev_pos, const float* pos_table, float* out,
                       float* stats_out, int B, int L, int C, int E, hipStream_t stream);
-/* OuterProductMean features (seqformer.py:400-409): feat[b,i,j] = [ left[b,j]*right[b,i] | left[b,j]-right[b,i] ];
- * left/right rows have stride ld floats */
 /* Pair-representation assembly AND the sequence attention's pair bias in one pass over the pair rows (round 6; seqformer.py:193-223 + :324-333):
  * out = z0 as abx_assemble_pair writes it (C = 128, E = 32: 192 channels) and biasT[b][h][i*L + j] = Linear(LayerNorm(z0[b,i,j,:]))[h] for 32 heads -
  * what abx_gemm computes from z0 with a folded LayerNorm (w_planes = abx_split_weights_f16 planes [12][2][32][16] of the gamma-scaled weight with
@@ -450,6 +449,8 @@ int abx_assemble_pair_bias(const float* pair_static, long long ps_b, const float
                            const float* beta, const long long* prev_pos, const float* pos_table, float* out, const unsigned short* w_planes,
                            int w_exp, const float* csum, const float* bias, float ln_eps, float* biasT, int B, int L, int* range_flag,
                            int range_tag, hipStream_t stream);
+/* OuterProductMean features (seqformer.py:400-409): feat[b,i,j] = [ left[b,j]*right[b,i] | left[b,j]-right[b,i] ];
+ * left/right rows have stride ld floats */
 int abx_opm_features(const float* left, const float* right, long long ld, float* feat, int B, int L, int C,
                      hipStream_t stream);
 /* OuterProductMean without its feature tensor (seqformer.py:395-411; round 6): z[b,i,j,:] += out_proj([l_j * r_i | l_j - r_i]) evaluated as

@@ -145,6 +145,77 @@ def test_abx_no_dual_as_switches_the_name_too():
     assert _child('dual', 'ABX_NO_DUAL_AS') == 'gemm3_dual_kernel<128, 96, 32, 96, 3>'
 
 
+# ---- AbxGemm.tune: the guard of gemm_prepare (ABX_TUNE_LIVE_MASK) ---------------------------------------------------------------------
+RETIRED_OR_UNKNOWN = (2, 4, 6, 8, 14, 16, 32, 256, 512, 1024, 1536, 32768, 4096, 8192, 1 << 16, 1 << 30)
+
+
+def _refused(main, side=None):
+    from abx_amd import _lib
+    rc, name = _plan(main, side)
+    msg = _lib.load().abx_last_error_string()
+    return rc < 0 and name == '' and b'tune' in msg, (rc, name, msg)
+
+
+def _tune_cases():
+    import pytest
+    return pytest.mark.parametrize('tune', RETIRED_OR_UNKNOWN)
+
+
+@_tune_cases()
+def test_retired_and_unknown_tune_values_are_refused(tune):
+    """Every value of the list names a retired variant ("Retired GEMM variants"), the ABLATE field of a library built without it, or
+    no variant at all: refused with ABX_ERR_ARG, no name, and a text that says `tune`."""
+    g = _ln_gemm(ROWS, 768)
+    g.tune = tune
+    ok, got = _refused(g)
+    assert ok, (tune, got)
+
+
+@_tune_cases()
+def test_retired_and_unknown_tune_values_are_refused_on_the_side_descriptor(tune):
+    """The same through abx_gemm_side's route (main + side, the bit on the side descriptor)."""
+    s = _side(ROWS)
+    s.tune = tune
+    ok, got = _refused(_ln_gemm(ROWS, 768), s)
+    assert ok, (tune, got)
+
+
+def test_live_tune_bits_are_accepted_and_mean_what_they_meant():
+    for tune, name in ((2048, TILE), (1, 'gemm_as_kernel<0, false, 0, false>'), (0, 'gemm_as_kernel<0, false, 0, false>'), (2048 | 1, TILE)):
+        g = _ln_gemm(ROWS, 768)
+        g.tune = tune
+        assert _plan(g) == (0, name), tune
+
+
+def _transition(M):
+    """The fused two-layer transition: LayerNorm-folded 192 -> 768, relu, 768 -> 192 from planes in the permuted k order."""
+    g = _ln_gemm(M, 768)
+    g.mlp, g.act, g.N2 = 1, 1, 192
+    g.B2_split, g.sB23n, g.sB23p, g.sB23k, g.bias2 = 12 * P, 16, 16 * 192, 32 * 192, 13 * P
+    g.sCm = 192
+    return g
+
+
+def test_defaults_name_the_same_kernels_where_a_variant_used_to_hang():
+    assert _plan(_side(ROWS)) == (0, 'gemm3_kernel<128, 32, 32, 32, 0, true, 6>')
+    assert _plan(_transition(ROWS)) == (0, 'gemm3_mlp_kernel<2>')
+
+
+def test_abx_gemm_tune_with_a_retired_value_fails_at_the_first_plan():
+    """An ABX_GEMM_TUNE left over from an old recipe (512 was the narrow ring) fails at the first GEMM, with the guard's message."""
+    out = _child('tune_plain', 'ABX_GEMM_TUNE', '512')
+    assert out.startswith('refused:') and 'tune' in out and '512' in out, out
+
+
+def test_abx_gemm_tune_with_a_retired_bit_fails_at_the_first_plan():
+    out = _child('tune_plain', 'ABX_GEMM_TUNE', '256')
+    assert out.startswith('refused:') and 'tune' in out and '256' in out, out
+
+
+def test_abx_gemm_tune_tile_only_names_the_tile_kernel():
+    assert _child('tune_plain', 'ABX_GEMM_TUNE', '2048') == TILE
+
+
 if __name__ == '__main__':
     sys.path.insert(0, ROOT)
     from abx_amd import ops
@@ -152,3 +223,9 @@ if __name__ == '__main__':
         print(ops.gemm_as_kernel_name(_ln_gemm(ROWS, 768)))
     elif sys.argv[1] == 'dual':
         print(ops.gemm_kernel_name(352 * 352, 192, 128, 100, a_kcontig=False, split=True, exact=2, dual=True))
+    elif sys.argv[1] == 'tune_plain':           # the plain case through the product's name helper, which fills in the process's ABX_GEMM_TUNE
+        from abx_amd._lib import AbxHipError
+        try:
+            print(ops.gemm_kernel_name(ROWS, 768, 192, 1, split=True, exact=2))
+        except AbxHipError as e:
+            print('refused:', e)

@@ -109,18 +109,6 @@ def main():
             A, W, C = r(M, K), r(K, N) / K ** 0.5, torch.empty(M, N, device=DEV)
             ms = timeit(lambda: ops.gemm(A, W, C))
             rec(f'gemm seq-track {M}x{N}x{K}', ms, 2.0 * M * N * K)
-    if only and 'tune' in only:
-        z = r(M2, 192)
-        stats = ops.row_stats(z)
-        for N, K in ((768, 192), (192, 768), (192, 192)):
-            A, W, C = r(M2, K), r(K, N) / K ** 0.5, torch.empty(M2, N, device=DEV)
-            bias, csum = r(N), r(N)
-            for tune in range(8):
-                kw = dict(bias=bias, tune=tune)
-                if K == 192:
-                    kw['ln'] = (stats, csum)
-                ms = timeit(lambda: ops.gemm(A, W, C, **kw))
-                rec(f'gemm {N}x{K} tune={tune} (noremap={tune & 1}, variant={tune >> 1})', ms, 2.0 * M2 * N * K)
     if only and 'ksweep' in only:
         for N in (192, 768, 128):
             for K in (16, 64, 192, 384, 768, 1536):
@@ -131,18 +119,11 @@ def main():
         for N, K in ((768, 192), (192, 768), (192, 192), (192, 128), (448, 192)):
             A, W, C = r(M2, K), r(K, N) / K ** 0.5, torch.empty(M2, N, device=DEV)
             bias, csum = r(N), r(N)
-            for tune, tag in ((0, 'default'), (2, '128x128'), (1, 'default, no xcd remap'), (3, '128x128 no remap')):
+            for tune, tag in ((0, 'default'), (1, 'default, no xcd remap')):
                 ms = timeit(lambda: ops.gemm(A, W, C, bias=bias, ln=(None, csum), tune=tune))
                 rec(f'shape N={N} K={K} {tag}', ms, 2.0 * M2 * N * K, 4.0 * M2 * (N + K))
             ms = timeit(lambda: ops.gemm(A, W, C, bias=bias, ln=(None, csum), exact=True))
             rec(f'shape N={N} K={K} exact fp32', ms, 2.0 * M2 * N * K, 4.0 * M2 * (N + K))
-    if only and 'ablate' in only:
-        for N, K in ((192, 1536), (768, 768)):
-            A, W, C = r(M2, K), r(K, N) / K ** 0.5, torch.empty(M2, N, device=DEV)
-            for tune, tag in ((0, 'full'), (16, 'no MFMA'), (32, 'no A dma'), (64, 'no W dma'), (96, 'no dma'), (128, 'no split'),
-                              (16 + 128, 'no MFMA, no split'), (96 + 128, 'MFMA + LDS reads only'), (2, '128x128 tile')):
-                ms = timeit(lambda: ops.gemm(A, W, C, tune=tune))
-                rec(f'ablate N={N} K={K} {tag}', ms, 2.0 * M2 * N * K)
     if only and 'tm' in only:
         z = r(M2, 192); z3 = z.view(Bc, LL, 192)
         G = r(Bc, LL, 448)

@@ -1,4 +1,5 @@
 """Ablations of the A-stationary GEMM (probe library built with -DABX_AS_ABLATE; tune bits 12-13: 1 no slice stores, 2 no MFMA, 3 no weight DMA in the walk).
+The define goes to gemm_as.hip (the ablated kernels) AND gemm.hip (the tune guard: ABX_TUNE_LIVE_MASK admits bits 12-13 only when built with it).
     python tools/ab_lib.py tools/probes/bin/libabx_hip_abl.so tools/probes/kb_as_abl.py [Bc]"""
 import sys
 import torch
