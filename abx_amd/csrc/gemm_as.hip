@@ -28,6 +28,7 @@
 #include "abx_hip.h"
 #include "split_dev.h"
 #include "grid_map.h"
+#include "gemm3_mainloop.h"      // ABX_SPLIT_MIN_TILES: the route rule of abx_gemm3_dispatch
 
 namespace {
 
@@ -982,6 +983,329 @@ int as_dual_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan) {
     return 0;
 }
 
+// ---- the pair Transition as an A-stationary fused MLP ---------------------------------------------------------------------------------------
+//     out = relu(LN(z) W1 + b1) W2 + b2 + z          K = 192 channels, hidden 768, 192 outputs                      (seqformer.py:358-376)
+// gemm3_mlp_kernel gives a block 128 rows and walks their z rows once per hidden chunk of 128: six times the DMA, the fragment reads and the
+// f16 split of all 192 channels.  Here a block owns 64 rows: they arrive in one burst and are split in place exactly as in as_block (the
+// statistics + split of k-tile s + 2 ride in step s of the first chunk), and every chunk reads its A fragments from that image.
+// 4 waves = 2 (row halves wm) x 2 (hidden halves wn).  A chunk of 128 hidden channels is 24 UNIFORM steps of six MFMAs per wave on an 8 KB
+// weight tile, streamed by the column-1 waves through one ring of three slots with a counted wait (four instructions per step and wave):
+//   steps 0 .. 11   GEMM 1 with swapped operands: wave (wm, wn) accumulates H^T of the hidden channels 64 wn .. 64 wn + 63 of the chunk for
+//                   its 32 rows (lane = row: two 32 x 32 tiles), W1 tile [2][128][16] of k-tile s;
+//   step 12         folded LayerNorm (lane-local statistics), bias, ReLU and the split of the 32 registers into the pieces of FOUR k-tiles of
+//                   GEMM 2 (the 2^4 lift of split2b: |h| >= 4094 -> NaN -> the range word), in place of the accumulators;
+//   steps 12 .. 23  GEMM 2: three column passes of 64 outputs x the wave's four hidden k-tiles, the pieces replayed from registers; the
+//                   tile [wn][2][64][16] holds, for either hidden half, the W2 k-tile its waves need.  96 accumulator registers: the
+//                   wave's PARTIAL sum over its hidden half of all 192 outputs.
+// After the last chunk the two waves of a row half exchange one half of their partial sums through the freed A region (each keeps 96
+// columns: partial(wn = 0) + partial(wn = 1), one addition per element whichever wave performs it) and run the epilogue of as_dual_block:
+// x 2^-(4 + b2_exp), bias, 4 x 4 quad transpose, + z read again from global memory (the pieces are 23-bit images), 16-byte stores.
+// The sum over the hidden channels is split in two: results are NOT bit-identical to gemm3_mlp_kernel (they agree at fp32 rounding of the
+// hidden sum).  The kernel is therefore chosen by the shape class alone, never by M: a sample's bits do not depend on the launch.
+constexpr int AM_NH = 768, AM_N2 = 192, AM_NCH = AM_NH / 128, AM_NU = 24;
+constexpr int AM_STAGE = 8192;                                       // W1: [2][128][16] f16; W2: [hidden half][2][64][16] f16
+constexpr int AM_OFF_RING = AS_A;
+constexpr int AM_OFF_ST = AM_OFF_RING + 3 * AM_STAGE;                // [2][64]: mean - shift | rstd cs
+constexpr int AM_OFF_CONST = AM_OFF_ST + 2 * 64 * 4;                 // [2][768]: ln_csum | bias of the first layer
+constexpr int AM_LDS = AM_OFF_CONST + 2 * AM_NH * 4;                 // 80 384 (63 granules of 1 280: two blocks per CU)
+constexpr int AM_XCH = 3 * 16 * 64 * 4;                              // exchange image of one wave: three 32 x 32 tiles, 12 288
+static_assert(AM_LDS <= 81920 && 4 * AM_XCH <= AS_A && AM_NU % 3 == 0 && AM_NU % 2 == 0, "two blocks per CU; ring slot and fragment set of a step are constants");
+
+// the rendezvous of a GEMM 2 step (as_rendezvous: this step's weight fragments pass through the statement).  VM: a streaming wave
+template <bool VM>
+__device__ __forceinline__ void am_rendezvous2(u32x4 (&fb)[2][2]) {
+    if constexpr (VM) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" : "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]) : : "memory");
+    else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]) : : "memory");
+}
+
+template <bool EDGE>
+__device__ __forceinline__ void as_mlp_block(const AbxGemm& g, char* lds, int mt, int b) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave >> 1, wn = wave & 1, h = lane >> 5;
+    const int m0 = mt * AS_BM;
+    float* st = reinterpret_cast<float*>(lds + AM_OFF_ST);
+    const float* cc = reinterpret_cast<const float*>(lds + AM_OFF_CONST);
+
+    // ---- weight tiles: wave (wm, 1) fetches 4 KB of a step's tile, four 1 KB chunks of 32 rows: plane wm of W1, hidden half wm of W2
+    const char* w1base = reinterpret_cast<const char*>(g.B_split);
+    const char* w2base = reinterpret_cast<const char*>(g.B2_split);
+    const unsigned w1k = (unsigned)(g.sB3k * 2), w2k = (unsigned)(g.sB23k * 2);     // (bytes per k-tile; the dispatch bounds the whole walk by 2^32)
+    const unsigned w1chunk = (unsigned)(32 * g.sB3n * 2), w1tile = (unsigned)(128 * g.sB3n * 2);
+    const unsigned w2chunk = (unsigned)(32 * g.sB23n * 2), w2plane = (unsigned)(g.sB23p * 2);
+    unsigned woff1, woff2;
+    {
+        const int row = lane >> 1, half = (lane & 1) ^ ((row >> 3) & 1);
+        woff1 = (unsigned)((wm * g.sB3p + (long long)row * g.sB3n + 8 * half) * 2);
+        woff2 = (unsigned)(((long long)row * g.sB23n + 8 * half) * 2);
+    }
+    // tile of step u of chunk c -> ring slot
+    auto issue_w = [&](int c, auto u_, int slot) __attribute__((always_inline)) {
+        constexpr int u = decltype(u_)::value;
+        char* dst = lds + AM_OFF_RING + slot * AM_STAGE + wm * 4096;
+        // (the source of a step is formed AT the step, 32-bit scalar arithmetic on an opaque stride: left to itself the compiler keeps the 24
+        // 64-bit sources of a chunk as loop-carried pointers - some 50 scalar registers, spilled to vector lanes)
+        if constexpr (u < AS_NK) {
+            unsigned ks = w1k;
+            asm volatile("" : "+s"(ks));
+            const char* src = w1base + (u * ks + (unsigned)c * w1tile);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) glds16(src + i * w1chunk + vgpr32(woff1), dst + i * 1024);
+        } else {
+            constexpr int pass = (u - AS_NK) >> 2, q = (u - AS_NK) & 3;
+            unsigned ks = w2k;
+            asm volatile("" : "+s"(ks));
+            const char* src = w2base + ((unsigned)(8 * c + 4 * wm + q) * ks + pass * 2 * w2chunk);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) glds16(src + (i >> 1) * w2plane + (i & 1) * w2chunk + vgpr32(woff2), dst + i * 1024);
+        }
+    };
+
+    // ---- prologue.  Column 0: the z burst, statistics + split of its first two k-tiles.  Column 1: column constants, three weight tiles
+    const float cs1 = __builtin_ldexpf(1.0f, -ABX_F16_A_EXP - g.b_exp), inv_cs1 = __builtin_ldexpf(1.0f, ABX_F16_A_EXP + g.b_exp);
+    AsConv cv;
+    char* a_half = lds + wm * AS_HALF;
+    if (wn == 0) {
+        as_issue_a(g, lds, m0, b, wm);
+        as_conv_init(cv, g);
+        wait_vm<20>();
+        as_conv_ktile<true>(cv, a_half);
+        as_conv_ktile<false>(cv, a_half + AS_KT);
+    } else {
+        const float* c0 = wm ? g.bias : g.ln_csum;
+#pragma unroll
+        for (int i = 0; i < AM_NH / 64; ++i)
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(c0 + i * 64 + lane), (lds_ptr_t)(lds + AM_OFF_CONST + wm * (AM_NH * 4) + i * 256), 4, 0, 0);
+        issue_w(0, IC<0>{}, 0);
+        issue_w(0, IC<1>{}, 1);
+        issue_w(0, IC<2>{}, 2);
+        wait_vm<8>();                                        // the constants and tile 0 have landed
+    }
+    __syncthreads();
+
+    // ---- fragments
+    const int offAf = wm * AS_HALF + plane_off<32>(0, lane & 31, h);                               // + kt * AS_KT + p * 1024
+    const int offB1 = AM_OFF_RING + plane_off<128>(0, wn * 64 + (lane & 31), h);                   // + slot * AM_STAGE + p * 4096 + j * 1024
+    const int offB2 = AM_OFF_RING + wn * 4096 + plane_off<64>(0, lane & 31, h);                    // + slot * AM_STAGE + p * 2048 + t * 1024
+    u32x4 fa[2][2], fb[2][2][2];
+    auto read_frags = [&](int set, auto u_, int slot) __attribute__((always_inline)) {
+        constexpr int u = decltype(u_)::value;
+        if constexpr (u < AS_NK) {
+#pragma unroll
+            for (int p = 0; p < 2; ++p) fa[set][p] = *reinterpret_cast<const u32x4*>(lds + u * AS_KT + offAf + p * 1024);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int p = 0; p < 2; ++p) fb[set][j][p] = *reinterpret_cast<const u32x4*>(lds + offB1 + slot * AM_STAGE + p * 4096 + j * 1024);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int p = 0; p < 2; ++p) fb[set][t][p] = *reinterpret_cast<const u32x4*>(lds + offB2 + slot * AM_STAGE + p * 2048 + t * 1024);
+        }
+    };
+
+    f32x16 acc1[2], acc2[AM_N2 / 32];
+    u32x4 hf[4][2];                                             // pieces of the wave's four hidden k-tiles of the chunk: [k-tile][a0 | a1]
+#pragma unroll
+    for (int t = 0; t < AM_N2 / 32; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc2[t][r] = 0.f;
+
+    // H^T tiles -> pieces.  Register r of tile j in lane (row, h) = hidden channel 32 j + 8 (r >> 2) + 4 h + (r & 3): the registers 8 s .. 8 s + 7
+    // are the k slots of the k-tile 2 j + s in the permuted order of the W2 planes (gemm3_mlp_block).  st holds rstd cs, the sums go in as csum / cs
+    auto hidden_pieces = [&](int c) __attribute__((always_inline)) {
+        const float dm = st[wm * 32 + (lane & 31)], rs = st[64 + wm * 32 + (lane & 31)];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                float v[8];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int hc = c * 128 + wn * 64 + j * 32 + 8 * (2 * s + q) + 4 * h;
+                    const f32x4 cs = *reinterpret_cast<const f32x4*>(cc + hc), bi = *reinterpret_cast<const f32x4*>(cc + AM_NH + hc);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float x = rs * (acc1[j][8 * s + 4 * q + e] - dm * (cs[e] * inv_cs1)) + bi[e];
+                        v[4 * q + e] = relu_keep_nan(x);
+                    }
+                }
+                unsigned q0[4], q1[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) split2b(v[2 * e], v[2 * e + 1], q0[e], q1[e]);
+                hf[2 * j + s][0] = u32x4{q0[0], q0[1], q0[2], q0[3]};
+                hf[2 * j + s][1] = u32x4{q1[0], q1[1], q1[2], q1[3]};
+            }
+    };
+
+    // ---- one step; set = u & 1 holds its fragments, ring slot u % 3 its tile
+    auto step = [&](int c, auto u_, auto first_, auto role_) __attribute__((always_inline)) {
+        constexpr int u = decltype(u_)::value, role = decltype(role_)::value, set = u & 1;
+        constexpr bool first = decltype(first_)::value != 0;
+        // the tile of the next step has landed (own DMA: the tile after it, four instructions, may stay in flight), own LDS reads returned
+        // (a GEMM 2 step has no A fragments: the hidden pieces are registers)
+        if constexpr (u >= AS_NK) am_rendezvous2<role == 1>(fb[set]);
+        else if constexpr (role == 0) as_rendezvous_free(fa[set], fb[set]);
+        else as_rendezvous<4>(fa[set], fb[set]);
+        if constexpr (role == 1) {
+            // tile of step s + 3 -> the slot step s has just left (beyond the walk: a duplicate nobody reads, uniform instruction counts)
+            issue_w(min(u + 3 >= AM_NU ? c + 1 : c, AM_NCH - 1), IC<(u + 3) % AM_NU>{}, u % 3);
+        } else if constexpr (first && u < AS_NK - 2) {
+            wait_vm<2 * (AS_NK - 3 - u)>();
+            as_conv_ktile<false>(cv, a_half + (u + 2) * AS_KT);
+            if constexpr (u == AS_NK - 3) as_conv_finish(cv, st, wm, g.ln_eps, cs1);
+        }
+        read_frags((u + 1) & 1, IC<(u + 1) % AM_NU>{}, (u + 1) % 3);
+        if constexpr (u < AS_NK) {
+            u32x4 p2[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) p2[j] = f16x8_lo(fb[set][j][0]);
+            // a1 p2, a0 p1, a0 p0 (smallest first), operands swapped: the accumulators hold H^T
+            if constexpr (u == 0) {
+                const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc1[j] = mfma_split(p2[j], fa[set][1], z);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc1[j] = mfma_split(p2[j], fa[set][1], acc1[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc1[j] = mfma_split(fb[set][j][1], fa[set][0], acc1[j]);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc1[j] = mfma_split(fb[set][j][0], fa[set][0], acc1[j]);
+        } else {
+            if constexpr (u == AS_NK) hidden_pieces(c);
+            constexpr int pass = (u - AS_NK) >> 2, q = (u - AS_NK) & 3;
+            // a1 p0, a0 p1, a0 p0 (smallest first; the hidden went in as h 2^4: no p2)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) acc2[2 * pass + t] = mfma_split(hf[q][1], fb[set][t][0], acc2[2 * pass + t]);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) acc2[2 * pass + t] = mfma_split(hf[q][0], fb[set][t][1], acc2[2 * pass + t]);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) acc2[2 * pass + t] = mfma_split(hf[q][0], fb[set][t][0], acc2[2 * pass + t]);
+        }
+    };
+
+    read_frags(0, IC<0>{}, 0);
+    auto walk = [&](auto role_) __attribute__((always_inline)) {
+        static_for<0, AM_NU>([&](auto u_) { step(0, u_, IC<1>{}, role_); });
+        for (int c = 1; c < AM_NCH; ++c) static_for<0, AM_NU>([&](auto u_) { step(c, u_, IC<0>{}, role_); });
+    };
+    if (wn == 0) walk(IC<0>{});
+    else walk(IC<1>{});
+
+    // ---- the residual rows of this lane's stores (after the quad transpose: row 8 rq + 4 h + (lane & 3), four consecutive columns per tile)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // (every DMA still in flight is a duplicate; drained before the ring's block ends)
+    const float* rd = g.resid + (long long)b * g.sRb;
+    float* Cb = g.C + (long long)b * g.sCb;
+    f32x4 rv[4][3];
+    bool row_ok[4];
+#pragma unroll
+    for (int rq = 0; rq < 4; ++rq) {
+        const int m = m0 + wm * 32 + 8 * rq + 4 * h + (lane & 3);
+        row_ok[rq] = !EDGE || m < g.M;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const int n = wn * 96 + t * 32 + ((lane & 31) >> 2) * 4;
+            rv[rq][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (row_ok[rq]) rv[rq][t] = *reinterpret_cast<const f32x4*>(rd + (long long)m * g.sRm + n);
+        }
+    }
+    float bias2[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) bias2[t] = g.bias2[wn * 96 + t * 32 + (lane & 31)];
+
+    // ---- the partial sums of the other 96 columns -> the partner wave, through the A region (every wave has left the walk: no reader of it;
+    // no vector-memory wait at the barriers: the residual loads stay in flight across the exchange)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    const float cs2 = __builtin_ldexpf(1.0f, -4 - g.b2_exp);    // (the hidden went in as h 2^4: split2b)
+    bool bad = false;
+    auto tail = [&](auto wn_) __attribute__((always_inline)) {
+        constexpr int cw = decltype(wn_)::value;                // this wave keeps the tiles 3 cw .. 3 cw + 2
+        f32x4* xo = reinterpret_cast<f32x4*>(lds + wave * AM_XCH);
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const f32x16& a = acc2[3 * (1 - cw) + t];
+                xo[(t * 4 + rq) * 64 + lane] = (f32x4){a[4 * rq], a[4 * rq + 1], a[4 * rq + 2], a[4 * rq + 3]};
+            }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        const f32x4* xi = reinterpret_cast<const f32x4*>(lds + (wave ^ 1) * AM_XCH);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const int n = cw * 96 + t * 32 + ((lane & 31) >> 2) * 4;
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const f32x4 pv = xi[(t * 4 + rq) * 64 + lane];
+                float x[4], o[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) x[c] = (acc2[3 * cw + t][4 * rq + c] + pv[c]) * cs2 + bias2[t];
+                quad_transpose(x, o);
+                f32x4 ov;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    ov[c] = o[c] + rv[rq][t][c];
+                    bad |= row_ok[rq] && __builtin_amdgcn_classf(ov[c], 0x207);
+                }
+                const int m = m0 + wm * 32 + 8 * rq + 4 * h + (lane & 3);
+                if (row_ok[rq]) *reinterpret_cast<f32x4*>(Cb + (long long)m * g.sCm + n) = ov;
+            }
+        }
+    };
+    if (wn == 0) tail(IC<0>{});
+    else tail(IC<1>{});
+    if (g.range_flag && __any(bad) && lane == 0) atomicOr(g.range_flag, g.range_tag);
+}
+
+__global__ __launch_bounds__(256, 2) void gemm_as_mlp_kernel(const AbxGemm g) {
+    extern __shared__ __attribute__((aligned(16))) float as_smem[];
+    char* lds = reinterpret_cast<char*>(as_smem);
+    const ClockProbe probe(g.clock_probe);
+    const unsigned ntm = (unsigned)((g.M + AS_BM - 1) / AS_BM);
+    const unsigned wgid = xcd_contiguous(blockIdx.x, gridDim.x);
+    const int b = (int)(wgid / ntm), mt = (int)(wgid - (unsigned)b * ntm);
+    if ((mt + 1) * AS_BM > g.M) as_mlp_block<true>(g, lds, mt, b);
+    else as_mlp_block<false>(g, lds, mt, b);
+    probe.finish();
+}
+
+// The mlp descriptor of the pair Transition -> gemm_as_mlp_kernel.  Returns 1 when the tile kernel (gemm3_mlp_kernel) keeps it.
+// INVARIANT: the choice depends on the SHAPE CLASS only (K = 192, hidden 768, 192 outputs, a residual, the split-f16 route) and never on M: the
+// two kernels differ in the order of the hidden sum, and a sample's bits must not depend on how many samples share a launch.
+int as_mlp_dispatch(const AbxGemm& g, hipStream_t st, int* rc, AbxPlan* plan) {
+    static const bool off = abx_env_on("ABX_NO_MLP_AS");        // (A / B measurements: the tile kernel everywhere)
+    if (off) return 1;
+    if (g.exact == 1 || g.K != AS_NK * 16 || g.N != AM_NH || g.N2 != AM_N2) return 1;
+    if (!g.A || g.A_split || g.sAk != 1 || !g.B_split || !g.B2_split || !g.b_f16) return 1;
+    if (!g.ln_csum || g.ln_stats || !g.bias || !g.bias2 || !g.resid || !g.C) return 1;
+    if (g.act != 1 || g.alpha != 1.0f || g.gate || g.glu || g.rowscale || g.out_ln_w || g.C_split || g.c_transposed || g.a_relu || g.A2 ||
+        g.a_pair_transpose > 0 || g.a_pair || g.c_pair || g.pair_Lp != 0 || g.c_split_tile || g.batch_inner || g.c_planes_from)
+        return 1;
+    if (!g.c_vec_ok || !g.r_vec_ok) return 1;
+    // the route of abx_gemm3_dispatch: small launches whose arithmetic class the caller has not fixed stay on the exact kernels
+    if (g.exact != 2 && (((long long)g.M + 127) / 128) * (AM_NH / 128) * g.batch < ABX_SPLIT_MIN_TILES) return 1;
+    if (!rows_ok(g.A, g.sAm, g.sAb) || !planes_ok(g.B_split, g.sB3n, g.sB3p, g.sB3k, g.sB3b) || g.sB3b != 0) return 1;
+    if (!planes_ok(g.B2_split, g.sB23n, g.sB23p, g.sB23k) || !exp_ok(g.b_exp) || !exp_ok(g.b2_exp)) return 1;
+    // a block reads its own rows (burst, residual) before it stores them: C may BE the rows (in place) or lie apart, nothing in between
+    const long long rows = g.M;
+    auto apart_or_same = [&](const float* p, long long sb, long long sm) {
+        if (p == g.C && sb == g.sCb && sm == g.sCm) return true;
+        const float* c1 = g.C + (g.batch - 1) * g.sCb + (rows - 1) * g.sCm + AM_N2;
+        const float* p1 = p + (g.batch - 1) * sb + (rows - 1) * sm + AM_N2;
+        return !(g.C < p1 && p < c1);
+    };
+    if (!apart_or_same(g.A, g.sAb, g.sAm) || !apart_or_same(g.resid, g.sRb, g.sRm)) return 1;
+    // 32-bit per-lane DMA offsets
+    if (64LL * g.sAm >= (1LL << 30)) return 1;
+    if (g.sB3p + (long long)AM_NH * g.sB3n >= (1LL << 30) || g.sB23p + (long long)AM_N2 * g.sB23n >= (1LL << 30)) return 1;
+    if ((long long)AS_NK * g.sB3k >= (1LL << 31) || (long long)(AM_NH / 16) * g.sB23k >= (1LL << 31)) return 1;
+    const long long ntm = ((long long)g.M + AS_BM - 1) / AS_BM;
+    if (ntm * g.batch >= (1LL << 31)) return 1;
+    *rc = ABX_LAUNCH_LIT(plan, "abx_gemm(as, mlp)", &gemm_as_mlp_kernel, AM_LDS, dim3((unsigned)(ntm * g.batch)), dim3(256), AM_LDS, st, g);
+    return 0;
+}
+
 }  // namespace
 
 // Called by abx_gemm / abx_gemm_side (gemm.hip) with validated descriptors (vector flags filled).  side == nullptr: no side GEMM.
@@ -990,6 +1314,7 @@ int abx_gemm_as_dispatch(const AbxGemm& g, const AbxGemm* side, hipStream_t st, 
     static const bool off = abx_env_on("ABX_NO_GEMM_AS");       // (A / B measurements: always the tile kernels)
     if (off || (g.tune & ABX_TUNE_TILE_ONLY)) return 1;
     if (g.A2) return side ? 1 : as_dual_dispatch(g, st, rc, plan);    // the TriangleMultiplication tail
+    if (g.mlp == 1) return side ? 1 : as_mlp_dispatch(g, st, rc, plan);   // the pair Transition
     if (g.exact == 1 || !g.B_split || !g.b_f16 || g.A_split || !g.A || g.sAk != 1 || g.K != AS_NK * 16) return 1;
     if (g.A2 || g.out_ln_w || g.mlp || g.ln_stats || g.gate || g.resid || g.batch_inner || !g.ln_csum || !g.bias) return 1;
     if (g.act != 0 || g.alpha != 1.0f) return 1;

@@ -177,7 +177,11 @@ typedef struct AbxGemm {
      * DESIGN.md ("Retired GEMM variants").  Three retired fields keep their constant (FORCE 1-3, MLP_MINB1 4, NARROW_RING 9-10): their
      * kernels and dispatch lines are still compiled, unreachable behind the guard, for the reason given there.
      * Environment: ABX_NO_DUAL_AS set, not empty and not "0" keeps gemm3_dual_kernel for every dual descriptor of the process (A / B
-     * measurements); the on / off switches all read that way */
+     * measurements); the on / off switches all read that way.
+     * The pair Transition (mlp = 1 with K = 192, N = 768, N2 = 192, a residual, plain fp32 rows in place or apart from the output, split-f16
+     * route) takes gemm_as_mlp_kernel at ANY M - the choice is the shape class's, because that kernel sums the hidden channels in another
+     * order than gemm3_mlp_kernel and a sample's bits must not depend on the launch; bit 11 keeps gemm3_mlp_kernel for the call,
+     * ABX_NO_MLP_AS for the process */
     int tune;
     int c_planes_from, c_planes_group;             /* plain store, c_planes_from > 0: the output columns n >= c_planes_from leave as the B-side
                                                       OPERAND IMAGE of a following split-f16 product instead of fp32 - two float16 planes of

@@ -2,7 +2,7 @@
 """Launch ONE of the dominant kernels a few times at the bench geometry, for rocprofv3 --pmc passes (tools/pmc_run.sh).
     python tools/pmc_kernels.py <which> [Bc] [L]
 which: qkvg (LN -> 768, gemm3 128x128 tiles: tune 2048)  qkv (round 5: LN -> q | k | v 576 + pair-bias side, A-stationary kernel)
-       gtail (gated tail of the triangle attention, AbxGemm.mlp = 2)  mlp (fused transition)  trans2 (768 -> 192 + resid, gemm3 128x192)  glu (LN -> glu planes, transposed store)
+       gtail (gated tail of the triangle attention, AbxGemm.mlp = 2)  mlp / mlptile (fused transition: the default dispatch - gemm_as_mlp_kernel - / the 128-row tile kernel, tune 2048)  trans2 (768 -> 192 + resid, gemm3 128x192)  glu (LN -> glu planes, transposed store)
        contract (plane x plane)  projout (channel-major A, gate, resid)  tri (triangle attention)  ipa (IPA attention)
        trif / trif1 (row-fused triangle attention on the z rows, slot order (b, row, h) / (b, h, row))  pairbias (the 4-column pair-bias projection alone)
        dualas / dualtile (the tri-mul tail as a dual GEMM: the A-stationary kernel forced, tune 16384 / the 128 x 96 tile kernel, tune 2048)"""
@@ -39,12 +39,12 @@ elif which == 'gtail':
     bg, cs, bo = r(192), Wg.sum(0).contiguous(), r(192)
     for _ in range(REPS):
         ops.gemm(z, Wg, z, bias=bg, ln=(None, cs), B3=w3, act=2, gate=o, resid=z, exact=2, mlp=(wo3p, bo))
-elif which == 'mlp':
+elif which in ('mlp', 'mlptile'):
     z, W1, W2 = r(M2, 192), r(192, 768) / 14, r(768, 192) / 28
     W13, W23p = ops.split_weights(W1), ops.split_weights(ops.permute_k16(W2))
     b1, b2, cs = r(768), r(192), W1.sum(0).contiguous()
     for _ in range(REPS):
-        ops.gemm(z, W1, z, bias=b1, ln=(None, cs), B3=W13, act=1, resid=z, exact=2, mlp=(W23p, b2))
+        ops.gemm(z, W1, z, bias=b1, ln=(None, cs), B3=W13, act=1, resid=z, exact=2, mlp=(W23p, b2), tune=2048 if which == 'mlptile' else None)
 elif which == 'trans2':
     h, W, z = r(M2, 768), r(768, 192) / 28, r(M2, 192)
     W3 = ops.split_weights(W)
