@@ -163,6 +163,11 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
 // Gates: 1 / (1 + e^-x) as v_exp_f32 + v_rcp_f32 (1 ulp each: relative error < 3e-7) - 4 VALU instructions instead of the ~18 of
 // expf + IEEE division; the pair stack evaluates ~47 G gates per step (glu, final gate, attention gates), beside the MFMAs
 __device__ __forceinline__ float sigmoidf_(float x) {

@@ -20,6 +20,7 @@
 #include "abx_hip.h"
 #include "peptide_dev.h"
 #include "reduce_dev.h"
+#include "residue_rules.h"
 #include "structure_dev.h"
 #include <cmath>
 
@@ -31,11 +32,7 @@ constexpr int NT = 256;                // threads of every workgroup
 constexpr int NW = NT / 64;
 constexpr int J_CHUNK = 2048;          // default and largest chunk of the j-list in LDS
 constexpr int MAX_ROWS = 2048;         // antibody rows of a structure
-constexpr double FIXED_ONE = 1073741824.0;     // 2^30
 constexpr double CYS_SS2 = 6.25;
-// residue types (residue_constants.restypes)
-constexpr int T_ARG = 1, T_ASN = 2, T_ASP = 3, T_CYS = 4, T_GLU = 6, T_GLY = 7, T_HIS = 8, T_LYS = 11, T_MET = 12, T_PRO = 14, T_SER = 15,
-              T_THR = 16, T_TRP = 17;
 // bits of a row's info word: type in bits 0-4
 constexpr int R_PRESENT = 1 << 5, R_EXPOSED = 1 << 6, R_LINK = 1 << 7, R_REGION = 1 << 8, R_CDR = 1 << 9, R_SG = 1 << 10;
 
@@ -58,16 +55,14 @@ __device__ __forceinline__ Block block_of(void* ws, int b, int Lab) {
     return k;
 }
 
-__device__ __forceinline__ bool is_cdr(int c) { return c == 1 || c == 3 || c == 5 || c == 8 || c == 10 || c == 12; }
-
 __global__ __launch_bounds__(NT) void dev_weigh_kernel(const AbxDevelopabilityArgs a, void* ws) {
-    __shared__ int wcnt[NW][2];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ int wcnt[NW * 2];
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int N14 = a.Lab * 14;
     const Structure s(a, b);
     const Block k = block_of(ws, b, a.Lab);
     const int* pts = a.points + (long long)b * a.L * 28;
-    int ni = 0, nj = 0;
+    int n[2] = {0, 0};                                  // the i-list and the j-list so far
     for (int base = 0; base < N14; base += NT) {
         const int at = base + tid;
         bool counted = false;
@@ -83,29 +78,18 @@ __global__ __launch_bounds__(NT) void dev_weigh_kernel(const AbxDevelopabilityAr
             }
         }
         const bool weighted = w != 0;
-        const unsigned long long bi = __ballot(counted), bj = __ballot(weighted);
-        __syncthreads();                                // the previous chunk's counts have been read
-        if (lane == 0) {
-            wcnt[wv][0] = __popcll(bi);
-            wcnt[wv][1] = __popcll(bj);
-        }
-        __syncthreads();
-        int ii = ni + lanes_below(bi), ij = nj + lanes_below(bj);
-        for (int v = 0; v < NW; ++v) {
-            ii += v < wv ? wcnt[v][0] : 0;
-            ij += v < wv ? wcnt[v][1] : 0;
-            ni += wcnt[v][0];
-            nj += wcnt[v][1];
-        }
-        if (counted) k.ilist[ii] = p;                   // ii < N14: at most one entry per slot
+        const unsigned long long bal[2] = {__ballot(counted), __ballot(weighted)};
+        int rank[2];
+        block_rank<NW, 2>(bal, wcnt, rank, n);
+        if (counted) k.ilist[rank[0]] = p;              // below N14: at most one entry per slot
         if (weighted) {
-            k.jxyz[ij] = p;
-            k.jw[ij] = w;
+            k.jxyz[rank[1]] = p;
+            k.jw[rank[1]] = w;
         }
     }
     if (tid == 0) {
-        k.counts[0] = ni;
-        k.counts[1] = nj;
+        k.counts[0] = n[0];
+        k.counts[1] = n[1];
     }
 }
 
@@ -142,8 +126,6 @@ __global__ __launch_bounds__(NT) void dev_pair_kernel(const AbxDevelopabilityArg
     }
     if (mine) k.sap[i] = sap;
 }
-
-__device__ __forceinline__ void lds_add(unsigned long long* p, long long v) { atomicAdd(p, (unsigned long long)v); }
 
 __global__ __launch_bounds__(NT) void dev_reduce_kernel(const AbxDevelopabilityArgs a, void* ws) {
     __shared__ unsigned long long rsum[MAX_ROWS];       // sum of SAP_i of the row (two's complement)
@@ -199,17 +181,12 @@ __global__ __launch_bounds__(NT) void dev_reduce_kernel(const AbxDevelopabilityA
             atomicAdd(&cnt[4], 1);
             if (f & R_REGION) atomicAdd(&cnt[5], 1);
         }
-        const int ch = (aa == T_LYS || aa == T_ARG ? 1 : 0) - (aa == T_ASP || aa == T_GLU ? 1 : 0);
+        const int ch = type_charge(aa);
         if (ch) atomicAdd(&cnt[a.chain_id[r] == heavy ? 6 : 7], ch);
         if (aa == T_HIS) atomicAdd(&cnt[9], 1);
-        const double ref = a.ref[aa];
-        double rel = 0.0;
-        for (int sl = 4; sl < 14; ++sl) {
-            const bool counted = a.radius[aa * 14 + sl] > 0.f && s.exists(r, sl, aa);
-            rel = rel + (double)(counted ? pts[2 * (r * 14 + sl)] : 0) * a.a[aa * 14 + sl];
-            if (sl == 5 && counted && aa == T_CYS) f |= R_SG;
-        }
-        if (ref > 0.0 && rel >= a.exposed * ref) f |= R_EXPOSED;
+        const double ref = a.ref[aa], rel = sidechain_rel_area(s, a.radius, pts, a.a, r, aa);
+        if (aa == T_CYS && a.radius[aa * 14 + 5] > 0.f && s.exists(r, 5, aa)) f |= R_SG;
+        if (row_exposed(rel, ref, a.exposed)) f |= R_EXPOSED;
         info[r] = f;
         if (a.rows) {
             double* o = a.rows + ((long long)b * L + r) * 4;
@@ -217,12 +194,7 @@ __global__ __launch_bounds__(NT) void dev_reduce_kernel(const AbxDevelopabilityA
             o[1] = ref > 0.0 ? rel / ref : 0.0;
         }
     }
-    best = fmax(best, __shfl_xor(best, 32, 64));
-    best = fmax(best, __shfl_xor(best, 16, 64));
-    best = fmax(best, __shfl_xor(best, 8, 64));
-    best = fmax(best, __shfl_xor(best, 4, 64));
-    best = fmax(best, __shfl_xor(best, 2, 64));
-    best = fmax(best, __shfl_xor(best, 1, 64));
+    best = wave_max_d(best);
     if (lane == 0) wmax[wv] = best;
     __syncthreads();
     // ---- links (both rows present)
@@ -268,7 +240,7 @@ __global__ __launch_bounds__(NT) void dev_reduce_kernel(const AbxDevelopabilityA
                 if (f & R_REGION) atomicAdd(&cnt[18], nl);
                 if (f & R_CDR) atomicAdd(&cnt[19], nl);
             }
-            charge = (aa == T_LYS || aa == T_ARG ? 1 : 0) - (aa == T_ASP || aa == T_GLU ? 1 : 0);
+            charge = type_charge(aa);
         }
         if (a.rows) {
             double* o = a.rows + ((long long)b * L + r) * 4;

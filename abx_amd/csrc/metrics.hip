@@ -160,19 +160,15 @@ __global__ __launch_bounds__(256) void score_row_kernel(const AbxDesignScoreArgs
     double acc[3 * NREG];
 #pragma unroll
     for (int k = 0; k < 3 * NREG; ++k) acc[k] = 0.0;
-    int h3_before = 0;                                  // CDR-H3 rows in the chunks already walked
+    int h3_before[1] = {0};                             // CDR-H3 rows in the chunks already walked
     for (int base = 0; base < Lab; base += 256) {
         const int i = base + tid;
         const int code = i < Lab ? a.cdr_def[i] : -1;
         // rank of this row among the CDR-H3 rows (sequence order, whatever their masks): the Loop slice is [4 : nh3 - 2]
-        const unsigned long long bal = __ballot(code == 5);
-        const int lane = tid & 63;
-        __syncthreads();
-        if (lane == 0) wcnt[tid >> 6] = __popcll(bal);
-        __syncthreads();
-        int rank = h3_before + __popcll(bal & ((1ull << lane) - 1ull));
-        for (int w = 0; w < (tid >> 6); ++w) rank += wcnt[w];
-        h3_before += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        const unsigned long long bal[1] = {__ballot(code == 5)};
+        int ranks[1];
+        block_rank<4, 1>(bal, wcnt, ranks, h3_before);
+        const int rank = ranks[0];
         if (i >= Lab || !ca_ok(i)) continue;
         const float* g = s.gt + ((long long)i * 14 + 1) * 3;
         const float* p = s.xyz(i, 1);

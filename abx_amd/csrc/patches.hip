@@ -9,9 +9,9 @@
 // are static LDS) and tables with 2^30 h_max^2 Lab^2 or 2^30 (q_max / 10)^2 Lab L >= 2^62.
 //
 // Three kernels, no global atomics:
-//   1. patch_flags_kernel, one workgroup per structure, one thread per row of the complex: type, presence, exposure (developability's
-//      rule), seed, region, heavy chain; the counted atoms compacted to the front of the row's 14 float4 (x, y, z | role bits) in the
-//      workspace, their number in the row's info word.
+//   1. patch_flags_kernel, one workgroup per structure, one thread per row of the complex: type, presence, exposure
+//      (residue_rules.h), seed, region, heavy chain; the counted atoms compacted to the front of the row's 14 float4 (x, y, z | role
+//      bits) in the workspace, their number in the row's info word.
 //   2. patch_pair_kernel, the hot path, grid (tile of 256 j-rows, tile of TI = 16 antibody i-rows, structure): one lane per j-row with its
 //      atoms in registers as float64 (slots beyond its count at +inf: their distances are +inf and never the minimum), the atoms of the
 //      i-rows in LDS, every lane reads the same address - a broadcast.  D2[i][j] to the (Lab, L) float64 plane of the workspace, and per
@@ -21,6 +21,8 @@
 //      j-row; int64 sums through LDS), SFvCSP, the cross terms, the per-row shares; writes the row and the optional (L, 4) table.
 #include "common.h"
 #include "abx_hip.h"
+#include "reduce_dev.h"
+#include "residue_rules.h"
 #include "structure_dev.h"
 #include <cmath>
 
@@ -32,7 +34,6 @@ constexpr int NT = 256;                // threads of every workgroup
 constexpr int NW = NT / 64;
 constexpr int TI = 16;                 // antibody rows of a pair tile
 constexpr int MAX_L = 2048;            // rows of a structure: the row tables of patch_reduce_kernel (56 KB of LDS)
-constexpr double FIXED_ONE = 1073741824.0;     // 2^30
 // bits of a row's info word: type in bits 0-4, the number of counted atoms in bits 16-19
 constexpr int R_PRESENT = 1 << 5, R_EXPOSED = 1 << 6, R_SEED = 1 << 7, R_VICINITY = 1 << 8, R_SALT = 1 << 9, R_REGION = 1 << 10,
               R_HEAVY = 1 << 11, R_CDR = 1 << 12;
@@ -60,8 +61,6 @@ __device__ __forceinline__ Block block_of(void* ws, int b, int L, int Lab) {
     return k;
 }
 
-__device__ __forceinline__ bool is_cdr(int c) { return c == 1 || c == 3 || c == 5 || c == 8 || c == 10 || c == 12; }
-
 __global__ __launch_bounds__(NT) void patch_flags_kernel(const AbxPatchArgs a, void* ws) {
     const int b = blockIdx.x, L = a.L, Lab = a.Lab;
     const Structure s(a, b);
@@ -72,23 +71,21 @@ __global__ __launch_bounds__(NT) void patch_flags_kernel(const AbxPatchArgs a, v
         const int aa = s.aatype(r);
         float4* at = k.atoms + 14ll * r;
         int n = 0;
-        double rel = 0.0;
         for (int sl = 0; sl < 14; ++sl) {
             const bool counted = a.radius[aa * 14 + sl] > 0.f && s.exists(r, sl, aa);
             if (counted) {
                 const float* x = s.xyz(r, sl);
                 at[n++] = make_float4(x[0], x[1], x[2], __int_as_float(a.table[aa * 14 + sl] & ROLES));
             }
-            if (sl >= 4) rel = rel + (double)(counted ? pts[2 * (r * 14 + sl)] : 0) * a.a[aa * 14 + sl];
         }
         for (int e = n; e < 14; ++e) at[e] = make_float4(0.f, 0.f, 0.f, 0.f);
         int f = aa | n << 16;
         if (n) {
             f |= R_PRESENT | (a.region && a.region[r] ? R_REGION : 0);
             if (r < Lab) {
-                const double ref = a.ref[aa];
-                f |= (a.chain_id[r] == heavy ? R_HEAVY : 0) | (is_cdr(a.cdr_def[r]) ? R_CDR : 0);
-                if (ref > 0.0 && rel >= a.exposed * ref) f |= R_EXPOSED | (is_cdr(a.cdr_def[r]) ? R_SEED : 0);
+                const bool cdr = is_cdr(a.cdr_def[r]);
+                f |= (a.chain_id[r] == heavy ? R_HEAVY : 0) | (cdr ? R_CDR : 0);
+                if (row_exposed(sidechain_rel_area(s, a.radius, pts, a.a, r, aa), a.ref[aa], a.exposed)) f |= R_EXPOSED | (cdr ? R_SEED : 0);
             }
         }
         k.info[r] = f;
@@ -152,8 +149,6 @@ __global__ __launch_bounds__(NT) void patch_pair_kernel(const AbxPatchArgs a, vo
     }
     if (j < Lab) k.salt[(long long)blockIdx.y * Lab + j] = salted ? 1 : 0;
 }
-
-__device__ __forceinline__ void lds_add(unsigned long long* p, long long v) { atomicAdd(p, (unsigned long long)v); }
 
 __global__ __launch_bounds__(NT) void patch_reduce_kernel(const AbxPatchArgs a, void* ws) {
     __shared__ int info[MAX_L];

@@ -16,6 +16,7 @@
 #include "abx_hip.h"
 #include "reduce_dev.h"
 #include "structure_dev.h"
+#include "surface_dev.h"
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -25,7 +26,6 @@ namespace {
 constexpr int NT = 1024;               // threads of the workgroup
 constexpr int NW = NT / 64;            // its waves
 constexpr int PER_RES = 5;             // table entries per residue row the LDS is sized for
-constexpr double FOUR_PI = 12.566370614359172;
 constexpr int NCNT = 16;               // integer counters (the columns 0-9 and 12)
 
 // flags of a table entry (float4.w of the atom): the role bits of `table`, then
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(NT) void polar_kernel(const AbxPolarArgs a, double 
     __syncthreads();
     // ---- 1. the table, in slot order
     const float* pred = a.pred_atom14 + (long long)b * a.pred_sb;
-    int before = 0;
+    int found[1] = {0};
     for (int base = 0; base < N14; base += NT) {
         const int k = base + tid;
         bool ok = false;
@@ -88,23 +88,16 @@ __global__ __launch_bounds__(NT) void polar_kernel(const AbxPolarArgs a, double 
                 an = make_float4(x[3 * as], x[3 * as + 1], x[3 * as + 2], 0.f);
             }
         }
-        const unsigned long long bal = __ballot(ok);
-        __syncthreads();                                // the previous chunk's counts have been read
-        if (lane == 0) wcnt[wv] = __popcll(bal);
-        __syncthreads();
-        int idx = before + lanes_below(bal), all = 0;
-        for (int v = 0; v < NW; ++v) {
-            const int c = wcnt[v];
-            idx += v < wv ? c : 0;
-            all += c;
-        }
-        before += all;
+        const unsigned long long bal[1] = {__ballot(ok)};
+        int rank[1];
+        block_rank<NW, 1>(bal, wcnt, rank, found);
+        const int idx = rank[0];
         if (ok && idx < cap) {                          // (a table with more than PER_RES polar atoms per residue is cut, never overrun)
             A[idx] = at;
             U[idx] = an;
         }
     }
-    const int n = before < cap ? before : cap;
+    const int n = found[0] < cap ? found[0] : cap;
     __syncthreads();
     // the region bit and the point counts of the entries
     for (int i = tid; i < n; i += NT) {
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(NT) void polar_kernel(const AbxPolarArgs a, double 
             const float r = a.radius[aa * 14 + sl];
             if (!(r > 0.f && ex[k])) continue;
             const double R = (double)r + a.probe;
-            const double area = FOUR_PI * (R * R) * (double)(pts[2 * k] - pts[2 * k + 1]) / (double)a.P;
+            const double area = points_area(R, (double)(pts[2 * k] - pts[2 * k + 1]), (double)a.P);
             if (a.table[aa * 14 + sl] & ABX_POLAR_ELEMENT) pol += area;
             else apol += area;
         }

@@ -1,6 +1,7 @@
-// Wave and block helpers of the per-design analyses (metrics.hip, accuracy.hip, interface.hip, polar.hip): fixed-order sums, ballot
-// ranks and the superposition by Horn's quaternion.  ensemble.hip is not a user: its Jacobi is a register-resident formulation of
-// its own with another rotation order, and its results are pinned bit for bit by the ensemble tests.
+// Wave and block helpers of the per-design analyses: fixed-order sums (metrics, accuracy, interface, torsions), ballot ranks over a
+// block (metrics, interface, polar, developability, shape), lds_add (developability, patches) and the superposition by Horn's
+// quaternion (metrics, accuracy).  ensemble.hip is not a user: its Jacobi is a register-resident formulation of its own with another
+// rotation order, and its results are pinned bit for bit by the ensemble tests.
 #pragma once
 #include "common.h"
 
@@ -14,6 +15,58 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 __device__ __forceinline__ int lanes_below(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
+
+__device__ __forceinline__ int wave_scan_i(int v, int lane) {       // inclusive
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o, 64);
+        v += lane >= o ? t : 0;
+    }
+    return v;
+}
+
+// N integer columns over the NW waves of the block, chunk after chunk: `total` runs over the calls (zero before the first one).
+// before[k] grows by total[k] on entry + the totals of the waves below this thread's (the caller puts the thread's place in its own
+// wave there); total[k] grows by those of all waves.
+// wave_totals[k] is read from lane 63 of every wave (the last lane of an inclusive scan; a popcount of a ballot is the same in every
+// lane).  Called by every thread of the block: two barriers, the first one frees `sh` ([NW][N] ints) from its previous use.
+template <int NW, int N>
+__device__ __forceinline__ void block_offsets(const int (&wave_totals)[N], int* sh, int (&before)[N], int (&total)[N]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 63) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) sh[wv * N + k] = wave_totals[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) before[k] += total[k];
+#pragma nounroll                                        // (unrolled, the NW * N loads are in flight at once: 7 VGPRs more at N = 6)
+    for (int u = 0; u < NW; ++u) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const int c = sh[u * N + k];
+            before[k] += u < wv ? c : 0;
+            total[k] += c;
+        }
+    }
+}
+
+// rank[k] = total[k] on entry + the set bits of ballot k in the lanes and waves of the block below this thread; total[k] grows by all
+// of them.  As block_offsets.
+template <int NW, int N>
+__device__ __forceinline__ void block_rank(const unsigned long long (&ballots)[N], int* sh, int (&rank)[N], int (&total)[N]) {
+    int wave_totals[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        wave_totals[k] = __popcll(ballots[k]);
+        rank[k] = lanes_below(ballots[k]);
+    }
+    block_offsets<NW, N>(wave_totals, sh, rank, total);
+}
+
+// a signed 64-bit sum in LDS (two's complement)
+__device__ __forceinline__ void lds_add(unsigned long long* p, long long v) { atomicAdd(p, (unsigned long long)v); }
 
 // Sum of N doubles per thread over the 256 threads of the block, in a fixed order; every thread returns with the totals in v.
 // `sh`: [4][N] doubles.

@@ -9,8 +9,8 @@
 //   shape_offsets_kernel  one workgroup per structure: the atom table of the interface kernel (x, y, z, radius; slot index << 1 | side),
 //                         the interface atoms with the offsets of their buried and open dots (prefix sums in atom order), the list
 //                         sizes; a structure whose sizes exceed max_dots, or whose `points` cannot be, is marked and skipped from here on.
-//   shape_dots_kernel     one wave per interface atom, the structure's atom table in LDS: the neighbour scan and the point test of
-//                         iface_points_kernel, then the buried dots go to the I list and the open ones to the E list of the atom's side
+//   shape_dots_kernel     one wave per interface atom, the structure's atom table in LDS: the point test of surface_dev.h, the one that
+//                         iface_points_kernel runs, then the buried dots go to the I list and the open ones to the E list of the atom's side
 //                         by ballot prefix sums over the points in ascending order.  A wave never writes past the segment that
 //                         `points` promised; an atom whose counts disagree marks the structure.
 //   shape_trim_kernel     one workgroup per (side, structure): a buried dot with an open dot of its side within `trim` goes; the E list
@@ -25,6 +25,7 @@
 #include "abx_hip.h"
 #include "reduce_dev.h"
 #include "structure_dev.h"
+#include "surface_dev.h"
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -36,18 +37,15 @@ constexpr int NW = NT / 64;
 constexpr int NTD = 1024;              // threads of the dot kernel
 constexpr int NWD = NTD / 64;
 constexpr int DOT_BLOCKS = 4;          // workgroups of the dot kernel per structure (64 waves for a few hundred interface atoms)
-constexpr int CAP = 192;               // neighbour list entries per wave (worked off when fewer than 64 are free)
 constexpr int NTT = 1024;              // threads of the trim kernel = open dots per LDS chunk
 constexpr int NWT = NTT / 64;
 constexpr int J_CHUNK = 1024;          // default and largest chunk of the other side's dots in the match kernel
 constexpr int MATCH_TILES = 8;         // most workgroups of the match kernel per (side, structure): each walks the tiles tile, tile + 8, ...
 constexpr int MAX_DOTS = 1 << 20;
-constexpr double SLACK = 1e-3;         // Angstrom added to R_a + R_b in the neighbour prefilter (interface.hip)
 
 struct Dot { double x, y, z; int info, pad; };      // a buried dot: position, row << 10 | point
 struct Open { double x, y, z; };                    // an open dot: position
 
-__host__ __device__ constexpr long long dots_lds_bytes(int L) { return 14ll * L * 20 + NWD * CAP * 4; }
 // bytes of one structure's workspace: header (64), float4 table, int4 per interface atom, int tag, then per side and dot of capacity:
 // I (32), E (24), S (8), d2 (8) - a multiple of 16
 __host__ __device__ constexpr long long ws_stride(int L, int M) { return (64 + 14ll * L * 36 + 144ll * M + 15) / 16 * 16; }
@@ -75,37 +73,22 @@ struct Workspace {
     __device__ __forceinline__ bool skipped() const { return hdr[H_BAD] != 0 || hdr[H_MISMATCH] != 0; }
 };
 
-__device__ __forceinline__ int wave_scan_i(int v, int lane) {       // inclusive
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        v += lane >= o ? t : 0;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(NT) void shape_offsets_kernel(const AbxShapeArgs a, unsigned char* __restrict__ ws) {
-    __shared__ int wtot[NW][6];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, N14 = a.L * 14;
+    __shared__ int wtot[NW * 6];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, N14 = a.L * 14;
     const Structure s(a, b);
     const Workspace w(ws, b, a.L, a.max_dots);
     const int* pts = a.points + (long long)b * a.L * 28;
-    int ntab = 0, natom = 0, run[4] = {0, 0, 0, 0};     // atoms, interface atoms, dots so far: I of side A, E of A, I of B, E of B
+    // so far: dots I of side A, E of A, I of B, E of B, then atoms and interface atoms
+    int run[6] = {0, 0, 0, 0, 0, 0};
     bool bad = false;
     for (int base = 0; base < N14; base += NT) {
         const int k = base + tid;
-        bool ok = false, sel = false, sideB = false;
+        bool ok = false, sel = false;
         float4 at = make_float4(0.f, 0.f, 0.f, 0.f);
-        int nb = 0, ne = 0;
+        int tag = 0, nb = 0, ne = 0;
         if (k < N14) {
-            const int row = k / 14, sl = k - row * 14, aa = s.aatype(row);
-            const float r = s.radius[aa * 14 + sl];
-            ok = r > 0.f && s.exists(row, sl, aa);
-            sideB = row >= a.Lab;
-            if (ok) {
-                const float* x = s.xyz(row, sl);
-                at = make_float4(x[0], x[1], x[2], r);
-            }
+            ok = table_entry(s, k, a.Lab, at, tag);
             const int alone = pts[2 * k], cplx = pts[2 * k + 1];
             if (alone < 0 || cplx < 0 || alone > a.P || cplx > alone) bad = true;
             else if (alone > cplx) {
@@ -116,43 +99,29 @@ __global__ __launch_bounds__(NT) void shape_offsets_kernel(const AbxShapeArgs a,
                 } else bad = true;                          // buried dots of an atom that is not there
             }
         }
+        const bool sideB = tag & 1;
         const unsigned long long bo = __ballot(ok), bs = __ballot(sel);
-        int v[4], inc[4];
-        v[0] = sideB ? 0 : nb; v[1] = sideB ? 0 : ne; v[2] = sideB ? nb : 0; v[3] = sideB ? ne : 0;
+        const int v[4] = {sideB ? 0 : nb, sideB ? 0 : ne, sideB ? nb : 0, sideB ? ne : 0};
+        int col[6], off[6];                                 // inclusive scans (lane 63: the wave's totals), exclusive places
 #pragma unroll
-        for (int q = 0; q < 4; ++q) inc[q] = wave_scan_i(v[q], lane);
-        __syncthreads();                                // the previous chunk's totals have been read
-        if (lane == 63) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) wtot[wv][q] = inc[q];
-            wtot[wv][4] = __popcll(bo);
-            wtot[wv][5] = __popcll(bs);
+        for (int q = 0; q < 4; ++q) {
+            col[q] = wave_scan_i(v[q], lane);
+            off[q] = col[q] - v[q];
         }
-        __syncthreads();
-        int idx = ntab + lanes_below(bo), ia = natom + lanes_below(bs), off[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) off[q] = run[q] + inc[q] - v[q];
-        for (int u = 0; u < NW; ++u) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                off[q] += u < wv ? wtot[u][q] : 0;
-                run[q] += wtot[u][q];
-            }
-            idx += u < wv ? wtot[u][4] : 0;
-            ia += u < wv ? wtot[u][5] : 0;
-            ntab += wtot[u][4];
-            natom += wtot[u][5];
-        }
+        col[4] = __popcll(bo); off[4] = lanes_below(bo);
+        col[5] = __popcll(bs); off[5] = lanes_below(bs);
+        block_offsets<NW, 6>(col, wtot, off, run);
+        const int idx = off[4], ia = off[5];
         if (ok) {
             w.tab[idx] = at;
-            w.tag[idx] = (k << 1) | (sideB ? 1 : 0);
+            w.tag[idx] = tag;
         }
         if (sel) w.atoms[ia] = make_int4(idx, sideB ? off[2] : off[0], sideB ? off[3] : off[1], (nb << 16) | ne);   // ia < N14
     }
     const bool any_bad = __syncthreads_or(bad ? 1 : 0) != 0;
     if (tid == 0) {
-        w.hdr[H_NTAB] = ntab;
-        w.hdr[H_NATOM] = natom;
+        w.hdr[H_NTAB] = run[4];
+        w.hdr[H_NATOM] = run[5];
         w.hdr[H_NI] = run[0]; w.hdr[H_NI + 1] = run[2];
         w.hdr[H_NE] = run[1]; w.hdr[H_NE + 1] = run[3];
         w.hdr[H_NT] = 0; w.hdr[H_NT + 1] = 0;
@@ -164,90 +133,28 @@ __global__ __launch_bounds__(NT) void shape_offsets_kernel(const AbxShapeArgs a,
 
 __global__ __launch_bounds__(NTD) void shape_dots_kernel(const AbxShapeArgs a, unsigned char* __restrict__ ws) {
     extern __shared__ __align__(16) unsigned char lds[];
-    const int N14 = a.L * 14, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.y, P = a.P;
-    float4* tab = reinterpret_cast<float4*>(lds);                       // [n] x, y, z, radius
-    int* tag = reinterpret_cast<int*>(lds + 16ll * N14);                // [n] slot index << 1 | side
-    int* list = reinterpret_cast<int*>(lds + 20ll * N14) + wv * CAP;    // this wave's neighbours: table index | other side << 31
-    const Workspace w(ws, b, a.L, a.max_dots);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, P = a.P;
+    const Workspace w(ws, blockIdx.y, a.L, a.max_dots);
     if (w.hdr[H_BAD]) return;
-    const int n = w.hdr[H_NTAB], natom = w.hdr[H_NATOM];
+    const int natom = w.hdr[H_NATOM];
     if ((int)blockIdx.x * NWD >= natom) return;         // the whole workgroup: no barrier has been passed
-    for (int i = tid; i < n; i += NTD) {
-        tab[i] = w.tab[i];
-        tag[i] = w.tag[i];
-    }
-    __syncthreads();
-    const double probe = a.probe;
+    const TableLds t(lds, a.L, NTD, w.tab, w.tag, w.hdr[H_NTAB]);
     const int npass = (P + 63) >> 6;
     for (int q = blockIdx.x * NWD + wv; q < natom; q += gridDim.x * NWD) {
         const int4 ent = w.atoms[q];
         const int ia = ent.x;
-        const float4 me = tab[ia];
-        const int mtag = tag[ia], mside = mtag & 1;
-        const double xa = (double)me.x, ya = (double)me.y, za = (double)me.z, ra = (double)me.w, Ra = (double)me.w + probe;
-        // bit k of a mask: this lane's point k * 64 + lane.  alive: occluded by no own-side atom so far; crossed: by an other-side one
-        unsigned alive = 0, crossed = 0;
-        for (int k = 0; k < npass; ++k) alive |= (k * 64 + lane < P ? 1u : 0u) << k;
-        int cnt = 0;
-
-        // the points of this atom against the cnt neighbours of the list (interface.hip, the same operations)
-        auto work_off = [&]() {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");     // the list entries of the other lanes (one wave: in order)
-            __builtin_amdgcn_wave_barrier();
-            for (int k = 0; k < npass; ++k) {
-                bool live = (alive >> k) & 1u;
-                if (__ballot(live) == 0ull) continue;
-                const int p = min(k * 64 + lane, P - 1);
-                const double px = xa + Ra * a.sphere[3 * p], py = ya + Ra * a.sphere[3 * p + 1], pz = za + Ra * a.sphere[3 * p + 2];
-                bool cross = false;
-                for (int j = 0; j < cnt; ++j) {
-                    const int e = list[j];
-                    const float4 o = tab[e & 0x7fffffff];
-                    const double dx = px - (double)o.x, dy = py - (double)o.y, dz = pz - (double)o.z;
-                    const double d2 = (dx * dx + dy * dy) + dz * dz;
-                    const double Rb = (double)o.w + probe;
-                    if (live && d2 < Rb * Rb) {
-                        if (e < 0) cross = true;
-                        else live = false;
-                    }
-                    if (__ballot(live) == 0ull) break;
-                }
-                if (!live) alive &= ~(1u << k);
-                if (cross) crossed |= 1u << k;
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");     // the list is free again
-        };
-
-        bool dead = false;                              // no point is left
-        for (int base = 0; base < n && !dead; base += 64) {
-            const int j = base + lane;
-            bool nb = false, other = false;
-            if (j < n && j != ia) {
-                const float4 o = tab[j];
-                other = (tag[j] & 1) != mside;
-                const double dx = xa - (double)o.x, dy = ya - (double)o.y, dz = za - (double)o.z;
-                const double d2 = (dx * dx + dy * dy) + dz * dz;
-                const double rs = (Ra + ((double)o.w + probe)) + SLACK;
-                nb = d2 < rs * rs;
-            }
-            const unsigned long long bal = __ballot(nb);
-            if (nb) list[cnt + lanes_below(bal)] = j | (other ? (int)0x80000000 : 0);
-            cnt += __popcll(bal);
-            if (cnt > CAP - 64) {
-                work_off();
-                cnt = 0;
-                dead = __ballot(alive != 0u) == 0ull;
-            }
-        }
-        if (cnt > 0 && !dead) work_off();
+        // the masks that iface_points_kernel counted into `points`: the same function
+        const PointMasks m = point_test<false>(t, ia, a.sphere, P, a.probe, 0.0);
+        const float4 me = t.tab[ia];
+        const int mtag = t.tag[ia], mside = mtag & 1;
+        const double xa = (double)me.x, ya = (double)me.y, za = (double)me.z, ra = (double)me.w;
         // the dots, points ascending: buried ones to the I segment, open ones to the E segment that `points` promised
         const int want_b = ent.w >> 16, want_e = ent.w & 0xffff, row = (mtag >> 1) / 14;
         Dot* I = w.I + (long long)mside * w.M + ent.y;
         Open* E = w.E + (long long)mside * w.M + ent.z;
         int nb = 0, ne = 0;
         for (int k = 0; k < npass; ++k) {
-            const bool live = (alive >> k) & 1u, cr = (crossed >> k) & 1u;
+            const bool live = (m.alive >> k) & 1u, cr = (m.crossed >> k) & 1u;
             const bool bur = live && cr, op = live && !cr;
             const unsigned long long bb = __ballot(bur), be = __ballot(op);
             const int p = min(k * 64 + lane, P - 1);
@@ -273,14 +180,14 @@ __global__ __launch_bounds__(NTD) void shape_dots_kernel(const AbxShapeArgs a, u
 __global__ __launch_bounds__(NTT) void shape_trim_kernel(const AbxShapeArgs a, unsigned char* __restrict__ ws) {
     __shared__ double ex[NTT], ey[NTT], ez[NTT];
     __shared__ int wcnt[NWT];
-    const int side = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int side = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const Workspace w(ws, b, a.L, a.max_dots);
     if (w.skipped()) return;
     const int nI = w.hdr[H_NI + side], nE = w.hdr[H_NE + side];
     Dot* I = w.I + (long long)side * w.M;
     const Open* E = w.E + (long long)side * w.M;
     const double t2 = a.trim * a.trim;
-    int kept = 0;
+    int kept[1] = {0};
     for (int base = 0; base < nI; base += NTT) {
         const int i = base + tid;
         Dot d;
@@ -304,18 +211,12 @@ __global__ __launch_bounds__(NTT) void shape_trim_kernel(const AbxShapeArgs a, u
                     }
                 }
         }
-        const unsigned long long bal = __ballot(keep);
-        __syncthreads();                                // every dot of this chunk is in registers; the previous counts have been read
-        if (lane == 0) wcnt[wv] = __popcll(bal);
-        __syncthreads();
-        int idx = kept + lanes_below(bal);
-        for (int u = 0; u < NWT; ++u) {
-            idx += u < wv ? wcnt[u] : 0;
-            kept += wcnt[u];
-        }
-        if (keep) I[idx] = d;                           // in place: idx <= i
+        const unsigned long long bal[1] = {__ballot(keep)};
+        int idx[1];
+        block_rank<NWT, 1>(bal, wcnt, idx, kept);       // (its first barrier: every dot of this chunk is in registers)
+        if (keep) I[idx[0]] = d;                        // in place: idx <= i
     }
-    if (tid == 0) w.hdr[H_NT + side] = kept;
+    if (tid == 0) w.hdr[H_NT + side] = kept[0];
 }
 
 __global__ __launch_bounds__(NT) void shape_match_kernel(const AbxShapeArgs a, unsigned char* __restrict__ ws, int chunk) {
@@ -488,13 +389,13 @@ extern "C" int abx_shape_scores(const AbxShapeArgs* ap, void* workspace, hipStre
     ABX_REQUIRE(std::isfinite(a.weight) && a.weight >= 0.0, "abx_shape_scores: weight must be >= 0");
     ABX_REQUIRE(a.max_dots >= 1 && a.max_dots <= MAX_DOTS, "abx_shape_scores: max_dots must be in 1..1048576");
     ABX_REQUIRE(a.j_chunk >= 0 && a.j_chunk <= J_CHUNK, "abx_shape_scores: j_chunk must be in 0..1024");
-    ABX_REQUIRE(dots_lds_bytes(a.L) <= ABX_LDS_LIMIT, "abx_shape_scores: the atom table does not fit the LDS of a CU (L <= 541)");
+    ABX_REQUIRE(table_lds_bytes(a.L, NWD) <= ABX_LDS_LIMIT, "abx_shape_scores: the atom table does not fit the LDS of a CU (L <= 541)");
     unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
     const int chunk = a.j_chunk ? a.j_chunk : J_CHUNK;
     hipLaunchKernelGGL(shape_offsets_kernel, dim3(a.B), dim3(NT), 0, st, a, ws);
     if (int rc = abx_check_launch("abx_shape_scores(offsets)")) return rc;
     if (int rc = abx_ensure_dynamic_lds(reinterpret_cast<const void*>(shape_dots_kernel), ABX_LDS_LIMIT, "abx_shape_scores")) return rc;
-    hipLaunchKernelGGL(shape_dots_kernel, dim3(DOT_BLOCKS, a.B), dim3(NTD), (int)dots_lds_bytes(a.L), st, a, ws);
+    hipLaunchKernelGGL(shape_dots_kernel, dim3(DOT_BLOCKS, a.B), dim3(NTD), (int)table_lds_bytes(a.L, NWD), st, a, ws);
     if (int rc = abx_check_launch("abx_shape_scores(dots)")) return rc;
     hipLaunchKernelGGL(shape_trim_kernel, dim3(2, a.B), dim3(NTT), 0, st, a, ws);
     if (int rc = abx_check_launch("abx_shape_scores(trim)")) return rc;

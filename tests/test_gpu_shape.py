@@ -124,6 +124,35 @@ def test_point_densities(ops, P):
         assert np.abs(got[0, 1:3].numpy() - np.array(SC.DENSITY_512)).max() <= 1e-3
 
 
+@pytest.mark.parametrize('P,buried_atoms,kept,trimmed', [(65, 102, [39, 46], [144, 125]), (128, 115, [61, 48], [302, 309])])
+def test_shared_point_test_at_its_edges(ops, P, buried_atoms, kept, trimmed):
+    """The point test that iface_points_kernel and shape_dots_kernel share (csrc/surface_dev.h) at the smallest case that crosses its
+    edges: 16 Trp rows (Lab = 8, all 14 slots) in a 7 A box.  Every one of the 224 atoms has 92 to 223 neighbours inside the prefilter,
+    so its 192-entry list is worked off and refilled with a remainder, and the 224 atoms are three and a half 64-atom steps of the scan.
+    P = 65: a second pass over the points with one live lane.  The point counts and the interface row equal interface_host's; the shape
+    row on those counts equals shape_host's (a disagreement of the two kernels would make it eleven -1).  The literals are the host's."""
+    from abx_amd import interface, shape
+    L, Lab = 16, 8
+    x = (torch.rand(L, 14, 3, generator=torch.Generator().manual_seed(5)) * 7.0).float()
+    aa, mask = torch.full((L,), 17, dtype=torch.int64), torch.ones(L, 14, dtype=torch.bool)
+    batch = {'seq': aa.to(DEV), 'atom14_gt_positions': x.to(DEV), 'atom14_gt_exists': mask.to(DEV), 'anchor_flag': torch.zeros(Lab)}
+    it = interface.InterfaceScorer(batch, region=torch.zeros(L), n_points=P)
+    sc = shape.ShapeScorer(batch, region=torch.zeros(L), n_points=P, interface=it)
+    xa, sq = x[None, :Lab].to(DEV), aa[None, :Lab].to(DEV)
+    pts = sc.new_points(1)
+    irow = it.score(xa, sq, points=pts).cpu()[0]
+    srow = sc.score(xa, sq, points=pts).cpu()[0]
+    hrow, hpts = interface.interface_host(x, mask, aa, Lab, n_points=P)
+    print('P', P, 'interface', irow.tolist(), 'shape', srow.tolist())
+    assert torch.equal(pts.cpu()[0], torch.from_numpy(hpts))
+    assert int((hpts[..., 0] > hpts[..., 1]).sum()) == buried_atoms
+    assert_row(irow, hrow, list(range(6, 12)), list(range(6)), 1e-10, ('interface', P))
+    assert irow[9] == 4349 and irow[11] == 224
+    want = shape.shape_host(x, mask, aa, Lab, points=hpts, n_points=P)
+    assert_row(srow, want, EQUAL, CLOSE, RTOL, ('shape', P))
+    assert srow.tolist() != [-1.0] * 11 and srow[6:8].tolist() == kept and srow[9:].tolist() == trimmed
+
+
 def test_lds_chunks_give_the_same_rows(ops):
     """j_chunk = 64 on 6ct7: nine chunks of the antigen's 532 kept dots with a ragged last one (and three tiles of 256 of them as the
     matched side, the last one ragged too) give the bits of the default chunk; so do 1 and 100."""
